@@ -6,7 +6,13 @@ Laplacian with 64 right-hand sides.  One "step" = one batched apply X = M^{-1} B
 multilevel hierarchy (prec_solve, reference src/hif/alg/prec_solve.hpp:332-412) over one [n][64]
 block that is already resident in HBM; `value` counts RHS-applies per second over all ranks.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up (host factorization, import, upload), warms up, times the K steps and prints one JSON line:
+`value`, `ms_per_step` (wall clock of the K steps / K) and the workload's `config`.  --dump-outputs DIR writes
+X of the last timed step (bench.py dump_outputs).  --full adds everything else after the timed steps: the roofline
+(HIP-event apply time, algorithmic bytes, committed profiles), the CPU baselines, parity against the oracle, the
+other parameter set, the exact engine mode, narrow and wide batches and, for N > 1, the strong split and the gather.
 
 N > 1 without WORLD_SIZE in the environment: this process starts the N ranks itself (python -m
 torch.distributed.run --nproc-per-node N ... bench.py, as a CHILD, before anything here touches torch or the GPU),
@@ -14,15 +20,15 @@ relays rank 0's JSON line and exits with the child's code.  Launched by torch.di
 it is one of the ranks; --gpus must then equal WORLD_SIZE.
 
 Multi-GPU: the path shards over right-hand sides only.  Every rank holds the whole
-hierarchy and applies it to its OWN 64-column block: weak scaling, no collective in the data path;
-one RCCL all_gather of the solution blocks after the timed region (reported as gather_ms).  The STRONG
-split of one 64-column batch (64/N columns per GPU) is timed as well and reported as `strong_scaling`: shards of
+hierarchy and applies it to its OWN 64-column block: weak scaling, no collective in the data path.
+With --full, one RCCL all_gather of the solution blocks follows the timed region (reported as gather_ms), and the
+STRONG split of one 64-column batch (64/N columns per GPU) is timed and reported as `strong_scaling`: shards of
 fewer than 49 columns run the 16-column-slice kernels (about 2.7 ms for 8 columns against 3.9 ms for 64).
 
 Hierarchy: factorization is not part of the measured path and stays on the host (north_star).
-When the compiled reference is present (oracle/_ref, the GPU box gets it as a prebuilt binary) the
-cpu_baseline leg factorizes the matrix with the REAL reference and times the reference's own
-single-RHS solve; the hierarchy it produced is then handed to the HIP path field by field through
+When the compiled reference is present (oracle/_ref, built beside the checkout and carried with it as a
+prebuilt binary) the REAL reference factorizes the matrix (with --full, the cpu_baseline leg also times the
+reference's own single-RHS solve); the hierarchy it produced is then handed to the HIP path field by field through
 the import ABI -- exactly the deployment contract of INTEGRATION.md (reference factorizes, GPU
 applies), so GPU and CPU numbers refer to the same factors.  For N > 1 rank 0 factorizes, writes the
 imported hierarchy in the library's on-disk format (hifamd_save) and the other ranks replay that file
@@ -91,20 +97,30 @@ def lib_fingerprint():
     return hashlib.sha256(open(p, "rb").read()).hexdigest() if os.path.exists(p) else None
 
 
+def reference_factorize(A, pname):
+    """-> (R, seconds): the compiled reference (oracle/_ref) factorizes the workload on the host, or (None, None)
+    where it is absent."""
+    from oracle import ref
+
+    if not ref.available():
+        return None, None
+    P = PARAM_SETS[pname]
+    t0 = time.time()
+    R = ref.RefHIF(A.indptr, A.indices, A.data, None if P is None else ref.make_params(**P))
+    return R, time.time() - t0
+
+
 def cpu_baseline_leg(A, pname, budget_s):
-    """The ONLY place bench.py touches oracle/: times the reference's CPU path (1 thread, as
+    """--full: times the reference's CPU path (1 thread, as
     prec_solve is serial) on a bounded sample of single-RHS solves of the SAME workload, and returns
     the factors it built so that the GPU leg applies the identical hierarchy."""
-    from oracle import orc, ref
+    from oracle import orc
 
     n = A.shape[0]
     rng = np.random.default_rng(20260101)
     out = {}
-    if ref.available():
-        P = PARAM_SETS[pname]
-        t0 = time.time()
-        R = ref.RefHIF(A.indptr, A.indices, A.data, None if P is None else ref.make_params(**P))
-        t_fac = time.time() - t0
+    R, t_fac = reference_factorize(A, pname)
+    if R is not None:
         levels = R.levels()
         b = rng.uniform(-1, 1, n)
         R.solve(b)  # warm-up (sizes the reference's work buffer, builder.hpp:414-416)
@@ -163,6 +179,26 @@ def port_baseline(levels, n, budget_s):
             "ms_per_rhs": 1e3 * el / cnt}
 
 
+DUMP_BYTES = 32 << 20  # --dump-outputs: at most this much of X is written (a seeded sample of its rows beyond it)
+
+
+def dump_outputs(out_dir, X):
+    """--dump-outputs DIR: X of the last timed step as DIR/x.npy (float64, [rows][nrhs]).  A block larger than
+    DUMP_BYTES is sampled: a fixed, seeded choice of rows, ascending, whose indices go to DIR/x_rows.npy (float64)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n, k = X.shape
+    keep = max(1, DUMP_BYTES // (8 * k))
+    if n > keep:
+        rows = np.sort(np.random.default_rng(20260101).choice(n, size=keep, replace=False))
+        Xs = X.index_select(0, torch.from_numpy(rows).to(X.device))
+    else:
+        rows, Xs = np.arange(n), X
+    np.save(os.path.join(out_dir, "x.npy"), np.ascontiguousarray(Xs.cpu().numpy(), dtype=np.float64))
+    np.save(os.path.join(out_dir, "x_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -173,10 +209,18 @@ def main():
     ap.add_argument("--params", choices=list(PARAM_SETS), default="default",
                     help="reference factorization parameters: DEFAULT_PARAMS or the PDE-tuned set "
                          "(examples/advanced/demo_gmreshif.cpp:63-65)")
-    ap.add_argument("--secondary", type=int, default=1, help="also time the other parameter set (N=1 only)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget of each CPU baseline sample")
-    ap.add_argument("--extras", type=int, default=1, help="0: skip the side measurements (exact engine mode, 128-column "
-                                                          "batch, nrhs = 1) -- counter passes want the timed kernels only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: roofline (HIP-event apply "
+                         "time, committed profiles), CPU baselines, parity against the oracle, the other parameter set, "
+                         "exact engine mode, 1 / 8 / 16 / 32 / 128 / 256-column batches, strong split and gather (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write X of the last timed step to DIR/x.npy (float64; a seeded sample of its rows when larger "
+                         "than 32 MiB, their indices in DIR/x_rows.npy)")
+    ap.add_argument("--secondary", type=int, default=1, help="--full: also time the other parameter set (N=1 only)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: budget of each CPU baseline sample")
+    ap.add_argument("--extras", type=int, default=1, help="--full, 0: skip the side measurements (exact engine mode, "
+                                                          "128-column batch, nrhs = 1) -- counter passes want the timed "
+                                                          "kernels only")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to "
                                                       "rehearse the N > 1 flow on a box with fewer GPUs than ranks)")
     args = ap.parse_args()
@@ -222,7 +266,13 @@ def main():
         path = hier_cache_path(args.nx, pname)
         cpu, levels, M = None, None, None
         if rank == 0:
-            cpu, levels = cpu_baseline_leg(A, pname, args.cpu_seconds if want_cpu else 0.0)
+            if args.full:
+                cpu, levels = cpu_baseline_leg(A, pname, args.cpu_seconds if want_cpu else 0.0)
+            else:
+                R, _ = reference_factorize(A, pname)
+                if R is not None:
+                    levels = R.levels()
+                    R.close()
             if levels is not None:
                 M = hifir_amd.HIF.from_levels(levels, max_nrhs=args.nrhs, device=local_rank)
             elif os.path.exists(path):
@@ -248,13 +298,22 @@ def main():
         el = time.perf_counter() - t0
         return hd.max_over_ranks(el, device="cuda" if args.backend == "nccl" else "cpu")
 
-    def run(pname, want_cpu, steps, warmup):
+    def run(pname, want_cpu, steps, warmup, dump_dir=None):
         M, levels, cpu = get_hierarchy(pname, want_cpu)
         g = torch.Generator(device="cuda")
         g.manual_seed(20260101 + rank)
         B = (torch.rand((n, args.nrhs), dtype=torch.float64, device="cuda", generator=g) * 2 - 1)
         X = torch.empty_like(B)
         el = timed(M, B, X, steps, warmup)
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, X)
+        if not args.full:
+            # a plain run: the headline figure and what describes its workload, nothing else
+            res = dict(ms_per_step=1e3 * el / steps, value=world * args.nrhs * steps / el, setup=M.stats_ext(),
+                       stats=M.stats())
+            M.close()
+            del B, X
+            return res
         # kernel-side duration of one apply: HIP events on the stream the kernels run on
         dev_ms = M.time_apply(B, X, warmup=1, reps=max(5, steps // 2))
         balg = M.algorithmic_bytes(args.nrhs)
@@ -380,9 +439,9 @@ def main():
         return res
 
     want_cpu = (world == 1)
-    r = run(args.params, want_cpu, args.steps, args.warmup)
-    if rank == 0:
-        st = r["stats"]
+
+    def add_full_results(line, r):
+        """--full: every figure and check beside the headline one, added to rank 0's result line."""
         achieved = r["balg"] / (r["dev_ms"] * 1e-3) / 1e9
         cpu = r["cpu"]
         if want_cpu and r["levels"] is not None:
@@ -413,28 +472,7 @@ def main():
                 else:
                     traffic_note = (f"{os.path.relpath(cands[-1], ROOT)} was collected with another build of "
                                     f"libhifir_amd.so (sha256 {str(summ.get('lib_sha256'))[:12]} vs {str(lib_fingerprint())[:12]}): dropped")
-        line = {
-            "metric": "preconditioner applies/sec + achieved HBM GB/s, 1M-row 5-pt Laplacian, nrhs=64",
-            "value": r["value"], "unit": "RHS-applies/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"2-D 5-pt Poisson {args.nx}x{args.nx} (n={n}), multilevel HIFIR hierarchy factorized on "
-                                   f"the host by the reference with {args.params} parameters, batched apply X=M^-1 B, "
-                                   f"nrhs={args.nrhs} per GPU, B/X resident in HBM",
-                       "params": args.params, "nrhs_per_gpu": args.nrhs, "levels": int(st["sparse_levels"]),
-                       "dense_n": int(st["dense_n"]), "sum_n": int(st["sum_n"]), "sum_m": int(st["sum_m"]),
-                       "nnz_LU": int(st["nnz_LU"]), "nnz_EF": int(st["nnz_EF"]),
-                       "wavefronts_L": int(st["wavefronts_L"]), "wavefronts_U": int(st["wavefronts_U"]),
-                       "launches_per_apply": int(st["launches"]) if st["launches"] else None,
-                       "parallelism": f"rhs-sharded x{world} (hierarchy replicated)",
-                       # set-up cost (once per hierarchy) and what stays resident beside the factors
-                       "analysis_s": r["setup"].get("analysis_s"), "analysis_levels_from_file": r["setup"].get("analysis_cached_levels"),
-                       "finalize_s": r["setup"].get("finalize_s"), "graph_capture_ms": r["setup"].get("graph_capture_ms"),
-                       "operator_bytes": {"block_inverses": r["setup"].get("bytes_inverses"), "top_operators": r["setup"].get("bytes_top"),
-                                          "tail_operator": r["setup"].get("bytes_tail")},
-                       "tail_operator": {"rows": r["setup"].get("tail_rows"), "level": r["setup"].get("tail_level"),
-                                         "probe_relerr": r["setup"].get("tail_probe_relerr"),
-                                         "max_abs": r["setup"].get("tail_max_abs"), "rejected": r["setup"].get("tail_rejected")}},
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "traffic_note": traffic_note,
@@ -444,7 +482,7 @@ def main():
                          "launch_map": r["launch_map"], "levels_from_profile": stages},
             "cpu_baseline": cpu if world == 1 else None,  # timed on rank 0 at N = 1 only
             "parity_relerr_col0_vs_oracle": r["parity"],
-        }
+        })
         if r["gather_ms"] is not None:
             line["gather_ms"] = r["gather_ms"]
         if r.get("ranks_cached") is not None:
@@ -473,6 +511,35 @@ def main():
                                  "roofline_achieved_GBs": a2, "roofline_frac": a2 / HBM_PEAK_GBS,
                                  "algorithmic_bytes": r2["balg"], "cpu_baseline": r2["cpu"],
                                  "parity_relerr_col0_vs_oracle": r2["parity"], "exact_mode": r2["exact"]}
+
+    r = run(args.params, want_cpu, args.steps, args.warmup, args.dump_outputs)
+    if rank == 0:
+        st = r["stats"]
+        line = {
+            "metric": "preconditioner applies/sec + achieved HBM GB/s, 1M-row 5-pt Laplacian, nrhs=64",
+            "value": r["value"], "unit": "RHS-applies/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"2-D 5-pt Poisson {args.nx}x{args.nx} (n={n}), multilevel HIFIR hierarchy factorized on "
+                                   f"the host by the reference with {args.params} parameters, batched apply X=M^-1 B, "
+                                   f"nrhs={args.nrhs} per GPU, B/X resident in HBM",
+                       "params": args.params, "nrhs_per_gpu": args.nrhs, "levels": int(st["sparse_levels"]),
+                       "dense_n": int(st["dense_n"]), "sum_n": int(st["sum_n"]), "sum_m": int(st["sum_m"]),
+                       "nnz_LU": int(st["nnz_LU"]), "nnz_EF": int(st["nnz_EF"]),
+                       "wavefronts_L": int(st["wavefronts_L"]), "wavefronts_U": int(st["wavefronts_U"]),
+                       "launches_per_apply": int(st["launches"]) if st["launches"] else None,
+                       "parallelism": f"rhs-sharded x{world} (hierarchy replicated)",
+                       # set-up cost (once per hierarchy) and what stays resident beside the factors
+                       "analysis_s": r["setup"].get("analysis_s"), "analysis_levels_from_file": r["setup"].get("analysis_cached_levels"),
+                       "finalize_s": r["setup"].get("finalize_s"), "graph_capture_ms": r["setup"].get("graph_capture_ms"),
+                       "operator_bytes": {"block_inverses": r["setup"].get("bytes_inverses"), "top_operators": r["setup"].get("bytes_top"),
+                                          "tail_operator": r["setup"].get("bytes_tail")},
+                       "tail_operator": {"rows": r["setup"].get("tail_rows"), "level": r["setup"].get("tail_level"),
+                                         "probe_relerr": r["setup"].get("tail_probe_relerr"),
+                                         "max_abs": r["setup"].get("tail_max_abs"), "rejected": r["setup"].get("tail_rejected")}},
+        }
+        if args.full:
+            add_full_results(line, r)
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

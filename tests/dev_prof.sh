@@ -7,6 +7,6 @@ R=$PWD
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 \
+timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT --output-format csv -- python3 $R/bench.py --full --steps 10 --warmup 2 \
   --secondary 0 --extras 0 --cpu-seconds 1 > $R/gpurun_out/$TAG.json 2> $R/gpurun_out/$TAG.err
 tail -c 300 $R/gpurun_out/$TAG.json

@@ -194,7 +194,7 @@ if f and w:
     nf, bf = pmc(f, "FETCH_SIZE", os.path.join(src, "bench_fetch.json"))
     nw, bw = pmc(w, "WRITE_SIZE", os.path.join(src, "bench_write.json"))
     tf, tw = sum(bf.values()), sum(bw.values())
-    out = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 --warmup 1 --secondary 0 --extras 0",
+    out = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 --warmup 1 --secondary 0 --extras 0",
            "applies_profiled": [nf, nw], "unit": "KiB per 64-RHS apply (default-parameter hierarchy)",
            "FETCH_SIZE_KiB": tf, "WRITE_SIZE_KiB": tw,
            "hbm_bytes_per_apply_corrected": (2.0 * tf + tw) * 1024.0,

@@ -17,7 +17,7 @@ def test_bench_two_ranks_gloo_one_gpu(tmp_path):
     env = dict(os.environ)
     env["TMPDIR"] = str(tmp_path)  # (the hierarchy file of this run only)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--nx", "300", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--nx", "300", "--steps", "3",
            "--secondary", "0", "--extras", "0", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
