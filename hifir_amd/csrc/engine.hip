@@ -620,6 +620,7 @@ class Engine : public EngineBase {
     // completes asynchronous work on threads of its own; see DESIGN 8 on the host copy that changed twice in four rounds)
     if (stream && !is_twin) (void)hipDeviceSynchronize();
     if (gm_ctl_host) (void)hipHostFree(gm_ctl_host);
+    if (cg_pin) (void)hipHostFree(cg_pin);
 #ifdef HIFAMD_CSPROBE
     csprobe_dump();
 #endif
@@ -677,6 +678,14 @@ class Engine : public EngineBase {
     analysis_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_an0).count();
     seal_level(H);  // (what finalize must find again: import.hpp verify_level)
     host.levels.push_back(std::move(H));
+    herm_known = false;
+  }
+  // hifamd_hermitian: import.hpp check_hermitian over the host copy, computed once per imported hierarchy
+  bool herm_known = false;
+  HermCheck herm;
+  const HermCheck &hermitian() {
+    if (!herm_known) herm = check_hermitian(host), herm_known = true;
+    return herm;
   }
   int64_t host_repairs = 0;  // arrays of the host copy that verify_level found changed and rebuilt (hifamd_stats_ext slot 21)
   std::vector<LevelAnalysis<T>> cached_analysis;  // (alive during hifamd_load only)
@@ -904,6 +913,7 @@ class Engine : public EngineBase {
     if (!mat) throw Error(HIFAMD_NULL_OBJ, "NULL dense block");
     dense_factorize(host.dense, mat, nd, rrqr_cond);
     host.has_dense = true;
+    herm_known = false;
   }
 
   // LU last level of a reference built with HIF_DENSE_MODE=0 (small_scale/LUP.hpp)
@@ -915,6 +925,7 @@ class Engine : public EngineBase {
     if (!mat) throw Error(HIFAMD_NULL_OBJ, "NULL dense block");
     dense_factorize_lup(host.dense, mat, nd);
     host.has_dense = true;
+    herm_known = false;
   }
 
   // symmetric / Hermitian last level (the reference's symm_dense_solver, filled by symm_factor.hpp:654-657)
@@ -926,6 +937,7 @@ class Engine : public EngineBase {
     if (!mat) throw Error(HIFAMD_NULL_OBJ, "NULL dense block");
     dense_factorize_symm(host.dense, mat, nd, spd);
     host.has_dense = true;
+    herm_known = false;
   }
 
   // What the FIRST solve of a level (S2, prec_solve.hpp:364) need not move (round 4).  Its result y_1 only feeds the Schur
@@ -2692,6 +2704,136 @@ class Engine : public EngineBase {
     HIP_OK(hipStreamSynchronize(stream));
   }
 
+  // ---- preconditioned CG, batched over columns ------------------------------------------------------
+  // x0 = 0; r = b; z = M^{-1} r; p = z; rho = r^H z; then per step q = A p, sigma = p^H q, alpha = rho / sigma,
+  // x += alpha p, r -= alpha q, stop on ||r|| / ||b|| <= rtol, z = M^{-1} r, rho' = r^H z, p = z + (rho' / rho) p.
+  // Up to 64 columns in lock step: one batched apply, one SpMM and four fused vector passes (k_cg_*) per step, each
+  // pass followed by a one-workgroup finishing kernel; the per-column scalars live in HBM (CgState) and the host reads
+  // one integer per step (how many columns are still active) through a pinned buffer of the engine.  Only for a
+  // Hermitian M^{-1} (import.hpp check_hermitian); flags 0 converged / 1 breakdown / 2 reached maxit.
+  DevBuf cg_r, cg_z, cg_p, cg_q, cg_state;
+  int *cg_pin = nullptr;  // pinned: [0] active columns, [1, 65) iterations, [65, 129) flags
+  struct StreamWait {     // waits for the stream on every way out of a scope that enqueued work
+    hipStream_t s;
+    ~StreamWait() { (void)hipStreamSynchronize(s); }
+  };
+
+  CgState<D> cg_make_state(double rtol, int maxit) {
+    const size_t o_rho = 0, o_al = o_rho + 64 * sizeof(D), o_be = o_al + 64 * sizeof(D), o_bn = o_be + 64 * sizeof(D),
+                 o_int = o_bn + 64 * sizeof(double), bytes = o_int + (3 * 64 + 4) * sizeof(int);
+    if (cg_state.bytes < bytes) cg_state.alloc(bytes);
+    HIP_OK(hipMemsetAsync(cg_state.p, 0, bytes, stream));
+    char *b = cg_state.as<char>();
+    CgState<D> S;
+    S.rho = (D *)(b + o_rho);
+    S.alpha = (D *)(b + o_al);
+    S.beta = (D *)(b + o_be);
+    S.bnorm = (double *)(b + o_bn);
+    int *ib = (int *)(b + o_int);
+    S.iter = ib;
+    S.flag = ib + 64;
+    S.active = ib + 128;
+    S.ctl = ib + 192;
+    S.maxit = maxit;
+    S.rtol = rtol;
+    return S;
+  }
+  int cg_active(const CgState<D> &S) {
+    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return cg_pin[0];
+  }
+
+  void pcg_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank, int *flags,
+                int *iters) {
+    const int64_t n = lv[0]->n;
+    const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
+    for (DevBuf *b : {&cg_r, &cg_z, &cg_p, &cg_q})
+      if (b->bytes < vec) b->alloc(vec);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
+    D *r = cg_r.as<D>(), *z = cg_z.as<D>(), *p = cg_p.as<D>(), *q = cg_q.as<D>(), *pt = ir_part.as<D>();
+    StreamWait wait{stream};
+    const CgState<D> S = cg_make_state(rtol, maxit);
+    auto dot = [&](const D *a, const D *b) {
+      hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
+    };
+    auto finish = [&](int mode, int k) {
+      hipLaunchKernelGGL((k_cg_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, mode, k, S);
+    };
+    vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);  // r = b
+    dot(r, nullptr);
+    finish(0, 0);                                        // ||b||
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);   // x = 0
+    solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);  // z = M^{-1} r
+    dot(r, z);
+    finish(1, 0);                                        // rho = r^H z
+    vec_op(1, n, nc, p, nc, (const D *)z, nc, nullptr, 0);  // p = z
+    HIP_OK(hipGetLastError());
+    // (one read-back per step, after the convergence test; a column that breaks down in mode 4 costs one frozen step)
+    for (int k = 0, go = cg_active(S); k < maxit && go > 0; ++k) {
+      spmv_dev((const D *)p, nc, q, nc, nc, nullptr);    // q = A p
+      dot(p, q);
+      finish(2, k);                                      // alpha = rho / p^H q
+      hipLaunchKernelGGL((k_cg_xr<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, dX, ldx, r, (const D *)p, (const D *)q,
+                         S, pt);
+      finish(3, k);                                      // ||r|| / ||b||, maxit
+      if ((go = cg_active(S)) == 0) break;
+      solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);
+      dot(r, z);
+      finish(4, k);                                      // beta = rho' / rho
+      hipLaunchKernelGGL((k_cg_p<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, p, (const D *)z, S);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+    for (int c = 0; c < nc; ++c) {
+      if (iters) iters[c] = cg_pin[1 + c];
+      if (flags) flags[c] = cg_pin[65 + c];
+    }
+  }
+
+  void pcg_check(int maxit, double rtol) {
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "PCG needs the matrix (hifamd_set_matrix)");
+    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
+    const HermCheck &hc = hermitian();
+    if (!hc.ok)
+      throw Error(HIFAMD_BAD_PREC, "PCG needs a Hermitian preconditioner and this hierarchy is not one (level " +
+                                       std::to_string(hc.level) + ": " + hc.what +
+                                       "); factorize a Hermitian matrix with is_symm, or use GMRES");
+    if (nsp_on) throw Error(HIFAMD_BAD_PREC, "PCG does not support a null-space filter (hifamd_set_nsp_const)");
+  }
+
+  void pcg_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+               int *flags, int *iters) {
+    check_batch(dB, ldb, dX, ldx, nrhs);
+    pcg_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
+      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+      pcg_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr, iters ? iters + c0 : nullptr);
+    }
+  }
+
+  void pcg_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+                int *flags, int *iters) {
+    check_batch(B, ldb, X, ldx, nrhs);
+    pcg_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * nrhs * sizeof(T);
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
+    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyHostToDevice, stream));
+    pcg_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
   // ---- on-disk form of the imported hierarchy (import.hpp save_hierarchy / load_hierarchy) -----------------
   void save(std::FILE *f, int flags = 0) const {
     if (adjoint || is_twin) throw Error(HIFAMD_HIFIR_ERROR, "internal engines are not saved");
@@ -3489,6 +3631,35 @@ HifAmdStatus hifamd_fgmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *
   DISPATCH(ENG_D->gmres_host((const double *)B, ldb, (double *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps),
            ENG_Z->gmres_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps))
   API_END
+}
+
+HifAmdStatus hifamd_pcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, double rtol,
+                              int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->pcg_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->pcg_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                  double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->pcg_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->pcg_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+int hifamd_hermitian(HifAmdHdl h) {
+  if (!h || !h->eng) return -1;
+  try {
+    const HermCheck &hc = h->vt == HIFAMD_D ? ENG_D->hermitian() : ENG_Z->hermitian();
+    if (hc.ok) return 1;
+    set_err("level " + std::to_string(hc.level) + ": " + hc.what);
+    return 0;
+  } catch (const std::exception &e) {  // (allocation failure of the O(nnz) pass)
+    set_err(e.what());
+    return -1;
+  }
 }
 
 HifAmdStatus hifamd_time_apply(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,

@@ -1056,4 +1056,92 @@ bool adopt_analysis(HostLevel<T> &H, LevelAnalysis<T> &A, const BandOptions &opt
   return true;
 }
 
+// ---- is M^{-1} Hermitian? (hifamd_hermitian; the precondition of hifamd_pcg_batch) -------------------------------------
+// Per sparse level, exactly: U_B == L_B^H (same pattern, equal values), F == E^H (F absent only if E is empty), s == t,
+// p == q, Im d == 0; the last level absent or the SYEIG block of hifamd_set_dense_symm.  Then every factor of the
+// recursion M^{-1} = S_t P^T [...] P S_s (prec_solve.hpp:332-412) pairs with its adjoint and M^{-1} is Hermitian.
+// "Equal" is == per component, so a conjugated zero matches its unsigned twin; nothing is rounded or tolerated.
+struct HermCheck {
+  bool ok = false;
+  int64_t level = -1;  // first violation
+  std::string what;
+};
+
+// A^H in CCS form with ascending row indices inside every column (counting transpose)
+template <class T>
+Ccs<T> ccs_adjoint(const Ccs<T> &A) {
+  Ccs<T> B;
+  B.nrows = A.ncols;
+  B.ncols = A.nrows;
+  B.colptr.assign((size_t)A.nrows + 1, 0);
+  const int64_t nz = A.nnz();
+  for (int64_t k = 0; k < nz; ++k) ++B.colptr[(size_t)A.rowind[(size_t)k] + 1];
+  for (int64_t i = 0; i < A.nrows; ++i) B.colptr[(size_t)i + 1] += B.colptr[(size_t)i];
+  B.rowind.resize((size_t)nz);
+  B.vals.resize((size_t)nz);
+  std::vector<int64_t> fill(B.colptr.begin(), B.colptr.end() - 1);
+  for (int64_t j = 0; j < A.ncols; ++j)
+    for (int64_t k = A.colptr[(size_t)j]; k < A.colptr[(size_t)j + 1]; ++k) {
+      const int64_t o = fill[(size_t)A.rowind[(size_t)k]]++;
+      B.rowind[(size_t)o] = (int32_t)j;
+      B.vals[(size_t)o] = conj_(A.vals[(size_t)k]);
+    }
+  return B;
+}
+
+// X == Y^H, entry for entry (both compared with ascending row indices inside every column)
+template <class T>
+bool is_adjoint_of(const Ccs<T> &X, const Ccs<T> &Y) {
+  if (X.nrows != Y.ncols || X.ncols != Y.nrows || X.nnz() != Y.nnz()) return false;
+  const Ccs<T> a = ccs_adjoint(ccs_adjoint(X)), b = ccs_adjoint(Y);
+  return a.colptr == b.colptr && a.rowind == b.rowind && a.vals == b.vals;
+}
+
+inline bool imag_is_zero(double) { return true; }
+inline bool imag_is_zero(const zdouble &x) { return x.imag() == 0.0; }
+
+template <class T>
+HermCheck check_hermitian(const HostHierarchy<T> &host) {
+  HermCheck r;
+  if (host.levels.empty()) {
+    r.what = "no levels imported";
+    return r;
+  }
+  for (size_t l = 0; l < host.levels.size(); ++l) {
+    const HostLevel<T> &H = host.levels[l];
+    r.level = (int64_t)l;
+    if (!is_adjoint_of(H.U, H.L)) {
+      r.what = "U_B != L_B^H";
+      return r;
+    }
+    if (H.F_ncols == 0 ? H.E.nnz() != 0 : !is_adjoint_of(H.F, H.E)) {
+      r.what = "F != E^H";
+      return r;
+    }
+    if (H.s != H.t) {
+      r.what = "s != t";
+      return r;
+    }
+    for (int64_t i = 0; i < H.n; ++i)
+      if (H.q_inv[(size_t)H.p[(size_t)i]] != i) {
+        r.what = "p != q";
+        return r;
+      }
+    for (const T &v : H.d)
+      if (!imag_is_zero(v)) {
+        r.what = "Im d != 0";
+        return r;
+      }
+  }
+  if (host.has_dense && host.dense.kind != 1) {
+    r.level = (int64_t)host.levels.size();
+    r.what = host.dense.kind == 2 ? "the dense last level is LUP (hifamd_set_dense_lup), not SYEIG"
+                                  : "the dense last level is QRCP (hifamd_set_dense), not SYEIG (hifamd_set_dense_symm)";
+    return r;
+  }
+  r.ok = true;
+  r.level = -1;
+  return r;
+}
+
 }  // namespace hifamd

@@ -25,6 +25,7 @@
 //   k_gather_div / k_prod_rows / k_spmm_prod / k_scatter_div   prec_prod, alg/prec_prod.hpp:55-147
 //   k_zcombine       complex products as two real MFMA products
 //   k_gm_step / k_gm_finish / k_gm_backsolve / k_gm_combine / k_gm_colop   device-resident Arnoldi process of GMRES
+//   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1906,6 +1907,155 @@ __global__ void __launch_bounds__(256) k_gm_colop(int op, int64_t n, int nc, T *
     else
       y[i * ldy + c] = viszero(a) ? vzero(T()) : vdivr(x[i * ldx + c], vreal(a));
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident preconditioned CG for a Hermitian positive-definite pair (A, M), up to 64 columns in lock step
+// (Engine::pcg_tile).  Vectors are [n][nc] contiguous.  Lane = column: wave w of block b owns the rows
+// i = 4 b + w + k * 4 kCgBlocks, every lane walks them in that order, the four waves of a block are added in wave
+// order and the kCgBlocks partials of a column in a fixed order by k_cg_finish.  Nothing of that depends on nc or
+// on the other columns, so a column's bits do not depend on the batch it travels in (unlike k_gm_step, whose
+// rows per pass are 256 / nc).  Inner products are Hermitian, sum conj(a_i) b_i.
+// ---------------------------------------------------------------------------------------------
+constexpr int kCgBlocks = 1024;  // blocks of 4 waves of every fused pass (and partials per column)
+
+template <class T>
+struct CgState {
+  T *rho, *alpha, *beta;  // [64]  r^H z of the last step, rho / sigma, rho' / rho (0 for a frozen column)
+  double *bnorm;          // [64]  ||b||
+  int *iter, *flag, *active;  // [64]
+  int *ctl;               // [0] columns still active
+  int maxit;
+  double rtol;
+};
+
+// adds the four wave partials of a block in wave order: partial[blockIdx.x][c], stride 64
+template <class T>
+__device__ __forceinline__ void cg_block_partial(T acc, T *sm /* [4][64] */, T *__restrict__ partial) {
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  sm[w * 64 + c] = acc;
+  __syncthreads();
+  if (threadIdx.x < 64)
+    partial[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[c], sm[64 + c]), sm[128 + c]), sm[192 + c]);
+}
+
+// the block's share of sum conj(a_i) b_i per column (b == nullptr: sum |a_i|^2)
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_dot(int64_t n, int nc, const T *__restrict__ a, const T *__restrict__ b,
+                                                T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc)
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      const T x = a[i * nc + c];
+      acc = vadd(acc, b ? vmul(vconj(x), b[i * nc + c]) : vfromreal(vabs2(x), T()));
+    }
+  cg_block_partial(acc, sm, partial);
+}
+
+// x += alpha p, r -= alpha q on the active columns, fused with the block's share of |r|^2 (x: row stride ldx)
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_xr(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
+                                               const T *__restrict__ p, const T *__restrict__ q, CgState<T> S,
+                                               T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc) {
+    const bool act = S.active[c] != 0;
+    const T al = S.alpha[c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      T ri = r[i * nc + c];
+      if (act) {
+        x[i * ldx + c] = vadd(x[i * ldx + c], vmul(al, p[i * nc + c]));
+        ri = vsub(ri, vmul(al, q[i * nc + c]));
+        r[i * nc + c] = ri;
+      }
+      acc = vadd(acc, vfromreal(vabs2(ri), T()));
+    }
+  }
+  cg_block_partial(acc, sm, partial);
+}
+
+// p = z + beta p on the active columns
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_p(int64_t n, int nc, T *__restrict__ p, const T *__restrict__ z, CgState<T> S) {
+  const int c = threadIdx.x & 63;
+  if (c >= nc || !S.active[c]) return;
+  const T be = S.beta[c];
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
+    p[i * nc + c] = vadd(z[i * nc + c], vmul(be, p[i * nc + c]));
+}
+
+// not a usable curvature / preconditioned residual norm: not finite, or real part <= 0
+__device__ __forceinline__ bool cg_bad(double v) { return !(v > 0.0) || !isfinite(v); }
+__device__ __forceinline__ bool cg_bad(cplx v) { return !(v.x > 0.0) || !isfinite(v.x) || !isfinite(v.y); }
+
+// Sums the kCgBlocks partials of every column in a fixed order (wave w takes blocks w, w + 16, ..., then the 16 wave
+// sums in wave order) and does the per-column scalar work of step k:
+//   mode 0: ||b||: the state; a zero column is done (x = 0, flag 0, 0 iterations)
+//   mode 1: rho = r^H z of the start                                   (not positive: flag 1, 0 iterations)
+//   mode 2: sigma = p^H A p: alpha = rho / sigma                       (not positive: flag 1, k iterations)
+//   mode 3: |r|^2 after the update: ||r|| / ||b|| <= rtol -> flag 0, k + 1 iterations; k + 1 == maxit -> flag 2
+//   mode 4: rho' = r^H z: beta = rho' / rho, rho = rho'                (not positive: flag 1, k + 1 iterations)
+// A column that stops gets alpha = beta = 0 and active = 0; ctl[0] = columns still active.
+template <class T>
+__global__ void __launch_bounds__(1024) k_cg_finish(const T *__restrict__ partial, int nc, int mode, int k, CgState<T> S) {
+  __shared__ T sm[16 * 64];
+  __shared__ int cnt;
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  T acc = vzero(T());
+  if (c < nc)
+    for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, partial[(int64_t)b * 64 + c]);
+  sm[threadIdx.x] = acc;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  if (threadIdx.x < nc) {
+    T tot = vzero(T());
+    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
+    int act = S.active[c];
+    int stop = -1, it = 0;  // flag and iterations of a column that stops here
+    if (mode == 0) {
+      const double bn = sqrt(vreal(tot));
+      S.bnorm[c] = bn;
+      S.iter[c] = 0;
+      S.flag[c] = 0;
+      S.alpha[c] = vzero(T());
+      S.beta[c] = vzero(T());
+      act = !(bn == 0.0);
+    } else if (act && mode == 1) {
+      if (cg_bad(tot)) stop = 1, it = 0;
+      else S.rho[c] = tot;
+    } else if (act && mode == 2) {
+      if (cg_bad(tot)) stop = 1, it = k;
+      else S.alpha[c] = vdiv(S.rho[c], tot);
+    } else if (act && mode == 3) {
+      if (sqrt(vreal(tot)) / S.bnorm[c] <= S.rtol) stop = 0, it = k + 1;
+      else if (k + 1 >= S.maxit) stop = 2, it = S.maxit;
+    } else if (act && mode == 4) {
+      if (cg_bad(tot)) {
+        stop = 1, it = k + 1;
+      } else {
+        S.beta[c] = vdiv(tot, S.rho[c]);
+        S.rho[c] = tot;
+      }
+    }
+    if (stop >= 0) {
+      S.flag[c] = stop;
+      S.iter[c] = it;
+      S.alpha[c] = vzero(T());
+      S.beta[c] = vzero(T());
+      act = 0;
+    }
+    S.active[c] = act;
+    if (act) atomicAdd(&cnt, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) S.ctl[0] = cnt;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -249,6 +249,31 @@ HifAmdStatus hifamd_fgmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *
                                  int restart, double rtol, int maxit, int64_t rank, int *flags, int *iters,
                                  int *sweeps);
 
+/* ---- preconditioned CG for a Hermitian positive-definite pair (A, M), batched --------------- */
+/* 1 when M^{-1} of the imported hierarchy is Hermitian, 0 when not, -1 for a NULL handle.  Exact test on the host
+ * copy, every sparse level: U_B == L_B^H (same pattern, equal values), F == E^H (F absent only if E is empty),
+ * s == t, p == q, Im d == 0; the last level absent or imported with hifamd_set_dense_symm (a QRCP or LUP block fails).
+ * This is what a hierarchy factorized with is_symm satisfies; a nonsymmetric factorization of a symmetric matrix does
+ * not.  Computed once per imported hierarchy; works before hifamd_finalize and without a GPU.  On 0, hifamd_last_error()
+ * names the first violation ("level <l>: <what>"). */
+int hifamd_hermitian(HifAmdHdl h);
+/* Standard preconditioned CG with x0 = 0 for nrhs columns in lock step: q = A p, alpha = rho / p^H q, x += alpha p,
+ * r -= alpha q, stop on ||r|| / ||b|| <= rtol, z = M^{-1} r, rho' = r^H z, p = z + (rho' / rho) p.  All vectors and the
+ * per-column scalars stay in HBM (four work vectors r, z, p, q per 64-column tile, no restarts); one batched apply, one
+ * SpMM and four fused vector passes serve every column per step, and the host reads back one integer per step.
+ * Inner products are Hermitian (sum conj(a_i) b_i) and their summation order depends on n only, so a column's result
+ * does not depend on the batch it is solved in.  Needs hifamd_set_matrix and a Hermitian M^{-1} (hifamd_hermitian; the
+ * HIFAMD_BAD_PREC message names the level and the array of the first violation); a null-space filter on HIFAMD_S
+ * (hifamd_set_nsp_const) is not supported and refused with HIFAMD_BAD_PREC.  maxit < 1 or rtol <= 0:
+ * HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  Per column: flags[c] = 0 converged / 1 breakdown (p^H A p
+ * or r^H M^{-1} r not positive or not finite: A or M is not positive definite on that column) / 2 reached maxit,
+ * iters[c] = iterations (a zero column: x = 0, flag 0, 0 iterations); either may be NULL.  Host pointers; the _dev
+ * variant takes device pointers for B, X (flags, iters stay host arrays) and returns when the solve is done. */
+HifAmdStatus hifamd_pcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
+                              double rtol, int maxit, int64_t rank, int *flags, int *iters);
+HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                  double rtol, int maxit, int64_t rank, int *flags, int *iters);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Average device time (ms) of the last `hifamd_solve_batch_dev`-shaped graph over `reps` replays,
  * measured with HIP events on the handle's stream (the stream the kernels run on). */

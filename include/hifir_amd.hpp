@@ -204,6 +204,19 @@ class HIF {
     return std::make_tuple(std::move(x), flag, iters);
   }
 
+  // ---- preconditioned CG for a Hermitian positive-definite pair (A, M) on the device (hifamd_pcg_batch) ----
+  // Needs an is_symm hierarchy: is_hermitian(); flag 0 converged, 1 breakdown, 2 reached maxit.
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, int, int> pcg(const Matrix &A, const ArrayType &b, const double rtol, const int maxit,
+                                      const bool full_rank = false) {
+    ensure_matrix(A);
+    ArrayType x(b.size());
+    int flag = 0, iters = 0;
+    detail::check(hifamd_pcg_batch(_h, b.data(), 1, x.data(), 1, 1, rtol, maxit, full_rank ? -1 : 0, &flag, &iters));
+    return std::make_tuple(std::move(x), flag, iters);
+  }
+  bool is_hermitian() const { return _h && hifamd_hermitian(_h) == 1; }
+
  private:
   void require() const {
     if (!_h) throw std::runtime_error("hifir_amd: MILU-Prec is empty!");  // builder.hpp:412
