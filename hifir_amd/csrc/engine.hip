@@ -2834,6 +2834,131 @@ class Engine : public EngineBase {
     HIP_OK(hipStreamSynchronize(stream));
   }
 
+  // ---- right-preconditioned BiCGSTAB, batched over columns ----------------------------------------
+  // x0 = 0, r^ = b, r = b, rho = (r^, r), p = r; per iteration y = M^{-1} p, v = A y, alpha = rho / (r^, v),
+  // x += alpha y, r -= alpha v, test; y = M^{-1} r, t = A y, omega = (t, r) / (t, t), x += omega y, r -= omega t, test;
+  // rho' = (r^, r), beta = (rho' / rho)(alpha / omega), p = r + beta (p - omega v).  A step is one apply plus one SpMM
+  // (two per iteration, maxit and iters count steps); the tests are ||r|| / ||b|| <= rtol and steps == maxit.  Up to 64
+  // columns in lock step, per-column scalars in HBM (BsState), the fused k_bs_* passes each closed by k_bs_finish; the
+  // host reads the active count after each of the two tests.  r^ is b itself, read in place, so the work vectors are
+  // r, p, v, y, t.  Every apply goes through solve_dev, so a null-space filter on HIFAMD_S filters it.
+  // Flags 0 converged / 1 breakdown / 2 reached maxit.
+  DevBuf bs_r, bs_p, bs_v, bs_y, bs_t, bs_part2, bs_state;
+
+  BsState<D> bs_make_state(double rtol, int maxit) {
+    const size_t o_sc = 0, o_bn = o_sc + 4 * 64 * sizeof(D), o_int = o_bn + 64 * sizeof(double),
+                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
+    if (bs_state.bytes < bytes) bs_state.alloc(bytes);
+    HIP_OK(hipMemsetAsync(bs_state.p, 0, bytes, stream));
+    char *b = bs_state.as<char>();
+    BsState<D> S;
+    S.rho = (D *)(b + o_sc);
+    S.alpha = S.rho + 64;
+    S.omega = S.rho + 128;
+    S.beta = S.rho + 192;
+    S.bnorm = (double *)(b + o_bn);
+    int *ib = (int *)(b + o_int);
+    S.iter = ib;
+    S.flag = ib + 64;
+    S.active = ib + 128;
+    S.ctl = ib + 192;
+    S.maxit = maxit;
+    S.rtol = rtol;
+    return S;
+  }
+  int bs_active(const BsState<D> &S) {
+    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return cg_pin[0];
+  }
+
+  void bicgstab_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank,
+                     int *flags, int *iters) {
+    const int64_t n = lv[0]->n;
+    const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
+    for (DevBuf *b : {&bs_r, &bs_p, &bs_v, &bs_y, &bs_t})
+      if (b->bytes < vec) b->alloc(vec);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    if (bs_part2.bytes < part) bs_part2.alloc(part);
+    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
+    D *r = bs_r.as<D>(), *p = bs_p.as<D>(), *v = bs_v.as<D>(), *y = bs_y.as<D>(), *t = bs_t.as<D>();
+    D *pt = ir_part.as<D>(), *pt2 = bs_part2.as<D>();
+    const D *rh = dB;  // r^ = b
+    StreamWait wait{stream};
+    const BsState<D> S = bs_make_state(rtol, maxit);
+    const dim3 grid(kCgBlocks), blk(256);
+    auto finish = [&](int mode, int k, const D *p1) {
+      hipLaunchKernelGGL((k_bs_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, p1, nc, mode, k, S);
+    };
+    vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);            // r = b
+    hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, (const D *)r, (const D *)nullptr, pt);
+    finish(0, 0, nullptr);                                    // ||b||, rho = ||b||^2
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);        // x = 0
+    vec_op(1, n, nc, p, nc, (const D *)r, nc, nullptr, 0);    // p = r
+    HIP_OK(hipGetLastError());
+    for (int k = 0, go = bs_active(S); go > 0 && 2 * k < maxit; ++k) {
+      solve_dev((const D *)p, nc, y, nc, nc, rank, nullptr);  // y = M^{-1} p           step 2k + 1
+      spmv_dev((const D *)y, nc, v, nc, nc, nullptr);         // v = A y
+      hipLaunchKernelGGL((k_bs_hdot<D>), grid, blk, 0, stream, n, nc, rh, ldb, (const D *)v, pt);
+      finish(1, k, nullptr);                                  // alpha = rho / (r^, v)
+      hipLaunchKernelGGL((k_bs_xr_half<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)y, (const D *)v, S, pt);
+      finish(2, k, nullptr);                                  // ||s|| / ||b||, maxit
+      if ((go = bs_active(S)) == 0) break;
+      solve_dev((const D *)r, nc, y, nc, nc, rank, nullptr);  // y = M^{-1} s           step 2k + 2
+      spmv_dev((const D *)y, nc, t, nc, nc, nullptr);         // t = A y
+      hipLaunchKernelGGL((k_bs_tr<D>), grid, blk, 0, stream, n, nc, (const D *)t, (const D *)r, pt, pt2);
+      finish(3, k, pt2);                                      // omega = (t, r) / (t, t)
+      hipLaunchKernelGGL((k_bs_xr_full<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)y, (const D *)t, rh, ldb,
+                         S, pt, pt2);
+      finish(4, k, pt2);                                      // ||r|| / ||b||, maxit, beta
+      if ((go = bs_active(S)) == 0) break;
+      hipLaunchKernelGGL((k_bs_p<D>), grid, blk, 0, stream, n, nc, p, (const D *)r, (const D *)v, S);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+    for (int c = 0; c < nc; ++c) {
+      if (iters) iters[c] = cg_pin[1 + c];
+      if (flags) flags[c] = cg_pin[65 + c];
+    }
+  }
+
+  void bicgstab_check(int maxit, double rtol) {
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "BiCGSTAB needs the matrix (hifamd_set_matrix)");
+    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
+  }
+
+  void bicgstab_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+                    int *flags, int *iters) {
+    check_batch(dB, ldb, dX, ldx, nrhs);
+    bicgstab_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
+      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+      bicgstab_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr,
+                    iters ? iters + c0 : nullptr);
+    }
+  }
+
+  void bicgstab_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+                     int *flags, int *iters) {
+    check_batch(B, ldb, X, ldx, nrhs);
+    bicgstab_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * nrhs * sizeof(T);
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
+    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyHostToDevice, stream));
+    bicgstab_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
   // ---- on-disk form of the imported hierarchy (import.hpp save_hierarchy / load_hierarchy) -----------------
   void save(std::FILE *f, int flags = 0) const {
     if (adjoint || is_twin) throw Error(HIFAMD_HIFIR_ERROR, "internal engines are not saved");
@@ -3646,6 +3771,22 @@ HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void
   API_BEGIN
   DISPATCH(ENG_D->pcg_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
            ENG_Z->pcg_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_bicgstab_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
+                                   double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->bicgstab_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->bicgstab_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                       double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->bicgstab_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->bicgstab_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
   API_END
 }
 

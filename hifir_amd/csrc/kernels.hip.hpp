@@ -26,6 +26,7 @@
 //   k_zcombine       complex products as two real MFMA products
 //   k_gm_step / k_gm_finish / k_gm_backsolve / k_gm_combine / k_gm_colop   device-resident Arnoldi process of GMRES
 //   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
+//   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 #pragma once
 #include <hip/hip_runtime.h>
@@ -2048,6 +2049,212 @@ __global__ void __launch_bounds__(1024) k_cg_finish(const T *__restrict__ partia
       S.flag[c] = stop;
       S.iter[c] = it;
       S.alpha[c] = vzero(T());
+      S.beta[c] = vzero(T());
+      act = 0;
+    }
+    S.active[c] = act;
+    if (act) atomicAdd(&cnt, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) S.ctl[0] = cnt;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident right-preconditioned BiCGSTAB with x0 = 0 and r^ = b, up to 64 columns in lock step
+// (Engine::bicgstab_tile).  Same layout and row walk as k_cg_*: vectors [n][nc] (r^ is b itself, row stride ldh),
+// lane = column, wave w of block b owns the rows i = 4 b + w + k * 4 kCgBlocks, wave partials added in wave order and
+// the kCgBlocks block partials of a column in k_cg_finish's order by k_bs_finish; a column's bits do not depend on
+// the batch it travels in.  A step is one M^{-1} apply plus one SpMM; one iteration is two steps.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+struct BsState {
+  T *rho, *alpha, *omega, *beta;  // [64]  (r^, r), rho / (r^, v), (t, r) / (t, t), (rho' / rho)(alpha / omega); 0 when frozen
+  double *bnorm;                  // [64]  ||b||
+  int *iter, *flag, *active;      // [64]  iter counts steps
+  int *ctl;                       // [0] columns still active
+  int maxit;
+  double rtol;
+};
+
+// the four wave partials of two sums, each added in wave order: p0 / p1[blockIdx.x][c], stride 64
+template <class T>
+__device__ __forceinline__ void bs_block_partial2(T a0, T a1, T *sm /* [2][4][64] */, T *__restrict__ p0,
+                                                  T *__restrict__ p1) {
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  sm[w * 64 + c] = a0;
+  sm[256 + w * 64 + c] = a1;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    p0[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[c], sm[64 + c]), sm[128 + c]), sm[192 + c]);
+    p1[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[256 + c], sm[320 + c]), sm[384 + c]), sm[448 + c]);
+  }
+}
+
+// the block's share of (r^, v) = sum conj(r^_i) v_i per column (r^: row stride ldh)
+template <class T>
+__global__ void __launch_bounds__(256) k_bs_hdot(int64_t n, int nc, const T *__restrict__ rh, int64_t ldh,
+                                                 const T *__restrict__ v, T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc)
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
+      acc = vadd(acc, vmul(vconj(rh[i * ldh + c]), v[i * nc + c]));
+  cg_block_partial(acc, sm, partial);
+}
+
+// half step on the active columns: x += alpha y, r -= alpha v (r then holds s), fused with the block's share of |r|^2
+template <class T>
+__global__ void __launch_bounds__(256) k_bs_xr_half(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
+                                                    const T *__restrict__ y, const T *__restrict__ v, BsState<T> S,
+                                                    T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc) {
+    const bool act = S.active[c] != 0;
+    const T al = S.alpha[c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      T ri = r[i * nc + c];
+      if (act) {
+        x[i * ldx + c] = vadd(x[i * ldx + c], vmul(al, y[i * nc + c]));
+        ri = vsub(ri, vmul(al, v[i * nc + c]));
+        r[i * nc + c] = ri;
+      }
+      acc = vadd(acc, vfromreal(vabs2(ri), T()));
+    }
+  }
+  cg_block_partial(acc, sm, partial);
+}
+
+// the block's shares of (t, r) = sum conj(t_i) r_i and (t, t) = sum |t_i|^2, one read of t and r
+template <class T>
+__global__ void __launch_bounds__(256) k_bs_tr(int64_t n, int nc, const T *__restrict__ t, const T *__restrict__ r,
+                                               T *__restrict__ part_tr, T *__restrict__ part_tt) {
+  __shared__ T sm[512];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T tr = vzero(T()), tt = vzero(T());
+  if (c < nc)
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      const T ti = t[i * nc + c];
+      tr = vadd(tr, vmul(vconj(ti), r[i * nc + c]));
+      tt = vadd(tt, vfromreal(vabs2(ti), T()));
+    }
+  bs_block_partial2(tr, tt, sm, part_tr, part_tt);
+}
+
+// full step on the active columns: x += omega y, r -= omega t, fused with the block's shares of |r|^2 and (r^, r)
+template <class T>
+__global__ void __launch_bounds__(256) k_bs_xr_full(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
+                                                    const T *__restrict__ y, const T *__restrict__ t,
+                                                    const T *__restrict__ rh, int64_t ldh, BsState<T> S,
+                                                    T *__restrict__ part_rr, T *__restrict__ part_hr) {
+  __shared__ T sm[512];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T rr = vzero(T()), hr = vzero(T());
+  if (c < nc) {
+    const bool act = S.active[c] != 0;
+    const T om = S.omega[c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      T ri = r[i * nc + c];
+      if (act) {
+        x[i * ldx + c] = vadd(x[i * ldx + c], vmul(om, y[i * nc + c]));
+        ri = vsub(ri, vmul(om, t[i * nc + c]));
+        r[i * nc + c] = ri;
+      }
+      rr = vadd(rr, vfromreal(vabs2(ri), T()));
+      hr = vadd(hr, vmul(vconj(rh[i * ldh + c]), ri));
+    }
+  }
+  bs_block_partial2(rr, hr, sm, part_rr, part_hr);
+}
+
+// p = r + beta (p - omega v) on the active columns
+template <class T>
+__global__ void __launch_bounds__(256) k_bs_p(int64_t n, int nc, T *__restrict__ p, const T *__restrict__ r,
+                                              const T *__restrict__ v, BsState<T> S) {
+  const int c = threadIdx.x & 63;
+  if (c >= nc || !S.active[c]) return;
+  const T be = S.beta[c], om = S.omega[c];
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
+    p[i * nc + c] = vadd(r[i * nc + c], vmul(be, vsub(p[i * nc + c], vmul(om, v[i * nc + c]))));
+}
+
+// a BiCGSTAB breakdown value: exactly zero or not finite
+__device__ __forceinline__ bool bs_bad(double v) { return v == 0.0 || !isfinite(v); }
+__device__ __forceinline__ bool bs_bad(cplx v) { return (v.x == 0.0 && v.y == 0.0) || !isfinite(v.x) || !isfinite(v.y); }
+
+// Sums the kCgBlocks partials of every column of p0 (and of p1 when given) in k_cg_finish's order and does the
+// per-column scalar work of iteration k (steps 2k + 1 and 2k + 2):
+//   mode 0: p0 = ||b||^2: ||b||, rho = ||b||^2; b = 0 is done (x = 0, flag 0, 0 steps); rho bad: flag 1, 0 steps
+//   mode 1: p0 = (r^, v): alpha = rho / (r^, v)                                   (bad: flag 1, 2k + 1 steps)
+//   mode 2: p0 = |s|^2: ||s|| / ||b|| <= rtol -> flag 0, 2k + 1 steps; 2k + 1 >= maxit -> flag 2
+//   mode 3: p0 = (t, r), p1 = (t, t): omega = (t, r) / (t, t)          ((t, t) or omega bad: flag 1, 2k + 2 steps)
+//   mode 4: p0 = |r|^2, p1 = rho' = (r^, r): ||r|| / ||b|| <= rtol -> flag 0, 2k + 2 steps; 2k + 2 >= maxit -> flag 2;
+//           rho' bad -> flag 1, 2k + 2 steps; else beta = (rho' / rho)(alpha / omega), rho = rho'
+// A column that stops gets rho = alpha = omega = beta = 0 and active = 0; ctl[0] = columns still active.
+template <class T>
+__global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, const T *__restrict__ p1, int nc, int mode,
+                                                    int k, BsState<T> S) {
+  __shared__ T sm0[16 * 64], sm1[16 * 64];
+  __shared__ int cnt;
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  T a0 = vzero(T()), a1 = vzero(T());
+  if (c < nc) {
+    for (int b = w; b < kCgBlocks; b += 16) a0 = vadd(a0, p0[(int64_t)b * 64 + c]);
+    if (p1)
+      for (int b = w; b < kCgBlocks; b += 16) a1 = vadd(a1, p1[(int64_t)b * 64 + c]);
+  }
+  sm0[threadIdx.x] = a0;
+  sm1[threadIdx.x] = a1;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  if (threadIdx.x < nc) {
+    T t0 = vzero(T()), t1 = vzero(T());
+    for (int v = 0; v < 16; ++v) t0 = vadd(t0, sm0[v * 64 + c]);
+    for (int v = 0; v < 16; ++v) t1 = vadd(t1, sm1[v * 64 + c]);
+    int act = S.active[c];
+    int stop = -1, it = 0;  // flag and steps of a column that stops here
+    if (mode == 0) {
+      const double bn = sqrt(vreal(t0));
+      S.bnorm[c] = bn;
+      S.iter[c] = 0;
+      S.flag[c] = 0;
+      act = !(bn == 0.0);
+      if (act && bs_bad(t0)) stop = 1, it = 0;
+      else S.rho[c] = t0;
+    } else if (act && mode == 1) {
+      if (bs_bad(t0)) stop = 1, it = 2 * k + 1;
+      else S.alpha[c] = vdiv(S.rho[c], t0);
+    } else if (act && mode == 2) {
+      if (sqrt(vreal(t0)) / S.bnorm[c] <= S.rtol) stop = 0, it = 2 * k + 1;
+      else if (2 * k + 1 >= S.maxit) stop = 2, it = S.maxit;
+    } else if (act && mode == 3) {
+      const T om = vdiv(t0, t1);
+      if (bs_bad(t1) || bs_bad(om)) stop = 1, it = 2 * k + 2;
+      else S.omega[c] = om;
+    } else if (act && mode == 4) {
+      if (sqrt(vreal(t0)) / S.bnorm[c] <= S.rtol) {
+        stop = 0, it = 2 * k + 2;
+      } else if (2 * k + 2 >= S.maxit) {
+        stop = 2, it = S.maxit;
+      } else if (bs_bad(t1)) {
+        stop = 1, it = 2 * k + 2;
+      } else {
+        S.beta[c] = vmul(vdiv(t1, S.rho[c]), vdiv(S.alpha[c], S.omega[c]));
+        S.rho[c] = t1;
+      }
+    }
+    if (stop >= 0 || !act) {
+      if (stop >= 0) S.flag[c] = stop, S.iter[c] = it;
+      S.rho[c] = vzero(T());
+      S.alpha[c] = vzero(T());
+      S.omega[c] = vzero(T());
       S.beta[c] = vzero(T());
       act = 0;
     }

@@ -497,6 +497,33 @@ class HIF:
             return X.reshape(-1), int(fl[0]), int(it[0])
         return X, fl, it
 
+    def bicgstab(self, b, rtol=1e-6, maxit=500, full_rank=False):
+        """Right-preconditioned BiCGSTAB (x0 = 0, shadow residual b) for a general pair (A, M), all columns of b ([n] or
+        [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix.  maxit and iters count
+        steps (one apply plus one SpMM each; two per iteration).  Returns (x, flags, iters); ints for a vector.
+        flags: 0 converged, 1 breakdown, 2 reached maxit."""
+        vec = (b.ndim == 1)
+        rank = -1 if full_rank else 0
+        if _is_torch(b):
+            import torch
+
+            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
+            X = torch.empty_like(B)
+            fl = np.zeros(B.shape[1], dtype=np.int32)
+            it = np.zeros(B.shape[1], dtype=np.int32)
+            _check(lib().hifamd_bicgstab_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0),
+                                                  B.shape[1], float(rtol), int(maxit), rank, _p(fl), _p(it)))
+        else:
+            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
+            X = np.empty_like(B)
+            fl = np.zeros(B.shape[1], dtype=np.int32)
+            it = np.zeros(B.shape[1], dtype=np.int32)
+            _check(lib().hifamd_bicgstab_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
+                                              int(maxit), rank, _p(fl), _p(it)))
+        if vec:
+            return X.reshape(-1), int(fl[0]), int(it[0])
+        return X, fl, it
+
     def fgmres(self, b, restart=30, rtol=1e-6, maxit=500, full_rank=False):
         """Flexible GMRES with 2^k refinement sweeps as the preconditioner of outer cycle k (the reference's
         fgmres_hifir, examples/advanced/gmres.hpp:127-231); host arrays.  Returns (x, flags, iters, sweeps)."""

@@ -274,6 +274,28 @@ HifAmdStatus hifamd_pcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, 
 HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                   double rtol, int maxit, int64_t rank, int *flags, int *iters);
 
+/* ---- right-preconditioned BiCGSTAB for a general (non-Hermitian) pair (A, M), batched --------- */
+/* BiCGSTAB with x0 = 0 and shadow residual r^ = b for nrhs columns in lock step: r = b, rho = (r^, r), p = r; per
+ * iteration y = M^{-1} p, v = A y, alpha = rho / (r^, v), x += alpha y, r -= alpha v, test; y = M^{-1} r, t = A y,
+ * omega = (t, r) / (t, t), x += omega y, r -= omega t, test; rho' = (r^, r), beta = (rho' / rho)(alpha / omega),
+ * p = r + beta (p - omega v).  The test is ||r|| / ||b|| <= rtol.  A STEP is one M^{-1} apply plus one SpMM (the unit
+ * of the GMRES and PCG iteration counts): maxit caps steps, and iters[c] reports steps, so a column may stop on an odd
+ * count (converged, or maxit reached, after the first half of an iteration).  All vectors and the per-column scalars
+ * stay in HBM (five work vectors r, p, v, y, t per 64-column tile; r^ is B itself, read in place; no restarts); the
+ * host reads back one integer after each of the two tests of an iteration.  Inner products are Hermitian
+ * (sum conj(a_i) b_i) and their summation order depends on n only, so a column's result does not depend on the batch
+ * it is solved in.  A null-space filter on HIFAMD_S (hifamd_set_nsp_const) filters every M^{-1} apply, as in GMRES;
+ * M^{-1} need not be Hermitian.  Needs hifamd_set_matrix (else HIFAMD_BAD_PREC, as for a handle not finalized);
+ * maxit < 1 or rtol <= 0: HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  Per column: flags[c] = 0
+ * converged / 1 breakdown ((r^, v), (t, t), omega, rho' or the initial rho exactly zero or not finite; x keeps its last
+ * completed update) / 2 reached maxit, iters[c] = steps taken (a zero column: x = 0, flag 0, 0 steps; a non-finite
+ * column: flag 1, 0 steps); either may be NULL.  Host pointers; the _dev variant takes device pointers for B, X
+ * (flags, iters stay host arrays), writes X in place and returns when the solve is done. */
+HifAmdStatus hifamd_bicgstab_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
+                                   double rtol, int maxit, int64_t rank, int *flags, int *iters);
+HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                       double rtol, int maxit, int64_t rank, int *flags, int *iters);
+
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Average device time (ms) of the last `hifamd_solve_batch_dev`-shaped graph over `reps` replays,
  * measured with HIP events on the handle's stream (the stream the kernels run on). */

@@ -217,6 +217,19 @@ class HIF {
   }
   bool is_hermitian() const { return _h && hifamd_hermitian(_h) == 1; }
 
+  // ---- right-preconditioned BiCGSTAB for a general pair (A, M) on the device (hifamd_bicgstab_batch) ----
+  // iters counts steps (one apply plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, int, int> bicgstab(const Matrix &A, const ArrayType &b, const double rtol, const int maxit,
+                                           const bool full_rank = false) {
+    ensure_matrix(A);
+    ArrayType x(b.size());
+    int flag = 0, iters = 0;
+    detail::check(
+        hifamd_bicgstab_batch(_h, b.data(), 1, x.data(), 1, 1, rtol, maxit, full_rank ? -1 : 0, &flag, &iters));
+    return std::make_tuple(std::move(x), flag, iters);
+  }
+
  private:
   void require() const {
     if (!_h) throw std::runtime_error("hifir_amd: MILU-Prec is empty!");  // builder.hpp:412
