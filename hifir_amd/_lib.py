@@ -20,6 +20,10 @@ SIGNATURES = {
     "hifamd_destroy": (_int, [_vp]),
     "hifamd_add_level": (_int, [_vp, _i64, _i64] + [_vp] * 9 + [_i64] + [_vp] * 10),
     "hifamd_set_nsp_const": (_int, [_vp, _int, _i64, _i64]),
+    "hifamd_set_nsp_basis": (_int, [_vp, _int, _i64, _vp, _i64]),
+    "hifamd_nsp_dim": (_i64, [_vp, _int]),
+    "hifamd_nsp_filter_batch": (_int, [_vp, _int, _vp, _i64, _i64]),
+    "hifamd_nsp_filter_batch_dev": (_int, [_vp, _int, _vp, _i64, _i64, _vp]),
     "hifamd_save": (_int, [_vp, C.c_char_p]),
     "hifamd_save_ex": (_int, [_vp, C.c_char_p, _int]),
     "hifamd_load": (_int, [C.c_char_p, _int, C.POINTER(_vp)]),

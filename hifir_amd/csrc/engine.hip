@@ -511,6 +511,11 @@ class Engine : public EngineBase {
   bool nsp_on = false;
   int64_t nsp_r0 = 0, nsp_r1 = -1;
   DevBuf nsp_part;
+  // basis mode (hifamd_set_nsp_basis): Q [n][nsp_kp] orthonormal, nsp_k vectors padded with zero vectors to nsp_kp; the
+  // block partials [nsp_kp][kCgBlocks][64] and the coefficients [nsp_kp][64] of one tile.  One filter per engine:
+  // nsp_on and nsp_k > 0 exclude each other.  (Twin engines never filter: solve_dev filters after their join.)
+  int nsp_k = 0, nsp_kp = 0;
+  DevBuf nsp_Q, nsp_cpart, nsp_C;
   DevBuf gm_v, gm_w, gm_Q, gm_Z, gm_alpha;  // GMRES: work vectors, Krylov basis, per-column coefficients
   int64_t ir_cols = 0;
 
@@ -2272,6 +2277,7 @@ class Engine : public EngineBase {
 
   // builder.hpp:419-422: after the solve, x loses its component along the (constant) null space
   void apply_nsp(D *dX, int64_t ldx, int64_t nrhs, hipStream_t st) {
+    if (nsp_k > 0) return apply_nsp_basis(dX, ldx, nrhs, st);
     if (!nsp_on) return;
     const int64_t n = lv[0]->n;
     const int64_t r0 = nsp_r0, r1 = (nsp_r1 < 0 || nsp_r1 < nsp_r0) ? n : nsp_r1;  // NspFilter.hpp:163-167
@@ -2286,6 +2292,77 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_sub_colmean<D>), dim3(vec_grid((r1 - r0) * nc)), dim3(256), 0, st, r0, r1, nc, dX + c0, ldx,
                          (const D *)nsp_part.as<D>(), nblk);
     }
+  }
+
+  // basis mode: x -= Q (Q^H x) per 64-column tile -- block partials of Q^H X, one workgroup per basis vector adds them,
+  // then the update (kernels.hip.hpp k_nsp_*; reduction order fixed by n alone)
+  template <int K>
+  void launch_nsp_basis(D *x, int64_t ldx, int nc, hipStream_t st) {
+    const int64_t n = lv[0]->n;
+    const D *Q = nsp_Q.as<D>();
+    D *part = nsp_cpart.as<D>(), *C = nsp_C.as<D>();
+    hipLaunchKernelGGL((k_nsp_coef<D, K>), dim3(kCgBlocks), dim3(256), 0, st, n, nc, (const D *)x, ldx, Q, part);
+    hipLaunchKernelGGL((k_nsp_finish<D>), dim3(K), dim3(1024), 0, st, (const D *)part, C);
+    hipLaunchKernelGGL((k_nsp_sub<D, K>), dim3(kCgBlocks), dim3(256), 0, st, n, nc, x, ldx, Q, (const D *)C);
+  }
+  void apply_nsp_basis(D *dX, int64_t ldx, int64_t nrhs, hipStream_t st) {
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
+      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+      switch (nsp_kp) {
+        case 1: launch_nsp_basis<1>(dX + c0, ldx, nc, st); break;
+        case 2: launch_nsp_basis<2>(dX + c0, ldx, nc, st); break;
+        case 4: launch_nsp_basis<4>(dX + c0, ldx, nc, st); break;
+        case 8: launch_nsp_basis<8>(dX + c0, ldx, nc, st); break;
+        case 16: launch_nsp_basis<16>(dX + c0, ldx, nc, st); break;
+        default: throw Error(HIFAMD_HIFIR_ERROR, "internal error: null-space basis of an unsupported padded size");
+      }
+    }
+    HIP_OK(hipGetLastError());
+  }
+
+  // hifamd_set_nsp_basis on this engine: orthonormalize on the host (import.hpp), ship Q, size the reduction buffers
+  void set_nsp_basis(int64_t k, const T *V, int64_t ldv) {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    HIP_OK(hipSetDevice(device));
+    if (k == 0) {
+      nsp_k = nsp_kp = 0;
+      for (DevBuf *b : {&nsp_Q, &nsp_cpart, &nsp_C}) b->release();
+      return;
+    }
+    const int64_t kp = nsp_padded(k);
+    const std::vector<T> Q = nsp_orthonormalize<T>(lv[0]->n, k, V, ldv, kp);
+    nsp_k = nsp_kp = 0;
+    nsp_Q.upload(Q);
+    nsp_cpart.alloc((size_t)kp * kCgBlocks * 64 * sizeof(T));
+    nsp_C.alloc((size_t)kp * 64 * sizeof(T));
+    nsp_k = (int)k, nsp_kp = (int)kp;
+    nsp_on = false;  // one filter per op
+  }
+
+  // the filter alone, in place (hifamd_nsp_filter_batch / _dev)
+  void nsp_filter_dev(D *dX, int64_t ldx, int64_t nrhs, hipStream_t user) {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    if (nrhs < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "nrhs must be >= 1");
+    if (ldx < nrhs) throw Error(HIFAMD_MISMATCHED_SIZES, "row stride smaller than nrhs");
+    HIP_OK(hipSetDevice(device));
+    apply_nsp(dX, ldx, nrhs, user ? user : stream);
+  }
+  void nsp_filter_host(T *X, int64_t ldx, int64_t nrhs) {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    if (nrhs < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "nrhs must be >= 1");
+    if (ldx < nrhs) throw Error(HIFAMD_MISMATCHED_SIZES, "row stride smaller than nrhs");
+    if (!nsp_on && nsp_k == 0) return;
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * nrhs * sizeof(T);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    HIP_OK(hipMemcpy2DAsync(stage_x.p, nrhs * sizeof(T), X, ldx * sizeof(T), nrhs * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    apply_nsp(stage_x.as<D>(), nrhs, nrhs, stream);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
   }
 
   void launch_part(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int64_t rank, hipStream_t st, int kind,
@@ -2762,6 +2839,9 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_cg_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, mode, k, S);
     };
     vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);  // r = b
+    // projected PCG: with a basis filter P = I - Q Q^H on the solve the iteration runs on the complement of span(Q):
+    // r0 = P b, ||b|| := ||P b||, and every z = M^{-1} r below is already P M^{-1} r (solve_dev filters it)
+    if (nsp_k > 0) apply_nsp(r, nc, nc, stream);
     dot(r, nullptr);
     finish(0, 0);                                        // ||b||
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);   // x = 0
@@ -3095,7 +3175,8 @@ class Engine : public EngineBase {
     const double v[] = {finalize_seconds, capture_ms,     bytes_inverses,  bytes_top,     bytes_tail,           (double)tail_n,
                         (double)tail_level, tail_probe_err, tail_max_abs, (double)tail_rejected, tail_probe_tol, tail_max_growth,
                         (double)levels_from_cache, analysis_seconds, arena, (double)Rmax, tiles, factors, (double)max_nrhs,
-                        skip_w, skip_v, (double)host_repairs};
+                        skip_w, skip_v, (double)host_repairs,
+                        (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0))};
     const int nv = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < cap && i < nv; ++i) o[i] = v[i];
     return nv;
@@ -3437,6 +3518,15 @@ static void do_sync(E *e) {
   e->check_device_error();
 }
 
+// the engine whose filter op names, or NULL when that is the adjoint engine and it was never built (no filter then)
+template <class E>
+static E *nsp_engine(E *e, HifAmdOp op) {
+  if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the filter belongs to HIFAMD_S or HIFAMD_SH");
+  if (!e->finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+  if (op == HIFAMD_S) return e;
+  return e->adj ? e->adj.get() : nullptr;
+}
+
 extern "C" {
 
 const char *hifamd_version(void) { return "hifir_amd 0.1.0 (gfx950)"; }
@@ -3506,12 +3596,58 @@ HifAmdStatus hifamd_set_nsp_const(HifAmdHdl h, HifAmdOp op, int64_t start, int64
   API_BEGIN
   if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the filter belongs to HIFAMD_S or HIFAMD_SH");
   const bool on = !(end >= 0 && start > end);
+  // (one filter per op: a constant-mode filter that is switched on replaces a basis)
   if (h->vt == HIFAMD_D) {
     Engine<double> &E = ENG_D->for_op(op);
     E.nsp_on = on, E.nsp_r0 = start, E.nsp_r1 = end;
+    if (on && E.nsp_k > 0) E.set_nsp_basis(0, nullptr, 0);
   } else {
     Engine<zdouble> &E = ENG_Z->for_op(op);
     E.nsp_on = on, E.nsp_r0 = start, E.nsp_r1 = end;
+    if (on && E.nsp_k > 0) E.set_nsp_basis(0, nullptr, 0);
+  }
+  API_END
+}
+
+HifAmdStatus hifamd_set_nsp_basis(HifAmdHdl h, HifAmdOp op, int64_t k, const void *V, int64_t ldv) {
+  API_BEGIN
+  if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the filter belongs to HIFAMD_S or HIFAMD_SH");
+  if (k < 0 || k > HIFAMD_NSP_MAX) throw Error(HIFAMD_MISMATCHED_SIZES, "a null-space basis has 0 to 16 vectors (HIFAMD_NSP_MAX)");
+  if (k > 0 && (!V || ldv < k)) throw Error(HIFAMD_MISMATCHED_SIZES, "null-space basis: NULL array or row stride smaller than k");
+  const bool fin = h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized;
+  if (!fin) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+  // (removing a filter from an adjoint engine that was never built has nothing to do)
+  if (k == 0 && op == HIFAMD_SH && !(h->vt == HIFAMD_D ? (bool)ENG_D->adj : (bool)ENG_Z->adj)) return HIFAMD_SUCCESS;
+  DISPATCH(ENG_D->for_op(op).set_nsp_basis(k, (const double *)V, ldv), ENG_Z->for_op(op).set_nsp_basis(k, (const zdouble *)V, ldv))
+  API_END
+}
+
+int64_t hifamd_nsp_dim(HifAmdHdl h, HifAmdOp op) {
+  if (!h || !h->eng) return -1;
+  if (op == HIFAMD_S) return h->vt == HIFAMD_D ? ENG_D->nsp_k : ENG_Z->nsp_k;
+  if (op == HIFAMD_SH) {
+    if (h->vt == HIFAMD_D) return ENG_D->adj ? ENG_D->adj->nsp_k : 0;
+    return ENG_Z->adj ? ENG_Z->adj->nsp_k : 0;
+  }
+  return 0;
+}
+
+HifAmdStatus hifamd_nsp_filter_batch(HifAmdHdl h, HifAmdOp op, void *X, int64_t ldx, int64_t nrhs) {
+  API_BEGIN
+  if (h->vt == HIFAMD_D) {
+    if (Engine<double> *E = nsp_engine(ENG_D, op)) E->nsp_filter_host((double *)X, ldx, nrhs);
+  } else {
+    if (Engine<zdouble> *E = nsp_engine(ENG_Z, op)) E->nsp_filter_host((zdouble *)X, ldx, nrhs);
+  }
+  API_END
+}
+
+HifAmdStatus hifamd_nsp_filter_batch_dev(HifAmdHdl h, HifAmdOp op, void *dX, int64_t ldx, int64_t nrhs, void *stream) {
+  API_BEGIN
+  if (h->vt == HIFAMD_D) {
+    if (Engine<double> *E = nsp_engine(ENG_D, op)) E->nsp_filter_dev((double *)dX, ldx, nrhs, (hipStream_t)stream);
+  } else {
+    if (Engine<zdouble> *E = nsp_engine(ENG_Z, op)) E->nsp_filter_dev((cplx *)dX, ldx, nrhs, (hipStream_t)stream);
   }
   API_END
 }

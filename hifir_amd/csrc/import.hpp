@@ -311,6 +311,66 @@ Csr<T> adjoint_of_csr(const Csr<T> &A) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Basis mode of the null-space filter (hifamd_set_nsp_basis): the caller's k vectors V ([n][k] row-interleaved, row
+// stride ldv) -> an orthonormal basis Q of span(V), stored [n][kpad] (the columns k .. kpad-1 are zero: the kernels
+// are compiled for kpad = 1, 2, 4, 8, 16).  Modified Gram-Schmidt in the caller's order, every vector orthogonalized
+// twice against its predecessors, Hermitian inner products.  Vector j is DEPENDENT when its norm after the
+// orthogonalization is at most eps^(2/3) times its norm before: the rank criterion of the dense level (condition
+// limit eps^(-2/3), small_scale/QRCP.hpp:110-117).  A non-finite entry, a zero vector and a dependent vector are
+// refused with kBadPrec, the message naming the vector's index.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kNspMaxHost = 16;  // HIFAMD_NSP_MAX
+
+inline int64_t nsp_padded(int64_t k) {
+  int64_t kp = 1;
+  while (kp < k) kp *= 2;
+  return kp;
+}
+
+template <class T>
+std::vector<T> nsp_orthonormalize(int64_t n, int64_t k, const T *V, int64_t ldv, int64_t kpad) {
+  if (k < 1 || k > kNspMaxHost || kpad < k || n < 1) throw Error(kMismatchedSizes, "null-space basis: need 1 <= k <= 16 vectors");
+  if (!V || ldv < k) throw Error(kMismatchedSizes, "null-space basis: NULL array or row stride smaller than k");
+  const double dep_tol = std::pow(std::numeric_limits<double>::epsilon(), 2.0 / 3.0);
+  std::vector<std::vector<T>> W((size_t)k, std::vector<T>((size_t)n));  // one contiguous vector each
+  auto norm = [n](const std::vector<T> &v) {
+    double s = 0.0;
+    for (int64_t i = 0; i < n; ++i) s += real_(conj_(v[(size_t)i]) * v[(size_t)i]);
+    return std::sqrt(s);
+  };
+  for (int64_t j = 0; j < k; ++j) {
+    std::vector<T> &w = W[(size_t)j];
+    for (int64_t i = 0; i < n; ++i) {
+      w[(size_t)i] = V[i * ldv + j];
+      if (!std::isfinite(abs1_(w[(size_t)i])))
+        throw Error(kBadPrec, "null-space basis: vector " + std::to_string(j) + " has a non-finite entry (row " + std::to_string(i) + ")");
+    }
+    const double before = norm(w);
+    if (!(before > 0.0) || !std::isfinite(before))
+      throw Error(kBadPrec, "null-space basis: vector " + std::to_string(j) + " is zero (or its norm overflows)");
+    for (int pass = 0; pass < 2; ++pass)
+      for (int64_t l = 0; l < j; ++l) {
+        const std::vector<T> &q = W[(size_t)l];
+        T h = T(0);
+        for (int64_t i = 0; i < n; ++i) h += conj_(q[(size_t)i]) * w[(size_t)i];
+        for (int64_t i = 0; i < n; ++i) w[(size_t)i] -= h * q[(size_t)i];
+      }
+    const double after = norm(w);
+    if (!(after > dep_tol * before)) {
+      char ratio[32];
+      std::snprintf(ratio, sizeof(ratio), "%.3e", after / before);
+      throw Error(kBadPrec, "null-space basis: vector " + std::to_string(j) + " depends numerically on the vectors before it (" + ratio +
+                                " of its norm is left after orthogonalization, the limit is eps^(2/3))");
+    }
+    for (int64_t i = 0; i < n; ++i) w[(size_t)i] /= after;
+  }
+  std::vector<T> Q((size_t)(n * kpad), T(0));
+  for (int64_t j = 0; j < k; ++j)
+    for (int64_t i = 0; i < n; ++i) Q[(size_t)(i * kpad + j)] = W[(size_t)j][(size_t)i];
+  return Q;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Invariants of everything the kernels index with.  hifamd_finalize runs this right before the upload: a hierarchy
 // whose converted arrays are not what the conversion must have produced (whatever the cause) is refused with
 // HIFAMD_HIFIR_ERROR instead of being applied -- a wrong row pointer on the device is a hang or a wrong answer.

@@ -28,6 +28,7 @@
 //   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
 //   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
+//   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -2263,6 +2264,111 @@ __global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, co
   }
   __syncthreads();
   if (threadIdx.x == 0) S.ctl[0] = cnt;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Basis mode of the null-space filter (Engine::apply_nsp): every column x of a 64-column tile becomes x - Q (Q^H x),
+// Q [n][K] orthonormal (K = the basis padded with zero vectors to 1, 2, 4, 8 or 16, a compile-time size so that the K
+// accumulators stay in registers).  Three launches: k_nsp_coef (block partials of C = Q^H X), k_nsp_finish (one
+// workgroup per basis vector adds them), k_nsp_sub (x_i -= sum_j q_ij c_j).  Same row walk and reduction order as
+// k_cg_dot / k_cg_finish: lane = column, wave w of block b owns the rows i = 4 b + w + k * 4 kCgBlocks, wave partials
+// added in wave order, block partials in k_cg_finish's order; nothing depends on nc or on the other columns, so a
+// column's bits are the same alone and in any batch.  The row of Q is the same for all lanes of a wave: the row
+// index is made provably uniform (readfirstlane) so that it is fetched by scalar loads.  X has a row stride (ldx).
+// ---------------------------------------------------------------------------------------------
+constexpr int kNspMax = 16;  // HIFAMD_NSP_MAX
+
+__device__ __forceinline__ int nsp_wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// acc[j] += conj(q[j]) x, q the (wave-uniform) row of Q
+template <class T, int K>
+__device__ __forceinline__ void nsp_acc_row(T (&acc)[K], const T *__restrict__ q, T xi) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) acc[j] = vadd(acc[j], vmul(vconj(q[j]), xi));
+}
+// sum_j q[j] c[j], j ascending
+template <class T, int K>
+__device__ __forceinline__ T nsp_row_dot(const T *__restrict__ q, const T (&cj)[K]) {
+  T s = vmul(q[0], cj[0]);
+#pragma unroll
+  for (int j = 1; j < K; ++j) s = vadd(s, vmul(q[j], cj[j]));
+  return s;
+}
+
+template <class T, int K>
+__global__ void __launch_bounds__(256) k_nsp_coef(int64_t n, int nc, const T *__restrict__ x, int64_t ldx,
+                                                  const T *__restrict__ Q /* [n][K] */,
+                                                  T *__restrict__ partial /* [K][kCgBlocks][64] */) {
+  __shared__ T sm[2][256];
+  const int c = threadIdx.x & 63, w = nsp_wave_id();
+  const int64_t stride = (int64_t)kCgBlocks * 4;
+  T acc[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) acc[j] = vzero(T());
+  if (c < nc) {
+    // four rows per trip so that four loads of x are in flight (eight measured slower); the rows are still
+    // accumulated in walk order
+    int64_t i = (int64_t)blockIdx.x * 4 + w;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+      const T x0 = x[i * ldx + c], x1 = x[(i + stride) * ldx + c], x2 = x[(i + 2 * stride) * ldx + c],
+              x3 = x[(i + 3 * stride) * ldx + c];
+      nsp_acc_row<T, K>(acc, Q + i * K, x0);
+      nsp_acc_row<T, K>(acc, Q + (i + stride) * K, x1);
+      nsp_acc_row<T, K>(acc, Q + (i + 2 * stride) * K, x2);
+      nsp_acc_row<T, K>(acc, Q + (i + 3 * stride) * K, x3);
+    }
+    for (; i < n; i += stride) nsp_acc_row<T, K>(acc, Q + i * K, x[i * ldx + c]);
+  }
+  // the four wave partials of every basis vector in wave order (cg_block_partial's pattern, two LDS planes in turn)
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    T *s = sm[j & 1];
+    s[threadIdx.x] = acc[j];
+    __syncthreads();
+    if (threadIdx.x < 64)
+      partial[((int64_t)j * kCgBlocks + blockIdx.x) * 64 + c] = vadd(vadd(vadd(s[c], s[64 + c]), s[128 + c]), s[192 + c]);
+  }
+}
+
+// C[j][c] = the kCgBlocks partials of basis vector j = blockIdx.x in k_cg_finish's order (wave w takes blocks w, w + 16,
+// ..., then the 16 wave sums in wave order); all 64 columns, a column beyond nc holds zeros
+template <class T>
+__global__ void __launch_bounds__(1024) k_nsp_finish(const T *__restrict__ partial, T *__restrict__ C /* [K][64] */) {
+  __shared__ T sm[16 * 64];
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  const T *__restrict__ p = partial + (int64_t)blockIdx.x * kCgBlocks * 64;
+  T acc = vzero(T());
+  for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, p[(int64_t)b * 64 + c]);
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    T tot = vzero(T());
+    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
+    C[(int64_t)blockIdx.x * 64 + c] = tot;
+  }
+}
+
+// x_i -= sum_j q_ij c_j, j ascending, the sum formed first and subtracted once
+template <class T, int K>
+__global__ void __launch_bounds__(256) k_nsp_sub(int64_t n, int nc, T *__restrict__ x, int64_t ldx,
+                                                 const T *__restrict__ Q /* [n][K] */, const T *__restrict__ C /* [K][64] */) {
+  const int c = threadIdx.x & 63, w = nsp_wave_id();
+  if (c >= nc) return;
+  T cj[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) cj[j] = C[j * 64 + c];
+  const int64_t stride = (int64_t)kCgBlocks * 4;
+  int64_t i = (int64_t)blockIdx.x * 4 + w;
+  for (; i + 3 * stride < n; i += 4 * stride) {  // (four rows per trip: four loads of x in flight)
+    T *p0 = x + i * ldx + c, *p1 = x + (i + stride) * ldx + c, *p2 = x + (i + 2 * stride) * ldx + c,
+      *p3 = x + (i + 3 * stride) * ldx + c;
+    const T x0 = *p0, x1 = *p1, x2 = *p2, x3 = *p3;
+    *p0 = vsub(x0, nsp_row_dot<T, K>(Q + i * K, cj));
+    *p1 = vsub(x1, nsp_row_dot<T, K>(Q + (i + stride) * K, cj));
+    *p2 = vsub(x2, nsp_row_dot<T, K>(Q + (i + 2 * stride) * K, cj));
+    *p3 = vsub(x3, nsp_row_dot<T, K>(Q + (i + 3 * stride) * K, cj));
+  }
+  for (; i < n; i += stride) x[i * ldx + c] = vsub(x[i * ldx + c], nsp_row_dot<T, K>(Q + i * K, cj));
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -211,7 +211,7 @@ class HIF:
         keys = ["finalize_s", "graph_capture_ms", "bytes_inverses", "bytes_top", "bytes_tail", "tail_rows", "tail_level",
                 "tail_probe_relerr", "tail_max_abs", "tail_rejected", "tail_probe_tol", "tail_max_growth",
                 "analysis_cached_levels", "analysis_s", "arena_bytes", "arena_cols", "tile_bytes", "factor_bytes", "max_nrhs",
-                "rows_not_stored_L", "rows_not_stored_U", "host_copy_repairs"]
+                "rows_not_stored_L", "rows_not_stored_U", "host_copy_repairs", "nsp_basis_bytes"]
         return {key: float(s[i]) for i, key in enumerate(keys[:max(0, k)])}
 
     def level_stats(self, level):
@@ -364,6 +364,44 @@ class HIF:
         """Constant-mode null-space filter of solve() (HIF::nsp; trans: HIF::nsp_tran): rows [start, end) of
         every solution lose their mean; start > end >= 0 removes the filter."""
         _check(lib().hifamd_set_nsp_const(self._h, OP_SH if trans else OP_S, int(start), int(end)))
+
+    def set_nsp_basis(self, V, trans=False):
+        """Basis mode of the null-space filter (hifamd_set_nsp_basis): V, (n,) or (n, k) with 1 <= k <= 16, spans the
+        null space; after every solve (trans: every M^{-H} solve), also inside hifir / gmres / bicgstab, each column x
+        becomes x - Q (Q^H x) with Q an orthonormal basis of span(V).  None removes it.  With a basis set, pcg() runs
+        projected on the complement of span(Q)."""
+        op = OP_SH if trans else OP_S
+        if V is None:
+            _check(lib().hifamd_set_nsp_basis(self._h, op, 0, None, 0))
+            return
+        V = np.asarray(V)
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        V = np.ascontiguousarray(V, dtype=self.dtype)
+        if V.ndim != 2 or V.shape[0] != self.nrows():
+            raise HifAmdError(2, "null-space basis: expected (n,) or (n, k)")
+        _check(lib().hifamd_set_nsp_basis(self._h, op, V.shape[1], _p(V), V.shape[1]))
+
+    def nsp_dim(self, trans=False):
+        """Vectors of the basis filter in force (0: none, or constant mode)."""
+        return int(lib().hifamd_nsp_dim(self._h, OP_SH if trans else OP_S))
+
+    def nsp_filter(self, X, trans=False):
+        """The filter in force (basis or constant mode) alone, in place, on X ((n,) or (n, nrhs); a C-contiguous host
+        array of the handle's dtype, or a CUDA tensor, which is not synchronized); returns X.  No filter: X as it is."""
+        op = OP_SH if trans else OP_S
+        if _is_torch(X):
+            X2 = self._dev_block(X.reshape(X.shape[0], -1), "X")
+            if X2.data_ptr() != X.data_ptr():
+                raise HifAmdError(2, "X: blocks must be row-interleaved (unit column stride)")
+            _check(lib().hifamd_nsp_filter_batch_dev(self._h, op, X2.data_ptr(), X2.stride(0), X2.shape[1], None))
+            return X
+        if not isinstance(X, np.ndarray) or X.dtype != self.dtype or not X.flags.c_contiguous or X.ndim not in (1, 2) \
+                or X.shape[0] != self.nrows():
+            raise HifAmdError(2, f"X: expected a C-contiguous {self.dtype} array of shape (n,) or (n, nrhs)")
+        nrhs = 1 if X.ndim == 1 else X.shape[1]
+        _check(lib().hifamd_nsp_filter_batch(self._h, op, _p(X), nrhs, nrhs))
+        return X
 
     def mmultiply(self, x, trans=False, rank=-1):
         """y = M x (trans: M^H x), the multilevel product HIF::mmultiply (builder.hpp:503-513) -- the inverse

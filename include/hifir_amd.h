@@ -152,7 +152,7 @@ HifAmdStatus hifamd_stats(HifAmdHdl h, double *stats16);
  * 19 / 20 rows (all levels) whose L / U result the FIRST solve of a level does not store because nothing reads it from
  * memory (real handles, sparse-own levels; HIFIR_AMD_SKIP_ROWS=0: none), 21 arrays of the host copy that hifamd_finalize found
  * changed since hifamd_add_level -- not by this library -- and rebuilt from the imported arrays (a warning names them on stderr;
- * anything it cannot rebuild is refused).
+ * anything it cannot rebuild is refused), 22 bytes of the null-space bases resident in HBM (hifamd_set_nsp_basis, both ops).
  * -1 for a NULL handle. */
 int hifamd_stats_ext(HifAmdHdl h, double *out, int cap);
 /* Per-level sizes (what the SURVEY 8(d) byte formula needs level by level): 0 m, 1 n, 2 nnz(L_B), 3 nnz(U_B), 4 nnz(E),
@@ -210,6 +210,32 @@ HifAmdStatus hifamd_hifir_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, vo
  * filter.  Unlike the reference (builder.hpp:439) batched applies are filtered as well.  Needs a
  * finalized handle. */
 HifAmdStatus hifamd_set_nsp_const(HifAmdHdl h, HifAmdOp op, int64_t start, int64_t end);
+/* Basis mode (the device form of the reference's user filter, NspFilter.hpp USER_OR / USER_CB: a host callback cannot
+ * run inside a device-resident Krylov loop, so the caller hands over vectors that span the null space): after every
+ * HIFAMD_S (op = HIFAMD_S) or HIFAMD_SH (op = HIFAMD_SH) apply -- inside iterative refinement, GMRES / FGMRES and
+ * BiCGSTAB too -- every column x becomes x - Q (Q^H x), Q an orthonormal basis of span(V).  V: host pointer, [n][k]
+ * row-interleaved with row stride ldv (the multi-RHS layout), 1 <= k <= HIFAMD_NSP_MAX, of the handle's value type;
+ * copied, orthonormalized on the host (modified Gram-Schmidt in the caller's order, twice, Hermitian inner products)
+ * and shipped to HBM.  k = 0 (V may be NULL) removes the basis.  One filter per op: setting a basis replaces a
+ * constant-mode filter on that op, and switching a constant-mode filter on replaces a basis.  Needs a finalized handle.
+ * Refusals, in this order: NULL handle HIFAMD_NULL_OBJ; op not HIFAMD_S / HIFAMD_SH, k < 0, k > HIFAMD_NSP_MAX, k > 0
+ * with V NULL or ldv < k HIFAMD_MISMATCHED_SIZES; handle not finalized HIFAMD_BAD_PREC; a non-finite entry, a zero
+ * vector or a vector that depends numerically on its predecessors (norm after orthogonalization <= eps^(2/3) of the
+ * norm before, the rank criterion of the dense level, QRCP.hpp:110-117) HIFAMD_BAD_PREC, the message naming the
+ * vector's index.  A column's filtered bits do not depend on the batch it travels in.
+ * Krylov drivers: GMRES / FGMRES and BiCGSTAB keep their semantics, the filter acts on their applies only -- a caller
+ * who wants a consistent right-hand side calls hifamd_nsp_filter_batch on it first.  PCG with a basis on HIFAMD_S runs
+ * projected (see hifamd_pcg_batch). */
+#define HIFAMD_NSP_MAX 16
+HifAmdStatus hifamd_set_nsp_basis(HifAmdHdl h, HifAmdOp op, int64_t k, const void *V, int64_t ldv);
+/* vectors of the basis filter in force on op (0: none or constant mode; -1: NULL handle) */
+int64_t hifamd_nsp_dim(HifAmdHdl h, HifAmdOp op);
+/* The filter in force on op (basis or constant mode) alone, in place, on [n][nrhs] blocks (what a caller uses to make b
+ * consistent or to project a start vector).  No filter set: the block is left as it is.  Host pointers (returns when
+ * done) / device pointers, enqueued on `stream` (NULL = the handle's own) and not synchronized, like
+ * hifamd_apply_batch_dev. */
+HifAmdStatus hifamd_nsp_filter_batch(HifAmdHdl h, HifAmdOp op, void *X, int64_t ldx, int64_t nrhs);
+HifAmdStatus hifamd_nsp_filter_batch_dev(HifAmdHdl h, HifAmdOp op, void *dX, int64_t ldx, int64_t nrhs, void *stream);
 
 /* ---- lhf?Apply with an operator tag (libhifir.h:685, libhifir.cpp:447-472), batched ----------- */
 /* op = HIFAMD_S / HIFAMD_SH: nirs <= 1 direct apply (ir_status, if given, gets {1, -1} per column);
@@ -263,8 +289,14 @@ int hifamd_hermitian(HifAmdHdl h);
  * SpMM and four fused vector passes serve every column per step, and the host reads back one integer per step.
  * Inner products are Hermitian (sum conj(a_i) b_i) and their summation order depends on n only, so a column's result
  * does not depend on the batch it is solved in.  Needs hifamd_set_matrix and a Hermitian M^{-1} (hifamd_hermitian; the
- * HIFAMD_BAD_PREC message names the level and the array of the first violation); a null-space filter on HIFAMD_S
- * (hifamd_set_nsp_const) is not supported and refused with HIFAMD_BAD_PREC.  maxit < 1 or rtol <= 0:
+ * HIFAMD_BAD_PREC message names the level and the array of the first violation); a constant-mode null-space filter on
+ * HIFAMD_S (hifamd_set_nsp_const) is not supported and refused with HIFAMD_BAD_PREC.  With a BASIS filter on HIFAMD_S
+ * (hifamd_set_nsp_basis, P = I - Q Q^H) PCG runs projected, on the complement of span(Q): r0 = P b, ||b|| in the
+ * stopping test is ||P b||, every z is P M^{-1} r; when Q spans the null space of a Hermitian positive semi-definite A
+ * the operator PCG sees is P M^{-1} P, Hermitian with M^{-1}, and x is the solution without a component in span(Q).
+ * The inconsistent part of b, (I - P) b, is DROPPED: the result solves A x = P b, i.e. it is the filtered
+ * representative of the least-squares solutions only when Q spans null(A); if Q is not a null space of A the
+ * breakdown flag or maxit report it.  P b = 0 is the zero column.  maxit < 1 or rtol <= 0:
  * HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  Per column: flags[c] = 0 converged / 1 breakdown (p^H A p
  * or r^H M^{-1} r not positive or not finite: A or M is not positive definite on that column) / 2 reached maxit,
  * iters[c] = iterations (a zero column: x = 0, flag 0, 0 iterations); either may be NULL.  Host pointers; the _dev
@@ -284,7 +316,8 @@ HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void
  * stay in HBM (five work vectors r, p, v, y, t per 64-column tile; r^ is B itself, read in place; no restarts); the
  * host reads back one integer after each of the two tests of an iteration.  Inner products are Hermitian
  * (sum conj(a_i) b_i) and their summation order depends on n only, so a column's result does not depend on the batch
- * it is solved in.  A null-space filter on HIFAMD_S (hifamd_set_nsp_const) filters every M^{-1} apply, as in GMRES;
+ * it is solved in.  A null-space filter on HIFAMD_S (hifamd_set_nsp_const / hifamd_set_nsp_basis) filters every
+ * M^{-1} apply, as in GMRES, and nothing else: b is taken as it is (hifamd_nsp_filter_batch makes it consistent);
  * M^{-1} need not be Hermitian.  Needs hifamd_set_matrix (else HIFAMD_BAD_PREC, as for a handle not finalized);
  * maxit < 1 or rtol <= 0: HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  Per column: flags[c] = 0
  * converged / 1 breakdown ((r^, v), (t, t), omega, rho' or the initial rho exactly zero or not finite; x keeps its last

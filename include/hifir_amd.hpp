@@ -145,6 +145,30 @@ class HIF {
     detail::check(hifamd_set_nsp_const(_h, trans ? HIFAMD_SH : HIFAMD_S, (std::int64_t)start,
                                        end == static_cast<size_type>(-1) ? -1 : (std::int64_t)end));
   }
+  /// Basis mode of the filter (the device form of NspFilter's user routine): V holds k vectors of nrows() entries one
+  /// after the other (k = V.size() / nrows(), 1 <= k <= HIFAMD_NSP_MAX) that span the null space; every solve result x
+  /// becomes x - Q (Q^H x).  An empty V removes it.
+  template <class Array>
+  void set_nsp_basis(const Array &V, const bool trans = false) {
+    require();
+    const size_type n = nrows(), k = n ? V.size() / n : 0u;
+    if (k * n != V.size()) throw std::runtime_error("hifir_amd: a null-space basis holds k vectors of nrows() entries");
+    std::vector<value_type> W(V.size());  // [n][k] row-interleaved, the layout of the C ABI
+    for (size_type j = 0; j < k; ++j)
+      for (size_type i = 0; i < n; ++i) W[i * k + j] = V.data()[j * n + i];
+    detail::check(hifamd_set_nsp_basis(_h, trans ? HIFAMD_SH : HIFAMD_S, (std::int64_t)k, k ? W.data() : nullptr, (std::int64_t)k));
+  }
+  size_type nsp_dim(const bool trans = false) const {
+    const std::int64_t k = _h ? hifamd_nsp_dim(_h, trans ? HIFAMD_SH : HIFAMD_S) : 0;
+    return k > 0 ? (size_type)k : 0u;
+  }
+  /// the filter in force alone, in place, on one vector (what makes a right-hand side consistent)
+  template <class Array>
+  void nsp_filter(Array &x, const bool trans = false) const {
+    require();
+    if (x.size() != nrows()) throw std::runtime_error("hifir_amd: unmatched sizes");
+    detail::check(hifamd_nsp_filter_batch(_h, trans ? HIFAMD_SH : HIFAMD_S, x.data(), 1, 1));
+  }
 
   // ---- x = M^{-1} b / M^{-H} b (builder.hpp:409-423) ---------------------------------------------
   template <class RhsType, class SolType>
