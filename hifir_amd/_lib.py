@@ -24,6 +24,9 @@ SIGNATURES = {
     "hifamd_nsp_dim": (_i64, [_vp, _int]),
     "hifamd_nsp_filter_batch": (_int, [_vp, _int, _vp, _i64, _i64]),
     "hifamd_nsp_filter_batch_dev": (_int, [_vp, _int, _vp, _i64, _i64, _vp]),
+    "hifamd_nsp_find": (_int, [_vp, _int, _i64, _dbl, _dbl, _int, _int, _i64, _vp, _i64, C.c_uint64, _int, _vp, _vp, _i64,
+                               _vp, _vp]),
+    "hifamd_nsp_get_basis": (_i64, [_vp, _int, _vp, _i64]),
     "hifamd_save": (_int, [_vp, C.c_char_p]),
     "hifamd_save_ex": (_int, [_vp, C.c_char_p, _int]),
     "hifamd_load": (_int, [C.c_char_p, _int, C.POINTER(_vp)]),

@@ -1486,10 +1486,17 @@ class Engine : public EngineBase {
     upload_matrix(C);
   }
 
+  double A_norm_inf = 0.0;  // largest row sum of |a_ij| of THIS engine's matrix (the adjoint engine: of A^H), for nsp_find
   void upload_matrix(const Csr<T> &C) {
     HIP_OK(hipSetDevice(device));
     A.upload(C, nullptr);
     HIP_OK(hipStreamSynchronize(stream));  // (transfers were synchronous on the transfer stream)
+    A_norm_inf = 0.0;
+    for (int64_t i = 0; i < C.nrows; ++i) {
+      double s = 0.0;
+      for (int32_t k = C.ptr[(size_t)i]; k < C.ptr[(size_t)i + 1]; ++k) s += abs_(C.val[(size_t)k]);
+      if (s > A_norm_inf || s != s) A_norm_inf = s;
+    }
     has_A = true;
   }
 
@@ -2363,6 +2370,127 @@ class Engine : public EngineBase {
     HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
     check_device_error();
+  }
+
+  // ---- null-space search (hifamd_nsp_find) on this engine: null(A) on the primary, null(A^H) on the adjoint --------
+  // B = -A X0 lies in range(A), so A D = B is consistent; D = gmres_dev(B) to rtol; V = X0 + D has ||A v|| <= rtol
+  // ||A x0|| per column and numerical rank = nullity.  Then, on 16 x 16 matrices (import.hpp): G = V^H V, rotation +
+  // scaling by its eigendecomposition (columns ordered by weight), and TWICE the order-preserving Cholesky step (a
+  // second eigendecomposition of G ~ I would rotate the null vectors into the other columns).  Accepted by the
+  // definition: res_j = ||A q_j||_2 <= tol ||A||_inf, the leading prefix, at most kmax.  Three [n][16] blocks live
+  // for the duration of the call only.  The filter in force is suspended (GMRES's applies would project the sought
+  // component away) and put back on every exit.
+  struct NspSuspend {
+    Engine<T> &E;
+    bool on;
+    int k, kp;
+    explicit NspSuspend(Engine<T> &e) : E(e), on(e.nsp_on), k(e.nsp_k), kp(e.nsp_kp) { e.nsp_on = false, e.nsp_k = e.nsp_kp = 0; }
+    ~NspSuspend() { E.nsp_on = on, E.nsp_k = k, E.nsp_kp = kp; }
+  };
+  // G[j * 64 + c] = v_j^H v_c of V [n][16]: the filter's reduction with Q = X = V (fixed order), read back
+  void nsp_gram(const D *V, D *part, D *C, std::vector<T> &G) {
+    const int64_t n = lv[0]->n;
+    hipLaunchKernelGGL((k_nsp_coef<D, kNspMax>), dim3(kCgBlocks), dim3(256), 0, stream, n, kNspMax, V, (int64_t)kNspMax, V, part);
+    hipLaunchKernelGGL((k_nsp_finish<D>), dim3(kNspMax), dim3(1024), 0, stream, (const D *)part, C);
+    HIP_OK(hipGetLastError());
+    G.resize((size_t)kNspMax * 64);
+    HIP_OK(hipMemcpyAsync(G.data(), C, G.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+  // V <- V M for a host 16 x 16 row-major M (the stream is idle when M's device copy is overwritten: nsp_gram synchronized)
+  void nsp_rmul(D *V, const std::vector<T> &M, D *dM) {
+    const int64_t n = lv[0]->n;
+    HIP_OK(hipMemcpyAsync(dM, M.data(), (size_t)kNspMax * kNspMax * sizeof(T), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    const int64_t g = std::min<int64_t>((n + 15) / 16, 4096);
+    hipLaunchKernelGGL((k_blk_rmul<D>), dim3((unsigned)std::max<int64_t>(g, 1)), dim3(256), 0, stream, n, V, (const D *)dM);
+    HIP_OK(hipGetLastError());
+  }
+  void nsp_find(int64_t kmax, double tol, double rtol, int restart, int maxit, int64_t rank, const T *X0, int64_t ldx0,
+                uint64_t seed, bool install, int64_t *found, T *Qout, int64_t ldq, double *resid16, int *info4) {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "the null-space search needs the matrix (hifamd_set_matrix)");
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const int K = kNspMax;
+    *found = 0;
+    NspSuspend guard(*this);
+    DevBuf bV, bB, bD, bPart, bC, bM;
+    const size_t blk = (size_t)n * K * sizeof(T);
+    bV.alloc(blk), bB.alloc(blk), bD.alloc(blk);
+    bPart.alloc((size_t)K * kCgBlocks * 64 * sizeof(T)), bC.alloc((size_t)K * 64 * sizeof(T)), bM.alloc((size_t)K * K * sizeof(T));
+    D *V = bV.as<D>(), *B = bB.as<D>(), *Dx = bD.as<D>();
+    if (X0) {
+      HIP_OK(hipMemcpy2DAsync(V, K * sizeof(T), X0, ldx0 * sizeof(T), K * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    } else {
+      hipLaunchKernelGGL((k_probe_fill<D>), dim3(vec_grid(n * K)), dim3(256), 0, stream, n, seed, V);
+    }
+    vec_op(0, n, K, Dx, K, nullptr, 0, nullptr, 0);
+    resid_dev((const D *)Dx, K, (const D *)V, K, B, K, K);  // B = 0 - A X0
+    std::vector<int> flags((size_t)K, 0), iters((size_t)K, 0);
+    gmres_dev((const D *)B, K, Dx, K, K, restart, rtol, maxit, rank, flags.data(), iters.data());
+    vec_op(2, n, K, V, K, (const D *)Dx, K, nullptr, 0);  // V = X0 + D
+    bool finite = true;
+    std::vector<T> G, M((size_t)K * K);
+    std::vector<double> w((size_t)K);
+    nsp_gram(V, bPart.as<D>(), bC.as<D>(), G);
+    finite = finite && nsp_gram_finite(G.data(), 64);
+    int cand = nsp_find_rotation<T>(G.data(), 64, M.data(), w.data());
+    nsp_rmul(V, M, bM.as<D>());
+    for (int pass = 0; pass < 2; ++pass) {
+      nsp_gram(V, bPart.as<D>(), bC.as<D>(), G);
+      finite = finite && nsp_gram_finite(G.data(), 64);
+      cand = std::min(cand, nsp_chol_inverse<T>(G.data(), 64, M.data()));
+      nsp_rmul(V, M, bM.as<D>());
+    }
+    spmv_dev((const D *)V, K, B, K, K, nullptr);  // B = A Q
+    std::vector<double> res;
+    col_norms(B, K, n, K, res);
+    check_device_error();
+    std::vector<double> rel((size_t)K);
+    for (int j = 0; j < K; ++j) {
+      rel[(size_t)j] = A_norm_inf > 0.0 ? res[(size_t)j] / A_norm_inf : res[(size_t)j];
+      if (j < cand && !std::isfinite(rel[(size_t)j])) finite = false;
+      if (j >= cand) rel[(size_t)j] = std::numeric_limits<double>::infinity();  // a dropped candidate (a zero column) is no null vector
+    }
+    int64_t nacc = 0;
+    while (nacc < cand && rel[(size_t)nacc] <= tol) ++nacc;
+    if (!finite) nacc = 0;
+    const int64_t k = std::min<int64_t>(nacc, kmax);
+    if (resid16) std::copy(rel.begin(), rel.end(), resid16);
+    if (info4) {
+      info4[0] = info4[1] = 0;
+      for (int j = 0; j < K; ++j) info4[0] += flags[(size_t)j] != 0, info4[1] = std::max(info4[1], iters[(size_t)j]);
+      info4[2] = (nacc > kmax || k == K) ? 1 : 0;
+      info4[3] = finite ? 0 : 1;
+    }
+    if (k > 0 && Qout) {
+      HIP_OK(hipMemcpy2DAsync(Qout, ldq * sizeof(T), V, K * sizeof(T), (size_t)k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+    }
+    if (k > 0 && install) {
+      // the columns are orthonormal already: no host round trip.  Everything that can fail happens on local buffers;
+      // the engine's are exchanged last
+      const int64_t kp = nsp_padded(k);
+      DevBuf nQ, nPart, nC;
+      nQ.alloc((size_t)n * kp * sizeof(T)), nPart.alloc((size_t)kp * kCgBlocks * 64 * sizeof(T)), nC.alloc((size_t)kp * 64 * sizeof(T));
+      HIP_OK(hipMemsetAsync(nQ.p, 0, nQ.bytes, stream));
+      HIP_OK(hipMemcpy2DAsync(nQ.p, kp * sizeof(T), V, K * sizeof(T), (size_t)k * sizeof(T), n, hipMemcpyDeviceToDevice, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+      auto exchange = [](DevBuf &a, DevBuf &b) { std::swap(a.p, b.p), std::swap(a.bytes, b.bytes), std::swap(a.owner, b.owner); };
+      exchange(nsp_Q, nQ), exchange(nsp_cpart, nPart), exchange(nsp_C, nC);
+      guard.on = false, guard.k = (int)k, guard.kp = (int)kp;  // one filter per op
+    }
+    *found = k;
+  }
+  // hifamd_nsp_get_basis: the nsp_k columns of the basis in force, [n][nsp_k] into Q (row stride ldq)
+  int64_t nsp_get_basis(T *Q, int64_t ldq) {
+    if (nsp_k == 0) return 0;
+    if (!Q || ldq < nsp_k) return -1;
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipMemcpy2DAsync(Q, ldq * sizeof(T), nsp_Q.p, nsp_kp * sizeof(T), (size_t)nsp_k * sizeof(T), lv[0]->n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return nsp_k;
   }
 
   void launch_part(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int64_t rank, hipStream_t st, int kind,
@@ -3650,6 +3778,43 @@ HifAmdStatus hifamd_nsp_filter_batch_dev(HifAmdHdl h, HifAmdOp op, void *dX, int
     if (Engine<zdouble> *E = nsp_engine(ENG_Z, op)) E->nsp_filter_dev((cplx *)dX, ldx, nrhs, (hipStream_t)stream);
   }
   API_END
+}
+
+HifAmdStatus hifamd_nsp_find(HifAmdHdl h, HifAmdOp op, int64_t kmax, double tol, double rtol, int restart, int maxit,
+                             int64_t rank, const void *X0, int64_t ldx0, uint64_t seed, int install, int64_t *found, void *Q,
+                             int64_t ldq, double *resid16, int *info4) {
+  API_BEGIN
+  if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "a null space belongs to HIFAMD_S (A) or HIFAMD_SH (A^H)");
+  if (kmax < 1 || kmax > HIFAMD_NSP_MAX) throw Error(HIFAMD_MISMATCHED_SIZES, "kmax must be 1 to 16 (HIFAMD_NSP_MAX)");
+  if (!(tol > 0.0) || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need tol > 0 and rtol > 0");
+  if (restart < 1 || maxit < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "need restart >= 1 and maxit >= 1");
+  if (X0 && ldx0 < HIFAMD_NSP_MAX) throw Error(HIFAMD_MISMATCHED_SIZES, "probe block: row stride smaller than 16 (HIFAMD_NSP_MAX)");
+  if (Q && ldq < kmax) throw Error(HIFAMD_MISMATCHED_SIZES, "basis output: row stride smaller than kmax");
+  if (!found) throw Error(HIFAMD_MISMATCHED_SIZES, "found: NULL output");
+  *found = 0;
+  // (before for_op: asking for the adjoint engine of a handle that cannot serve the call would build it first)
+  if (!(h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized)) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+  if (!(h->vt == HIFAMD_D ? ENG_D->has_A : ENG_Z->has_A)) throw Error(HIFAMD_BAD_PREC, "the null-space search needs the matrix (hifamd_set_matrix)");
+  DISPATCH(ENG_D->for_op(op).nsp_find(kmax, tol, rtol, restart, maxit, rank, (const double *)X0, ldx0, seed, install != 0, found,
+                                      (double *)Q, ldq, resid16, info4),
+           ENG_Z->for_op(op).nsp_find(kmax, tol, rtol, restart, maxit, rank, (const zdouble *)X0, ldx0, seed, install != 0, found,
+                                      (zdouble *)Q, ldq, resid16, info4))
+  API_END
+}
+
+int64_t hifamd_nsp_get_basis(HifAmdHdl h, HifAmdOp op, void *Q, int64_t ldq) {
+  if (!h || !h->eng) return -1;
+  try {
+    if (op == HIFAMD_S) return h->vt == HIFAMD_D ? ENG_D->nsp_get_basis((double *)Q, ldq) : ENG_Z->nsp_get_basis((zdouble *)Q, ldq);
+    if (op == HIFAMD_SH) {
+      if (h->vt == HIFAMD_D) return ENG_D->adj ? ENG_D->adj->nsp_get_basis((double *)Q, ldq) : 0;
+      return ENG_Z->adj ? ENG_Z->adj->nsp_get_basis((zdouble *)Q, ldq) : 0;
+    }
+  } catch (const std::exception &e) {
+    set_err(e.what());
+    return -1;
+  }
+  return 0;
 }
 
 int hifamd_debug_checksums(HifAmdHdl h, uint64_t *out, int cap) {

@@ -371,6 +371,101 @@ std::vector<T> nsp_orthonormalize(int64_t n, int64_t k, const T *V, int64_t ldv,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Host side of the null-space search (hifamd_nsp_find): the 16 x 16 steps between the device passes, and the host twin
+// of the probe generator.  A Gram matrix G is handed over as the device leaves it: G[j * ldg + c] = v_j^H v_c (row j =
+// the conjugated vector); only the triangle c <= j is read.  Every result is a row-major 16 x 16 matrix M for the
+// update V <- V M (kernels.hip.hpp k_blk_rmul).  Both steps return how many LEADING columns they kept: from the first
+// column that fails on, the columns of M are zero (the candidates are dropped, which is not an error).
+// ---------------------------------------------------------------------------------------------
+// entry `counter` of the probe stream of `seed` (include/hifir_amd.h states the formula; kernels.hip.hpp probe_value)
+inline double nsp_probe_value(uint64_t seed, uint64_t counter) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * counter;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return 2.0 * ((double)(z >> 11) * 0x1.0p-53) - 1.0;
+}
+// the [n][16] probe block hifamd_nsp_find generates for X0 == NULL, into X with row stride ldx >= 16
+template <class T>
+void nsp_probe_fill(int64_t n, uint64_t seed, T *X, int64_t ldx) {
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = 0; j < kNspMaxHost; ++j) {
+      const double re = nsp_probe_value(seed, (uint64_t)(kNspMaxHost * i + j) + 1);
+      if constexpr (sizeof(T) == sizeof(zdouble))
+        X[i * ldx + j] = T(re, nsp_probe_value(seed, (uint64_t)(kNspMaxHost * (n + i) + j) + 1));
+      else
+        X[i * ldx + j] = T(re);
+    }
+}
+
+template <class T>
+bool nsp_gram_finite(const T *G, int64_t ldg) {
+  for (int64_t j = 0; j < kNspMaxHost; ++j)
+    for (int64_t c = 0; c < kNspMaxHost; ++c)
+      if (!std::isfinite(abs1_(G[j * ldg + c]))) return false;
+  return true;
+}
+
+// Rotation + scaling: G = E diag(w) E^H (herm_eig), eigenvalues DESCENDING into w[16], M = E diag(w)^{-1/2} in that
+// order, so that the columns of V M are orthonormal up to the rounding of G and ordered by their weight in V.  Kept: the
+// leading eigenvalues that are positive and finite with a finite 1 / sqrt(w).  A non-finite G keeps nothing.
+template <class T>
+int nsp_find_rotation(const T *G, int64_t ldg, T *M, double *w) {
+  const int64_t K = kNspMaxHost;
+  std::fill(M, M + K * K, T(0));
+  std::fill(w, w + K, 0.0);
+  if (!nsp_gram_finite(G, ldg)) return 0;
+  std::vector<T> A((size_t)(K * K), T(0));
+  for (int64_t j = 0; j < K; ++j)
+    for (int64_t c = 0; c <= j; ++c) A[(size_t)(j + c * K)] = G[j * ldg + c];  // lower triangle, column-major
+  std::vector<double> wa;
+  herm_eig<T>(K, A, wa);  // ascending
+  int kept = 0;
+  for (int64_t c = 0; c < K; ++c) w[c] = wa[(size_t)(K - 1 - c)];
+  for (int64_t c = 0; c < K; ++c) {
+    const double s = 1.0 / std::sqrt(w[c]);
+    if (!(w[c] > 0.0) || !std::isfinite(w[c]) || !std::isfinite(s)) break;
+    for (int64_t j = 0; j < K; ++j) M[j * K + c] = A[(size_t)(j + (K - 1 - c) * K)] * s;
+    ++kept;
+  }
+  return kept;
+}
+
+// Order-preserving orthonormalization: G = R^H R (Cholesky, R upper triangular with a positive diagonal), M = R^{-1},
+// so that column c of V M is a combination of the columns 0 .. c of V only.  Kept: the leading columns whose pivot
+// G_cc - sum_k |R_kc|^2 is positive and finite.
+template <class T>
+int nsp_chol_inverse(const T *G, int64_t ldg, T *M) {
+  const int64_t K = kNspMaxHost;
+  std::fill(M, M + K * K, T(0));
+  if (!nsp_gram_finite(G, ldg)) return 0;
+  auto g = [&](int64_t j, int64_t c) { return c <= j ? G[j * ldg + c] : conj_(G[c * ldg + j]); };  // v_j^H v_c
+  std::vector<T> R((size_t)(K * K), T(0));  // R[k * K + c], k <= c
+  int64_t m = 0;
+  for (; m < K; ++m) {
+    for (int64_t k = 0; k < m; ++k) {  // column m of R above the diagonal: R^H R = G read at (k, m)
+      T s = g(k, m);
+      for (int64_t l = 0; l < k; ++l) s -= conj_(R[(size_t)(l * K + k)]) * R[(size_t)(l * K + m)];
+      R[(size_t)(k * K + m)] = s / real_(R[(size_t)(k * K + k)]);
+    }
+    double piv = real_(g(m, m));
+    for (int64_t k = 0; k < m; ++k) piv -= real_(conj_(R[(size_t)(k * K + m)]) * R[(size_t)(k * K + m)]);
+    if (!(piv > 0.0) || !std::isfinite(piv) || !std::isfinite(1.0 / std::sqrt(piv))) break;
+    R[(size_t)(m * K + m)] = T(std::sqrt(piv));
+  }
+  // M = R^{-1} of the leading m x m block, column by column (back substitution)
+  for (int64_t c = 0; c < m; ++c) {
+    M[c * K + c] = T(1.0 / real_(R[(size_t)(c * K + c)]));
+    for (int64_t j = c - 1; j >= 0; --j) {
+      T s = T(0);
+      for (int64_t l = j + 1; l <= c; ++l) s -= R[(size_t)(j * K + l)] * M[l * K + c];
+      M[j * K + c] = s / real_(R[(size_t)(j * K + j)]);
+    }
+  }
+  return (int)m;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Invariants of everything the kernels index with.  hifamd_finalize runs this right before the upload: a hierarchy
 // whose converted arrays are not what the conversion must have produced (whatever the cause) is refused with
 // HIFAMD_HIFIR_ERROR instead of being applied -- a wrong row pointer on the device is a hang or a wrong answer.

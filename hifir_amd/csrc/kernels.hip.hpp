@@ -29,6 +29,7 @@
 //   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
+//   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -2369,6 +2370,63 @@ __global__ void __launch_bounds__(256) k_nsp_sub(int64_t n, int nc, T *__restric
     *p3 = vsub(x3, nsp_row_dot<T, K>(Q + (i + 3 * stride) * K, cj));
   }
   for (; i < n; i += stride) x[i * ldx + c] = vsub(x[i * ldx + c], nsp_row_dot<T, K>(Q + i * K, cj));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Null-space search (Engine::nsp_find): the probe block and the 16 x 16 right-multiplication of an [n][16] block.
+// The Gram matrix V^H V is k_nsp_coef<T, 16> + k_nsp_finish with Q = X = V (the fixed-order reduction above).
+// ---------------------------------------------------------------------------------------------
+// The counter-based probe generator that include/hifir_amd.h defines (import.hpp nsp_probe_value is its host twin):
+// z = seed + 0x9E3779B97F4A7C15 * counter (mod 2^64), the splitmix64 finalizer, u = (z >> 11) 2^-53, value 2u - 1.
+__device__ __forceinline__ double probe_value(uint64_t seed, uint64_t counter) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * counter;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return 2.0 * ((double)(z >> 11) * 0x1.0p-53) - 1.0;  // (both steps exact or correctly rounded: no contraction issue)
+}
+
+// X [n][16] contiguous: entry (i, j) from counter 16 i + j + 1, the imaginary part of a complex entry from
+// counter 16 (n + i) + j + 1.  One pass, consecutive lanes write consecutive entries.
+template <class T>
+__global__ void __launch_bounds__(256) k_probe_fill(int64_t n, uint64_t seed, T *__restrict__ x) {
+  const int64_t total = n * kNspMax;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (std::is_same<T, cplx>::value)
+      x[e] = cplx{probe_value(seed, (uint64_t)e + 1), probe_value(seed, (uint64_t)(total + e) + 1)};
+    else
+      x[e] = probe_value(seed, (uint64_t)e + 1);
+  }
+}
+
+// V <- V C in place, V [n][16] contiguous, C [16][16] row-major (v_new[i][c] = sum_j v[i][j] C[j][c], j ascending).
+// One row per 16 lanes: a wave moves four rows (512 B real, 1 KB complex) per access, lane c of a group keeps column c
+// of C in registers for the whole kernel (read once, 32 / 64 VGPRs) and gets the 16 values of its row from the other
+// lanes of its group by shuffles, so every entry of V is loaded once and stored once: HBM-bound, 256 FMA per row.
+// Every wave runs the same number of trips with all lanes alive (rows beyond n are loaded as zero and not stored).
+template <class T>
+__global__ void __launch_bounds__(256) k_blk_rmul(int64_t n, T *__restrict__ v, const T *__restrict__ C) {
+  const int c = threadIdx.x & 15;
+  T cc[kNspMax];
+#pragma unroll
+  for (int j = 0; j < kNspMax; ++j) cc[j] = C[j * kNspMax + c];
+  const int64_t step = (int64_t)gridDim.x * 16;
+  for (int64_t base = (int64_t)blockIdx.x * 16; base < n; base += step) {  // (uniform over the block)
+    const int64_t i = base + (threadIdx.x >> 4);
+    const bool live = i < n;
+    const T mine = live ? v[i * kNspMax + c] : vzero(T());
+    T acc = vzero(T());
+#pragma unroll
+    for (int j = 0; j < kNspMax; ++j) {
+      T vj;
+      if constexpr (std::is_same<T, cplx>::value)
+        vj = cplx{__shfl(mine.x, j, 16), __shfl(mine.y, j, 16)};
+      else
+        vj = __shfl(mine, j, 16);
+      acc = vadd(acc, vmul(vj, cc[j]));
+    }
+    if (live) v[i * kNspMax + c] = acc;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -386,6 +386,45 @@ class HIF:
         """Vectors of the basis filter in force (0: none, or constant mode)."""
         return int(lib().hifamd_nsp_dim(self._h, OP_SH if trans else OP_S))
 
+    def find_nullspace(self, kmax=16, tol=1e-7, rtol=1e-10, restart=30, maxit=500, trans=False, install=True, X0=None,
+                       seed=0, full_rank=False):
+        """Find the null space of the attached matrix (trans: of A^H) on the device (hifamd_nsp_find): 16 probe columns
+        x0, GMRES on A d = -A x0 to rtol, V = X0 + D ordered and orthonormalized, a column q accepted when
+        ||A q||_2 <= tol ||A||_inf; `found` = the leading accepted columns, at most kmax.  rtol sqrt(n / nullity) has to
+        stay below tol, and tol below sigma_min+(A) / ||A||_inf.  X0: (n, 16) host probes of the handle's dtype; None:
+        generated on the device from `seed` (the generator of include/hifir_amd.h).  install: the found vectors become
+        the basis filter (as set_nsp_basis would set them); nothing found leaves the filter in force as it was.
+        Returns (Q (n, found), resid (16,) = ||A q_j|| / ||A||_inf per column, inf for a dropped one, info) with info =
+        {"unconverged": probe columns whose GMRES did not converge, "iters": largest GMRES iteration count,
+        "maybe_more": a column beyond kmax passed too, or found == 16, "nonfinite": something non-finite was met}."""
+        n = self.nrows()
+        kmax = int(kmax)
+        if X0 is not None:
+            if not isinstance(X0, np.ndarray) or X0.ndim != 2 or X0.shape != (n, 16):
+                raise HifAmdError(2, "X0: expected an (n, 16) block of probe columns")
+            X0 = np.ascontiguousarray(X0, dtype=self.dtype)
+        Q = np.zeros((n, min(max(kmax, 1), 16)), dtype=self.dtype)
+        resid = np.zeros(16)
+        info = np.zeros(4, dtype=np.int32)
+        found = C.c_int64(0)
+        _check(lib().hifamd_nsp_find(self._h, OP_SH if trans else OP_S, kmax, float(tol), float(rtol), int(restart),
+                                     int(maxit), -1 if full_rank else 0, _p(X0), 16, int(seed) & (2 ** 64 - 1),
+                                     1 if install else 0, C.byref(found), _p(Q), Q.shape[1], _p(resid), _p(info)))
+        keys = ("unconverged", "iters", "maybe_more", "nonfinite")
+        return np.ascontiguousarray(Q[:, :found.value]), resid, {k: int(info[i]) for i, k in enumerate(keys)}
+
+    def nsp_basis(self, trans=False):
+        """The orthonormal basis of the basis filter in force, (n, k) (hifamd_nsp_get_basis); None when there is none
+        (or the filter is in constant mode)."""
+        op = OP_SH if trans else OP_S
+        k = self.nsp_dim(trans)
+        if k <= 0:
+            return None
+        Q = np.empty((self.nrows(), k), dtype=self.dtype)
+        if lib().hifamd_nsp_get_basis(self._h, op, _p(Q), k) != k:
+            _check(4)
+        return Q
+
     def nsp_filter(self, X, trans=False):
         """The filter in force (basis or constant mode) alone, in place, on X ((n,) or (n, nrhs); a C-contiguous host
         array of the handle's dtype, or a CUDA tensor, which is not synchronized); returns X.  No filter: X as it is."""

@@ -236,6 +236,45 @@ int64_t hifamd_nsp_dim(HifAmdHdl h, HifAmdOp op);
  * hifamd_apply_batch_dev. */
 HifAmdStatus hifamd_nsp_filter_batch(HifAmdHdl h, HifAmdOp op, void *X, int64_t ldx, int64_t nrhs);
 HifAmdStatus hifamd_nsp_filter_batch_dev(HifAmdHdl h, HifAmdOp op, void *dX, int64_t ldx, int64_t nrhs, void *stream);
+/* FIND the null space of a singular system on the device, for the caller who knows THAT A is singular, not what its
+ * null space is.  op = HIFAMD_S: null(A); op = HIFAMD_SH: null(A^H) (runs on the adjoint engine, built on first use).
+ * Method: for a block X0 of always HIFAMD_NSP_MAX = 16 probe columns (a 16-column batch costs what one column costs,
+ * and the spare columns tell "nullity = kmax" from "more than kmax"), B = -A X0 lies in range(A), so A D = B is
+ * consistent; D = hifamd_gmres_batch_dev on the 16 columns (x0 = 0, restart, rtol, maxit, rank as there); V = X0 + D
+ * has ||A v_j|| <= rtol ||A x0_j|| and numerical rank = nullity.  V is ordered and orthonormalized through 16 x 16
+ * matrices: G = V^H V (fixed-order device reduction), Hermitian eigendecomposition on the host, eigenvalues descending,
+ * V <- V E diag(w)^{-1/2}; then twice the order-preserving step G = V^H V = R^H R (Cholesky), V <- V R^{-1}.  A column
+ * whose eigenvalue or Cholesky pivot is not positive and finite is dropped with every column behind it (not an error: a
+ * nonsingular A with a near-exact M gives V ~ 0).  Accepted by the definition, not by the spectrum: q_j is a numerical
+ * null vector when res_j = ||A q_j||_2 <= tol ||A||_inf (||A||_inf the largest row sum of |a_ij|, of A^H for
+ * HIFAMD_SH); *found = length of the LEADING PREFIX of accepted columns, at most kmax.
+ * How rtol and tol relate: for a random probe ||v|| ~ ||x0|| sqrt(k / n) (k the nullity), so the null columns reach
+ * res / ||A|| <~ rtol sqrt(n / k), while every unit column orthogonal to the null space has res >= sigma_min+(A), the
+ * smallest nonzero singular value: tol has to lie between the two (e.g. rtol = 1e-10, tol = 1e-7 up to 1M rows).  A
+ * matrix with sigma_min+ < tol ||A||_inf has, by this definition, a larger numerical null space.
+ * X0 != NULL: host [n][16] probes of the handle's value type, row stride ldx0 >= 16.  X0 == NULL: generated on the
+ * device from `seed` by a counter-based generator: entry (i, j) is f(16 i + j + 1), the imaginary part of a complex
+ * entry f(16 (n + i) + j + 1), where f(c): z = seed + 0x9E3779B97F4A7C15 c (mod 2^64); z = (z ^ (z >> 30))
+ * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) 0x94D049BB133111EB; z = z ^ (z >> 31) (the splitmix64 finalizer);
+ * u = (z >> 11) 2^-53; f = 2 u - 1.
+ * The filter in force on op (basis or constant) is suspended for the duration of the search and restored on every
+ * exit, error exits included.  install != 0 and *found > 0: the first *found columns become the basis filter of op
+ * (as hifamd_set_nsp_basis would set them, without a host round trip; a constant-mode filter on op is replaced);
+ * *found == 0 leaves the filter in force as it was.  Q (host, may be NULL, row stride ldq >= kmax) receives the
+ * *found columns [n][*found]; resid16 (may be NULL) the 16 values res_j / ||A||_inf in column order, +infinity for a
+ * dropped column; info4 (may be NULL) = {probe columns whose GMRES did not converge, largest GMRES iteration count,
+ * 1 if a column beyond kmax also passed or *found == 16 ("there may be more"), 1 if anything non-finite was met (then
+ * *found = 0)}.  Same inputs, same bits.  Needs hifamd_set_matrix; the 16-column batch passes the
+ * width check of hifamd_gmres_batch.
+ * Refusals, in this order: NULL handle HIFAMD_NULL_OBJ; op not HIFAMD_S / HIFAMD_SH, kmax < 1, kmax > 16, tol <= 0,
+ * rtol <= 0, restart < 1, maxit < 1, X0 given with ldx0 < 16, Q given with ldq < kmax, found NULL
+ * HIFAMD_MISMATCHED_SIZES; handle not finalized or no matrix HIFAMD_BAD_PREC. */
+HifAmdStatus hifamd_nsp_find(HifAmdHdl h, HifAmdOp op, int64_t kmax, double tol, double rtol, int restart, int maxit,
+                             int64_t rank, const void *X0, int64_t ldx0, uint64_t seed, int install, int64_t *found, void *Q,
+                             int64_t ldq, double *resid16, int *info4);
+/* the orthonormal basis in force on op, [n][k] into Q (host, row stride ldq >= k); returns k, 0 when there is none or
+ * the filter is in constant mode, -1 for a NULL handle, a NULL Q or ldq too small */
+int64_t hifamd_nsp_get_basis(HifAmdHdl h, HifAmdOp op, void *Q, int64_t ldq);
 
 /* ---- lhf?Apply with an operator tag (libhifir.h:685, libhifir.cpp:447-472), batched ----------- */
 /* op = HIFAMD_S / HIFAMD_SH: nirs <= 1 direct apply (ir_status, if given, gets {1, -1} per column);

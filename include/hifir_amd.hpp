@@ -162,6 +162,39 @@ class HIF {
     const std::int64_t k = _h ? hifamd_nsp_dim(_h, trans ? HIFAMD_SH : HIFAMD_S) : 0;
     return k > 0 ? (size_type)k : 0u;
   }
+  /// Find the null space of the attached matrix (trans: of A^H) on the device (hifamd_nsp_find, device-generated
+  /// probes of `seed`): returns the number of vectors found (at most kmax); Q receives them one after the other
+  /// (found * nrows() entries, the layout set_nsp_basis takes); resid16 / info4 as in hifir_amd.h (may be null).
+  /// install: they become the basis filter.
+  size_type find_nullspace(std::vector<value_type> &Q, const size_type kmax = HIFAMD_NSP_MAX, const double tol = 1e-7,
+                           const double rtol = 1e-10, const int restart = 30, const int maxit = 500, const bool trans = false,
+                           const bool install = true, const std::uint64_t seed = 0u, const bool full_rank = false,
+                           double *resid16 = nullptr, int *info4 = nullptr) {
+    require();
+    const size_type n = nrows(), kq = kmax ? kmax : 1u;
+    std::vector<value_type> W(n * kq);  // [n][kmax] row-interleaved, the layout of the C ABI
+    std::int64_t found = 0;
+    detail::check(hifamd_nsp_find(_h, trans ? HIFAMD_SH : HIFAMD_S, (std::int64_t)kmax, tol, rtol, restart, maxit,
+                                  full_rank ? -1 : 0, nullptr, 0, seed, install ? 1 : 0, &found, W.data(), (std::int64_t)kq,
+                                  resid16, info4));
+    Q.assign((size_type)found * n, value_type(0));
+    for (size_type j = 0; j < (size_type)found; ++j)
+      for (size_type i = 0; i < n; ++i) Q[j * n + i] = W[i * kq + j];
+    return (size_type)found;
+  }
+  /// the orthonormal basis of the basis filter in force, nsp_dim(trans) vectors one after the other (empty: none)
+  std::vector<value_type> nsp_basis(const bool trans = false) const {
+    require();
+    const size_type n = nrows(), k = nsp_dim(trans);
+    std::vector<value_type> Q(k * n);
+    if (!k) return Q;
+    std::vector<value_type> W(k * n);
+    if (hifamd_nsp_get_basis(_h, trans ? HIFAMD_SH : HIFAMD_S, W.data(), (std::int64_t)k) != (std::int64_t)k)
+      throw std::runtime_error("hifir_amd: the null-space basis could not be read back");
+    for (size_type j = 0; j < k; ++j)
+      for (size_type i = 0; i < n; ++i) Q[j * n + i] = W[i * k + j];
+    return Q;
+  }
   /// the filter in force alone, in place, on one vector (what makes a right-hand side consistent)
   template <class Array>
   void nsp_filter(Array &x, const bool trans = false) const {
