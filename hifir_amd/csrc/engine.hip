@@ -158,6 +158,13 @@ struct DevCsr {
   DevBuf us_desc, us_rowid, us_oslot, us_mptr, us_mcol, us_mval, us_own_val, us_own_src, us_own_rptr, us_own_lvl;
   std::vector<uint8_t> us_band_ok;
   std::vector<int32_t> us_band_nbk, us_band_own, us_band_c0;
+  // L triangles of sparse-own plans: dependent rows in LDS, sources streamed through a chunk (host.hpp build_ls_plan; kernel k_band_ls)
+  DevBuf ls_desc, ls_rowid, ls_oslot, ls_own_val, ls_own_src, ls_own_rptr, ls_own_lvl;
+  DevBuf ls_ebase[2], ls_ewptr[2], ls_ecol[2], ls_eval[2], ls_etag[2];  // outside entries: [0] plain, [1] with the level's F entries
+  bool ls_fused = false;
+  std::vector<uint8_t> ls_band_ok;
+  std::vector<int32_t> ls_band_nd, ls_band_own, ls_band_rptr, ls_band_c0, ls_band_cw, ls_band_nch;
+  int64_t ls_sources = 0, ls_deps = 0, ls_chunk_rows = 0;
   DevBuf ct_desc, ct_sptr, ct_src, ct_coef;
   bool ct_on = false;
   int64_t ct_tiles = 0;
@@ -210,6 +217,15 @@ struct DevCsr {
     us_mval.alias(o.us_mval), us_own_val.alias(o.us_own_val), us_own_src.alias(o.us_own_src), us_own_rptr.alias(o.us_own_rptr);
     us_own_lvl.alias(o.us_own_lvl);
     us_band_ok = o.us_band_ok, us_band_nbk = o.us_band_nbk, us_band_own = o.us_band_own, us_band_c0 = o.us_band_c0;
+    ls_desc.alias(o.ls_desc), ls_rowid.alias(o.ls_rowid), ls_oslot.alias(o.ls_oslot), ls_own_val.alias(o.ls_own_val);
+    ls_own_src.alias(o.ls_own_src), ls_own_rptr.alias(o.ls_own_rptr), ls_own_lvl.alias(o.ls_own_lvl);
+    for (int f = 0; f < 2; ++f)
+      ls_ebase[f].alias(o.ls_ebase[f]), ls_ewptr[f].alias(o.ls_ewptr[f]), ls_ecol[f].alias(o.ls_ecol[f]), ls_eval[f].alias(o.ls_eval[f]),
+          ls_etag[f].alias(o.ls_etag[f]);
+    ls_fused = o.ls_fused;
+    ls_band_ok = o.ls_band_ok, ls_band_nd = o.ls_band_nd, ls_band_own = o.ls_band_own, ls_band_rptr = o.ls_band_rptr;
+    ls_band_c0 = o.ls_band_c0, ls_band_cw = o.ls_band_cw, ls_band_nch = o.ls_band_nch;
+    ls_sources = o.ls_sources, ls_deps = o.ls_deps, ls_chunk_rows = o.ls_chunk_rows;
     ct_desc.alias(o.ct_desc);
     ct_sptr.alias(o.ct_sptr);
     ct_src.alias(o.ct_src);
@@ -465,6 +481,8 @@ class Engine : public EngineBase {
   int ct_wide_wgs = 128; // HIFIR_AMD_CT_WIDE: a component band with more workgroups than this takes two column tiles per workgroup
   int ct_wide4_wgs = 1 << 30;  // HIFIR_AMD_CT_WIDE4: ... and with more than this all four (one workgroup per component)
   int us_mode = 1;  // HIFIR_AMD_US=0: sparse-own U bands keep every row of a component in LDS (k_band_cd)
+  int ls_mode = 1;  // HIFIR_AMD_LS=0: sparse-own L bands keep every row of a component in LDS (k_band_cd; the same bits)
+  int ls_chunk = 0;  // HIFIR_AMD_LS_CHUNK=32/48/64: rows of k_band_ls's source chunk (0: the largest that fits 80 KB of LDS)
   int narrow_tiles = 1;  // HIFIR_AMD_NARROW_TILES=0: the tiled Schur products always multiply all four column tiles
   int skip_rows = 3;  // HIFIR_AMD_SKIP_ROWS: bit 0 L rows / bit 1 U rows a level's first solve does not store (build_row_flags); 0: every row
   int ct_mode_real = 1;  // HIFIR_AMD_CT_REAL=0: real handles keep the entry walk while HIFIR_AMD_CT_Z stays as set (tests)
@@ -535,6 +553,8 @@ class Engine : public EngineBase {
     skip_rows = env_int("HIFIR_AMD_SKIP_ROWS", 3);
     narrow_tiles = env_int("HIFIR_AMD_NARROW_TILES", 1);
     us_mode = env_int("HIFIR_AMD_US", 1);
+    ls_mode = env_int("HIFIR_AMD_LS", 1);
+    ls_chunk = env_int("HIFIR_AMD_LS_CHUNK", 0);
     top_last_arriver = env_int("HIFIR_AMD_TOP_LAST", 0);
     list_early = env_int("HIFIR_AMD_LIST_EARLY", 0);
     spmm_rb = env_int("HIFIR_AMD_SPMM_RB", 1) == 2 ? 2 : 1;
@@ -602,6 +622,9 @@ class Engine : public EngineBase {
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_us, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      for (int cw = 2; cw <= 4; ++cw)
+        for (int nch = 2; nch <= ls_max_chunks(cw); ++nch)
+          HIP_OK(hipFuncSetAttribute(ls_kernel(cw, nch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLsLdsMax));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cd_lds_bytes(true), 160 * 1024)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cd_lds_bytes(true), 160 * 1024)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cs<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cs_lds_bytes(true), 160 * 1024)));
@@ -734,6 +757,8 @@ class Engine : public EngineBase {
       E->skip_rows = skip_rows;
       E->narrow_tiles = narrow_tiles;
       E->us_mode = us_mode;
+      E->ls_mode = ls_mode;
+      E->ls_chunk = ls_chunk;
       E->list_early = list_early;
       E->spmm_rb = spmm_rb;
       E->spmm_tiles_z = spmm_tiles_z;
@@ -807,6 +832,8 @@ class Engine : public EngineBase {
       E->skip_rows = skip_rows;
       E->narrow_tiles = narrow_tiles;
       E->us_mode = us_mode;
+      E->ls_mode = ls_mode;
+      E->ls_chunk = ls_chunk;
       E->list_early = list_early;
       E->spmm_rb = spmm_rb;
       E->spmm_tiles_z = spmm_tiles_z;
@@ -1157,6 +1184,11 @@ class Engine : public EngineBase {
       L.n = H.n;
       L.F_ncols = H.F_ncols;
       L.E_void = H.E_void;
+      // sparse-own L bands: the one per-row order of the own entries that k_band_ls, k_band_cd and k_band_cs share (host.hpp
+      // ls_reorder_own) -- before the lists are shipped, whatever HIFIR_AMD_LS says and whatever analyzed the level
+      if constexpr (std::is_same<T, double>::value) {
+        if (band_opt.dense_block > 0 && H.Lp.cd_sparse) ls_reorder_own(H.Lp);
+      }
       ship_block_inverses(H.Lp, H.Lr, H.Ltinv_elems, L.L);
       ship_block_inverses(H.Up, H.Ur, H.Utinv_elems, L.U);
       tick("triangles + block inverses", fl_);
@@ -1241,6 +1273,29 @@ class Engine : public EngineBase {
             M.us_mcol.upload(Up2.mcol, 8), M.us_mval.upload(Up2.mval, 8), M.us_own_val.upload(Up2.own_val, 8);
             M.us_own_src.upload(Up2.own_src, 8), M.us_own_rptr.upload(Up2.own_rptr, 8), M.us_own_lvl.upload(Up2.own_lvl, 8);
             M.us_band_ok = Up2.band_ok, M.us_band_nbk = Up2.band_nbk, M.us_band_own = Up2.band_own, M.us_band_c0 = Up2.band_c0;
+          }
+        }
+      }
+      if constexpr (std::is_same<T, double>::value) {
+        if (ls_mode && band_opt.dense_block > 0 && L.L.cd_sparse && Rmax == 64) {
+          LsPlan<T> Lp2;
+          build_ls_plan(H.Lp, H.Lr, L.L.f_fused ? &H.Fr : nullptr, H.n + H.m, ls_chunk, Lp2);
+          if (Lp2.any) check_ls_plan(H.Lp, H.Lr, Lp2, 2 * H.n);  // (the arena: w, v behind it)
+          if (Lp2.any) {
+            DevCsr &M = L.L;
+            M.ls_desc.upload(Lp2.desc, 8), M.ls_rowid.upload(Lp2.rowid, 8), M.ls_oslot.upload(Lp2.oslot, 8);
+            M.ls_own_val.upload(Lp2.own_val, 8), M.ls_own_src.upload(Lp2.own_src, 8), M.ls_own_rptr.upload(Lp2.own_rptr, 8);
+            M.ls_own_lvl.upload(Lp2.own_lvl, 8);
+            for (int f = 0; f < 2; ++f) {
+              const LsStream<T> &E = f ? Lp2.fused : Lp2.plain;
+              if (!E.on) continue;
+              M.ls_ebase[f].upload(E.base, 8), M.ls_ewptr[f].upload(E.wptr, 8);
+              M.ls_ecol[f].upload(E.col, 80), M.ls_eval[f].upload(E.val, 80), M.ls_etag[f].upload(E.tag, 80);
+            }
+            M.ls_fused = Lp2.fused.on;
+            M.ls_band_ok = Lp2.band_ok, M.ls_band_nd = Lp2.band_nd, M.ls_band_own = Lp2.band_own, M.ls_band_rptr = Lp2.band_rptr;
+            M.ls_band_c0 = Lp2.band_c0, M.ls_band_cw = Lp2.band_cw, M.ls_band_nch = Lp2.band_nch;
+            M.ls_sources = Lp2.sources, M.ls_deps = Lp2.deps, M.ls_chunk_rows = Lp2.chunk_rows;
           }
         }
       }
@@ -1758,6 +1813,16 @@ class Engine : public EngineBase {
     const int nslz = std::min(4, (act_cols + 15) / 16);
     return L.U.cd_sparse || (ct_mode && L.U.ct_on) || (cs_mode && nslz < 4);
   }
+  // the instances of k_band_ls: CW = chunk rows / 16, NCH = chunks whose rows a wave holds in registers (CW * NCH <= kLsMaxSlots)
+  static const void *ls_kernel(int cw, int nch) {
+    typedef void (*K)(int32_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *, const uint16_t *, const int32_t *,
+                      const double *, const uint8_t *, const double *, const uint8_t *, const uint16_t *, const uint8_t *, double *, int32_t,
+                      int32_t, int32_t, FirstL<double>, RowSkip);
+    static const K tab[3][3] = {{k_band_ls<2, 2>, k_band_ls<2, 3>, k_band_ls<2, 4>},
+                                {k_band_ls<3, 2>, k_band_ls<3, 3>, nullptr},
+                                {k_band_ls<4, 2>, nullptr, nullptr}};
+    return (cw < 2 || cw > 4 || nch < 2 || nch > 4) ? nullptr : (const void *)tab[cw - 2][nch - 2];
+  }
   static size_t us_lds_bytes(int32_t lds_black, int32_t own_cap) {  // k_band_us: black rows, own values, S7 scales, row ids, S7 rows, offsets, sources, levels
     return (size_t)lds_black * 64 * sizeof(double) + (size_t)own_cap * sizeof(double) + 256 * sizeof(double) + 2 * 256 * sizeof(int32_t) +
            260 * sizeof(uint16_t) + (size_t)own_cap + 264;
@@ -1810,6 +1875,30 @@ class Engine : public EngineBase {
                              M.us_mval.as<double>(), M.us_own_val.as<double>(), M.us_own_src.as<uint8_t>(), M.us_own_rptr.as<uint16_t>(),
                              M.us_own_lvl.as<uint8_t>(), L.d.as<double>(), (const double *)L.w.as<double>(), L.v.as<double>(), lds_black,
                              own_cap2, fl, lu, M.cd_sparse ? rs : RowSkip{nullptr});
+          return;
+        }
+      }
+      if (LOWER && ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
+          (!with_f || M.ls_fused) && !cd_dbg && !no_walk && !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {
+        // dependent rows in LDS, sources through a chunk: two workgroups per unit
+        const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]), f = with_f ? 1 : 0;
+        const int32_t own_cap2 = std::max(64, (M.ls_band_own[band] + 63) & ~63), rptr_cap = (M.ls_band_rptr[band] + 3) & ~3;
+        const int32_t lds_dep = std::max(1, M.ls_band_nd[band]);
+        const size_t lds2 = ls_lds_bytes(lds_dep, 16 * cw, own_cap2, rptr_cap);
+        const void *kls = ls_kernel(cw, nch);
+        if (kls && lds2 <= kLsLdsMax) {
+          int32_t a_c0 = M.ls_band_c0[band], a_dep = lds_dep, a_own = own_cap2, a_rp = rptr_cap;
+          const int32_t *a_desc = M.ls_desc.as<int32_t>(), *a_rowid = M.ls_rowid.as<int32_t>(), *a_oslot = M.ls_oslot.as<int32_t>();
+          const int32_t *a_eb = M.ls_ebase[f].template as<int32_t>(), *a_ec = M.ls_ecol[f].template as<int32_t>();
+          const uint16_t *a_ew = M.ls_ewptr[f].template as<uint16_t>(), *a_or = M.ls_own_rptr.as<uint16_t>();
+          const double *a_ev = M.ls_eval[f].template as<double>(), *a_ov = M.ls_own_val.as<double>();
+          const uint8_t *a_et = M.ls_etag[f].template as<uint8_t>(), *a_os = M.ls_own_src.as<uint8_t>(), *a_ol = M.ls_own_lvl.as<uint8_t>();
+          double *a_w = L.w.as<double>();
+          FL a_fl = fl;
+          RowSkip a_rs = rs;
+          void *args[] = {&a_c0, &a_desc, &a_rowid, &a_oslot, &a_eb, &a_ew, &a_ec, &a_ev, &a_et, &a_ov, &a_os, &a_or, &a_ol, &a_w,
+                          &a_dep, &a_own, &a_rp, &a_fl, &a_rs};
+          HIP_OK(hipLaunchKernel(kls, dim3((unsigned)(g1 - g0)), dim3(1024), args, lds2, st));
           return;
         }
       }
@@ -3289,7 +3378,9 @@ class Engine : public EngineBase {
     // resident bytes of this handle beside the explicit operators: the work arena of every level (w + v, Rmax columns),
     // the coefficient tiles of the component bands, the factors with their plan arrays
     double arena = 0.0, tiles = 0.0, factors = 0.0, skip_w = 0.0, skip_v = 0.0;
+    double ls_src = 0.0, ls_dep = 0.0, ls_c = 0.0;  // k_band_ls: rows streamed, rows kept in LDS, the largest chunk (rows)
     for (const auto &L : lv) {
+      ls_src += (double)L->L.ls_sources, ls_dep += (double)L->L.ls_deps, ls_c = std::max(ls_c, (double)L->L.ls_chunk_rows);
       arena += (double)L->arena.bytes;
       skip_w += (double)L->skip_w;
       skip_v += (double)L->skip_v;
@@ -3304,7 +3395,7 @@ class Engine : public EngineBase {
                         (double)tail_level, tail_probe_err, tail_max_abs, (double)tail_rejected, tail_probe_tol, tail_max_growth,
                         (double)levels_from_cache, analysis_seconds, arena, (double)Rmax, tiles, factors, (double)max_nrhs,
                         skip_w, skip_v, (double)host_repairs,
-                        (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0))};
+                        (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0)), ls_src, ls_dep, ls_c};
     const int nv = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < cap && i < nv; ++i) o[i] = v[i];
     return nv;

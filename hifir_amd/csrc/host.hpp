@@ -1135,6 +1135,362 @@ void check_us_plan(const BandPlan &P, const Csr<T> &A, const UsPlan<T> &U) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Sparse-own L bands with streamed SOURCES (kernel k_band_ls).  Level 0 of a PDE hierarchy: two thirds of a component's rows
+// have no entry inside the component -- their L solve is "right-hand side minus outside entries", final before anything of
+// the component is solved -- and the other ("dependent") rows read them.  Only the dependent rows need an LDS slot for the
+// whole workgroup; the sources pass through ONE chunk buffer of C rows: a wave forms its source rows in registers, stores
+// them, deposits chunk after chunk, and behind a barrier every dependent row subtracts its entries into that chunk.  Then
+// the dependent rows are solved level by level in LDS as k_band_cd<true, sparse> does.  LDS per component: (dependent rows
+// + C) x 512 B (<= 80 KB on the reference's 1M-row hierarchy, against 103 KB) => two workgroups per compute unit.
+// Per row the arithmetic runs in ONE order, whichever kernel forms the row: right-hand side, outside entries (plan order,
+// the level's F entries behind them), own entries to sources by ascending source, own entries to dependent rows in plan
+// order.  ls_reorder_own puts a qualifying band's own lists (BandPlan::own_k / own_lsrc) into that order BEFORE they are
+// uploaded, so k_band_cd and k_band_cs (narrow batches, HIFIR_AMD_LS=0) walk what k_band_ls walks.
+// The component's rows are renumbered dependent rows first (relative order kept: dependency order), sources behind:
+//   desc   : per component 8 words: s0, nb, nd (dependent rows), own0, orp0, lvl0, nlvl, nch (chunks: ceil(sources / C))
+//   rowid  : per NEW slot the row id;  oslot: per new slot the plan's slot (row flags are kept in plan order)
+//   own_val / own_src / own_rptr : the dependent rows' own entries in nch + 1 SEGMENTS per component -- segment k < nch:
+//            entries into chunk k (own_src = source's index inside the chunk), segment nch: entries to dependent rows
+//            (own_src = new local index); own_rptr holds (nch + 1) * nd + 1 offsets relative to own0, segment-major
+//   own_lvl  : per component nlvl + 1 dependent-row boundaries
+// Wave w of the 16 owns the dependent rows w, w + 16, ... and the sources nd + w + 16 q (register slot q; chunk q / (C / 16)).
+// Outside entries (LsStream, one for the plain solve and one with the level's F entries appended): per component and wave
+// two packed runs (column = source ROW, value, tag): first the wave's dependent rows (tag = new local index), then its
+// sources (tag = register slot); wptr holds 33 offsets per component relative to base[component].
+// band_ok[b]: every workgroup of band b owns exactly one component (<= 255 rows), the band touches its rows first, and
+// (dependent rows, chunk, own entries) fit kLsLdsMax;  band_cw[b] = C / 16, band_nch[b] = most chunks of one component.
+// ---------------------------------------------------------------------------------------------
+constexpr int kLsDescWords = 8;
+constexpr size_t kLsLdsMax = 80 * 1024;  // two workgroups share a compute unit's 160 KB
+constexpr int kLsMaxSlots = 9;           // source rows one wave holds in registers (kernel: CW * NCH <= 9 keeps it within 64 VGPRs without scratch)
+inline int ls_max_chunks(int cw) { return std::min(4, kLsMaxSlots / cw); }
+inline size_t ls_lds_bytes(int32_t lds_dep, int32_t chunk_rows, int32_t own_cap, int32_t rptr_cap) {
+  // dependent rows, chunk, own values | dependent row ids | offsets | own sources | levels
+  return ((size_t)lds_dep + (size_t)chunk_rows) * 64 * sizeof(double) + (size_t)own_cap * sizeof(double) +
+         (size_t)((lds_dep + 1) & ~1) * sizeof(int32_t) + (size_t)rptr_cap * sizeof(uint16_t) + (size_t)own_cap + 264;
+}
+inline bool ls_band_qualifies(const BandPlan &P, int64_t b) {
+  if (!P.cd_sparse || P.band_cd.empty() || !P.band_cd[(size_t)b]) return false;
+  if (!P.band_dense.empty() && P.band_dense[(size_t)b]) return false;
+  if (!P.band_prefix.empty() && P.band_prefix[(size_t)b]) return false;
+  if (!P.band_fused.empty() && P.band_fused[(size_t)b]) return false;
+  const int32_t g0 = P.band_wg_ptr[(size_t)b], g1 = P.band_wg_ptr[(size_t)b + 1];
+  const int32_t c0 = P.wg_grp_ptr[(size_t)g0], c1 = P.wg_grp_ptr[(size_t)g1];
+  if (c1 - c0 != g1 - g0 || c1 <= c0) return false;  // (bags: the component kernel of the plan keeps them)
+  for (int32_t c = c0; c < c1; ++c)
+    if (P.grp_slot_ptr[(size_t)c + 1] - P.grp_slot_ptr[(size_t)c] > 255) return false;
+  return true;
+}
+
+// The one per-row order of the own entries (see above), applied in place to the own lists of every qualifying band of an
+// L plan: entries to sources (rows without own entries) first, by ascending local row; entries to dependent rows behind
+// them in the order they had.  Idempotent.  Returns the number of rows whose list changed.
+inline int64_t ls_reorder_own(BandPlan &P) {
+  int64_t changed = 0;
+  if (!P.cd_sparse || P.band_cd.empty() || P.cd_desc.empty()) return 0;
+  std::vector<std::pair<int32_t, uint8_t>> src, dep;
+  for (int64_t b = 0; b < P.nbands(); ++b) {
+    if (!ls_band_qualifies(P, b)) continue;
+    const int32_t c0 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b]], c1 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b + 1]];
+    for (int32_t c = c0; c < c1; ++c) {
+      const int32_t *dsc = &P.cd_desc[(size_t)c * kCdDescWords];
+      const int32_t nb = dsc[1], own0 = dsc[20], orp0 = dsc[22];
+      const uint16_t *rp = &P.own_rptr[(size_t)orp0];
+      for (int32_t r = 0; r < nb; ++r) {
+        const int32_t eb = own0 + rp[r], ee = own0 + rp[r + 1];
+        if (ee - eb < 2) continue;
+        src.clear(), dep.clear();
+        for (int32_t e = eb; e < ee; ++e) {
+          const uint8_t q = P.own_lsrc[(size_t)e];
+          (rp[q + 1] > rp[q] ? dep : src).push_back({P.own_k[(size_t)e], q});
+        }
+        std::stable_sort(src.begin(), src.end(), [](const std::pair<int32_t, uint8_t> &x, const std::pair<int32_t, uint8_t> &y) { return x.second < y.second; });
+        src.insert(src.end(), dep.begin(), dep.end());
+        bool diff = false;
+        for (int32_t e = eb; e < ee; ++e) {
+          diff = diff || P.own_k[(size_t)e] != src[(size_t)(e - eb)].first;
+          P.own_k[(size_t)e] = src[(size_t)(e - eb)].first, P.own_lsrc[(size_t)e] = src[(size_t)(e - eb)].second;
+        }
+        changed += diff;
+      }
+    }
+  }
+  return changed;
+}
+
+template <class T>
+struct LsStream {
+  std::vector<int32_t> base, col;  // per component the first entry; per entry the source row
+  std::vector<T> val;
+  std::vector<uint8_t> tag;
+  std::vector<uint16_t> wptr;  // per component 33 offsets: wave w's dependent run [2w, 2w+1), its source run [2w+1, 2w+2)
+  bool on = false;
+};
+template <class T>
+struct LsPlan {
+  std::vector<int32_t> desc, rowid, oslot;
+  std::vector<T> own_val;
+  std::vector<uint8_t> own_src, own_lvl;
+  std::vector<uint16_t> own_rptr;
+  LsStream<T> plain, fused;
+  std::vector<uint8_t> band_ok;
+  std::vector<int32_t> band_nd, band_own, band_rptr, band_c0, band_cw, band_nch;
+  int64_t sources = 0, deps = 0, chunk_rows = 0;  // rows streamed / rows kept in LDS over the qualifying bands; largest C
+  bool any = false;
+};
+
+// Lr: the triangle in slot order; P: its plan AFTER ls_reorder_own; Fr / src_row0: the level's F rows for the fused second
+// solve (build_cd_streams_fused), or nullptr; chunk_req: rows per chunk (a multiple of 16), 0 = the largest that fits
+template <class T>
+void build_ls_plan(const BandPlan &P, const Csr<T> &A /* slot order */, const Csr<T> *Fr, int64_t src_row0, int chunk_req, LsPlan<T> &S) {
+  S = LsPlan<T>();
+  const int64_t nb_bands = P.nbands();
+  if (!P.cd_sparse || P.band_cd.empty() || nb_bands <= 0 || P.cd_desc.empty()) return;
+  const int64_t m = A.nrows;
+  const size_t ngrp = P.grp_slot_ptr.size() - 1;
+  S.desc.assign(ngrp * (size_t)kLsDescWords, 0);
+  S.rowid.assign((size_t)m, 0);
+  S.oslot.assign((size_t)m, 0);
+  for (auto *v : {&S.band_nd, &S.band_own, &S.band_rptr, &S.band_c0, &S.band_cw, &S.band_nch}) v->assign((size_t)nb_bands, 0);
+  S.band_ok.assign((size_t)nb_bands, 0);
+  S.plain.base.assign(ngrp, 0), S.plain.wptr.assign(ngrp * 33, 0);
+  const bool with_f = Fr != nullptr && src_row0 + Fr->ncols <= (int64_t)std::numeric_limits<int32_t>::max() / 64;
+  if (with_f) S.fused.base.assign(ngrp, 0), S.fused.wptr.assign(ngrp * 33, 0);
+  std::vector<int32_t> newpos((size_t)m);
+  for (int64_t sl = 0; sl < m; ++sl) newpos[(size_t)sl] = (int32_t)sl;
+  auto is_dep = [&](int32_t sl) { return A.ptr[(size_t)sl + 1] > P.csplit[(size_t)sl]; };
+  // pass 1: the new order of every candidate component, the band's maxima, its chunk size
+  for (int64_t b = 0; b < nb_bands; ++b) {
+    if (!ls_band_qualifies(P, b)) continue;
+    const int32_t c0 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b]], c1 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b + 1]];
+    int32_t nd_max = 0, ns_max = 0, own_max = 0;
+    for (int32_t c = c0; c < c1; ++c) {
+      const int32_t s0 = P.grp_slot_ptr[(size_t)c], nb = P.grp_slot_ptr[(size_t)c + 1] - s0;
+      int32_t nd = 0, own = 0;
+      for (int32_t r = 0; r < nb; ++r) nd += is_dep(s0 + r), own += A.ptr[(size_t)(s0 + r) + 1] - P.csplit[(size_t)(s0 + r)];
+      nd_max = std::max(nd_max, nd), ns_max = std::max(ns_max, nb - nd), own_max = std::max(own_max, own);
+    }
+    if (own_max > 65535) continue;  // (uint16 offsets)
+    const int32_t own_cap = std::max(64, (own_max + 63) & ~63);
+    int cw = 0;
+    for (int t = 4; t >= 2 && !cw; --t) {  // the largest chunk that fits (or the one asked for), all sources within the wave's slots
+      if (chunk_req > 0 && 16 * t != chunk_req) continue;
+      const int32_t nch = (ns_max + 16 * t - 1) / (16 * t);
+      const int32_t rcap = ((nch + 1) * nd_max + 1 + 3) & ~3;
+      if (nch > ls_max_chunks(t)) continue;
+      if (ls_lds_bytes(std::max(1, nd_max), 16 * t, own_cap, rcap) <= kLsLdsMax) cw = t;
+    }
+    if (!cw) continue;
+    const int32_t C = 16 * cw;
+    S.band_ok[(size_t)b] = 1, S.band_c0[(size_t)b] = c0, S.band_cw[(size_t)b] = cw, S.band_nd[(size_t)b] = nd_max, S.band_own[(size_t)b] = own_max;
+    S.band_nch[(size_t)b] = (ns_max + C - 1) / C;
+    S.band_rptr[(size_t)b] = (S.band_nch[(size_t)b] + 1) * nd_max + 1;
+    S.chunk_rows = std::max<int64_t>(S.chunk_rows, C);
+    S.any = true;
+    for (int32_t c = c0; c < c1; ++c) {
+      const int32_t s0 = P.grp_slot_ptr[(size_t)c], nb = P.grp_slot_ptr[(size_t)c + 1] - s0;
+      int32_t nd = 0;
+      for (int32_t r = 0; r < nb; ++r)
+        if (is_dep(s0 + r)) newpos[(size_t)(s0 + r)] = s0 + nd++;
+      int32_t q = nd;
+      for (int32_t r = 0; r < nb; ++r)
+        if (!is_dep(s0 + r)) newpos[(size_t)(s0 + r)] = s0 + q++;
+      int32_t *dsc = &S.desc[(size_t)c * kLsDescWords];
+      dsc[0] = s0, dsc[1] = nb, dsc[2] = nd, dsc[7] = nd ? (nb - nd + C - 1) / C : 0;
+      S.deps += nd, S.sources += nb - nd;
+    }
+  }
+  if (!S.any) return;
+  for (int64_t sl = 0; sl < m; ++sl) {
+    const int32_t ns = newpos[(size_t)sl];
+    S.rowid[(size_t)ns] = A.rowid[(size_t)sl];
+    S.oslot[(size_t)ns] = (int32_t)sl;
+  }
+  // pass 2: own entries by segment, levels, and the waves' outside-entry runs
+  auto push_outside = [&](LsStream<T> &E, bool f, int32_t sl, int32_t tag) {
+    for (int32_t k = P.split[(size_t)sl]; k < P.csplit[(size_t)sl]; ++k) E.col.push_back(A.col[(size_t)k]), E.val.push_back(A.val[(size_t)k]), E.tag.push_back((uint8_t)tag);
+    if (!f) return;
+    const int32_t i = A.rowid[(size_t)sl];
+    for (int32_t k = Fr->ptr[(size_t)i]; k < Fr->ptr[(size_t)i + 1]; ++k)
+      E.col.push_back((int32_t)(src_row0 + Fr->col[(size_t)k])), E.val.push_back(Fr->val[(size_t)k]), E.tag.push_back((uint8_t)tag);
+  };
+  bool fused_ok = with_f;
+  for (int64_t b = 0; b < nb_bands; ++b) {
+    if (!S.band_ok[(size_t)b]) continue;
+    const int32_t C = 16 * S.band_cw[(size_t)b];
+    const int32_t c0 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b]], c1 = P.wg_grp_ptr[(size_t)P.band_wg_ptr[(size_t)b + 1]];
+    for (int32_t c = c0; c < c1; ++c) {
+      int32_t *dsc = &S.desc[(size_t)c * kLsDescWords];
+      const int32_t s0 = dsc[0], nb = dsc[1], nd = dsc[2], nch = dsc[7];
+      const int32_t *cdd = &P.cd_desc[(size_t)c * kCdDescWords];
+      const int32_t cown0 = cdd[20], corp0 = cdd[22];
+      const int64_t own0 = (int64_t)S.own_val.size(), orp0 = (int64_t)S.own_rptr.size(), lvl0 = (int64_t)S.own_lvl.size();
+      // (the own lists of the PLAN are walked, not the CSR rows: they carry the one per-row order)
+      for (int32_t k = 0; k <= nch; ++k)
+        for (int32_t r = 0; r < nd; ++r) {
+          S.own_rptr.push_back((uint16_t)((int64_t)S.own_val.size() - own0));
+          const int32_t lr = S.oslot[(size_t)(s0 + r)] - s0;  // the plan's local row
+          for (int32_t e = cown0 + P.own_rptr[(size_t)corp0 + (size_t)lr]; e < cown0 + P.own_rptr[(size_t)corp0 + (size_t)lr + 1]; ++e) {
+            const int32_t q = newpos[(size_t)(s0 + P.own_lsrc[(size_t)e])] - s0;
+            const int32_t seg = q < nd ? nch : (q - nd) / C;
+            if (seg != k) continue;
+            S.own_val.push_back(A.val[(size_t)P.own_k[(size_t)e]]);
+            S.own_src.push_back((uint8_t)(q < nd ? q : q - nd - C * k));
+          }
+        }
+      S.own_rptr.push_back((uint16_t)((int64_t)S.own_val.size() - own0));
+      // levels of the dependent rows: a row's level = 1 + the deepest dependent row it reads; contiguous row ranges
+      std::vector<int32_t> lev((size_t)std::max(1, nd), 0);
+      int32_t cur = 0;
+      S.own_lvl.push_back(0);
+      for (int32_t r = 0; r < nd; ++r) {
+        int32_t need = 0;
+        const size_t seg = (size_t)orp0 + (size_t)nch * (size_t)nd + (size_t)r;
+        for (int32_t e = S.own_rptr[seg]; e < S.own_rptr[seg + 1]; ++e) need = std::max(need, lev[(size_t)S.own_src[(size_t)own0 + (size_t)e]] + 1);
+        if (need > cur) cur = need, S.own_lvl.push_back((uint8_t)r);
+        lev[(size_t)r] = cur;
+      }
+      S.own_lvl.push_back((uint8_t)nd);
+      dsc[3] = (int32_t)own0, dsc[4] = (int32_t)orp0, dsc[5] = (int32_t)lvl0, dsc[6] = (int32_t)((int64_t)S.own_lvl.size() - lvl0 - 1);
+      for (int f = 0; f < (with_f ? 2 : 1); ++f) {
+        LsStream<T> &E = f ? S.fused : S.plain;
+        const int64_t e0 = (int64_t)E.col.size();
+        E.base[(size_t)c] = (int32_t)e0;
+        uint16_t *wp = &E.wptr[(size_t)c * 33];
+        for (int w = 0; w < 16; ++w) {
+          wp[2 * w] = (uint16_t)((int64_t)E.col.size() - e0);
+          for (int32_t r = w; r < nd; r += 16) push_outside(E, f != 0, S.oslot[(size_t)(s0 + r)], r);
+          wp[2 * w + 1] = (uint16_t)((int64_t)E.col.size() - e0);
+          for (int32_t r = nd + w, q = 0; r < nb; r += 16, ++q) push_outside(E, f != 0, S.oslot[(size_t)(s0 + r)], q);
+        }
+        wp[32] = (uint16_t)((int64_t)E.col.size() - e0);
+        const int64_t cnt = (int64_t)E.col.size() - e0;
+        if (cnt > 65535 || (int64_t)E.col.size() > (int64_t)std::numeric_limits<int32_t>::max()) {
+          if (f) fused_ok = false;
+          else S.band_ok[(size_t)b] = 0;
+        }
+      }
+    }
+  }
+  S.plain.on = true;
+  S.fused.on = fused_ok;
+  if (!fused_ok) S.fused = LsStream<T>();
+}
+
+// what k_band_ls indexes with, re-derived from the arrays themselves (finalize calls it before the upload: no index out of
+// range reaches the kernel, whatever built the plan).  nsrc_rows: rows of the vector the outside entries gather from
+template <class T>
+void check_ls_plan(const BandPlan &P, const Csr<T> &A, const LsPlan<T> &S, int64_t nsrc_rows) {
+  auto fail = [](const char *why) { throw Error(4, std::string("internal error: streamed-source plan: ") + why); };
+  const int64_t m = A.nrows;
+  const size_t ngrp = P.grp_slot_ptr.size() - 1;
+  if ((int64_t)S.rowid.size() != m || (int64_t)S.oslot.size() != m || S.desc.size() != ngrp * (size_t)kLsDescWords) fail("array lengths");
+  if ((int64_t)S.band_ok.size() != P.nbands()) fail("band table");
+  std::vector<uint8_t> seen((size_t)m, 0);
+  for (int64_t ns = 0; ns < m; ++ns) {
+    const int32_t sl = S.oslot[(size_t)ns];
+    if (sl < 0 || sl >= m || seen[(size_t)sl]) fail("slot permutation");
+    seen[(size_t)sl] = 1;
+    if (S.rowid[(size_t)ns] != A.rowid[(size_t)sl]) fail("row ids");
+  }
+  if (S.own_val.size() != S.own_src.size()) fail("own-entry arrays");
+  for (int f = 0; f < 2; ++f) {
+    const LsStream<T> &E = f ? S.fused : S.plain;
+    if (!E.on) continue;
+    if (E.base.size() != ngrp || E.wptr.size() != ngrp * 33 || E.col.size() != E.val.size() || E.col.size() != E.tag.size()) fail("outside-entry arrays");
+    for (int32_t c : E.col)
+      if (c < 0 || c >= nsrc_rows) fail("outside-entry source");
+  }
+  for (int64_t b = 0; b < P.nbands(); ++b) {
+    if (!S.band_ok[(size_t)b]) continue;
+    const int32_t g0 = P.band_wg_ptr[(size_t)b], g1 = P.band_wg_ptr[(size_t)b + 1];
+    if (S.band_c0[(size_t)b] != P.wg_grp_ptr[(size_t)g0] || P.wg_grp_ptr[(size_t)g1] - P.wg_grp_ptr[(size_t)g0] != g1 - g0) fail("one component per workgroup");
+    const int32_t cw = S.band_cw[(size_t)b], C = 16 * cw, nchb = S.band_nch[(size_t)b];
+    if (cw < 2 || cw > 4 || nchb < 0 || nchb > ls_max_chunks(cw)) fail("chunk size");
+    const int32_t own_cap = std::max(64, (S.band_own[(size_t)b] + 63) & ~63);
+    if (ls_lds_bytes(std::max(1, S.band_nd[(size_t)b]), C, own_cap, (S.band_rptr[(size_t)b] + 3) & ~3) > kLsLdsMax) fail("LDS size");
+    for (int32_t c = P.wg_grp_ptr[(size_t)g0]; c < P.wg_grp_ptr[(size_t)g1]; ++c) {
+      const int32_t *dsc = &S.desc[(size_t)c * kLsDescWords];
+      const int32_t s0 = dsc[0], nb = dsc[1], nd = dsc[2], own0 = dsc[3], orp0 = dsc[4], lvl0 = dsc[5], nlvl = dsc[6], nch = dsc[7];
+      if (s0 != P.grp_slot_ptr[(size_t)c] || nb != P.grp_slot_ptr[(size_t)c + 1] - s0 || nb < 1 || nb > 255 || nd < 0 || nd > nb) fail("descriptor");
+      if (nd > S.band_nd[(size_t)b]) fail("dependent rows exceed the band's LDS size");
+      if (nch < 0 || nch > nchb || (nd > 0 && nch * C < nb - nd) || nb - nd > C * ls_max_chunks(cw)) fail("chunks do not cover the sources");
+      for (int32_t r = 0; r < nb; ++r)
+        if (S.oslot[(size_t)(s0 + r)] < s0 || S.oslot[(size_t)(s0 + r)] >= s0 + nb) fail("a row left its component");
+      // the sources are the rows WITHOUT own entries, the dependent rows the ones with; every own entry of the triangle is
+      // accounted for once
+      int64_t own_csr = 0;
+      for (int32_t r = 0; r < nb; ++r) {
+        const int32_t sl = S.oslot[(size_t)(s0 + r)];
+        const int32_t cnt = A.ptr[(size_t)sl + 1] - P.csplit[(size_t)sl];
+        if (r >= nd && cnt != 0) fail("a source has an own entry");
+        if (r < nd && cnt == 0) fail("a dependent row without own entries");
+        own_csr += cnt;
+      }
+      const size_t nseg = (size_t)(nch + 1) * (size_t)nd;
+      if (orp0 < 0 || (size_t)orp0 + nseg + 1 > S.own_rptr.size() || (int64_t)nseg + 1 > S.band_rptr[(size_t)b]) fail("offset arrays");
+      if (lvl0 < 0 || nlvl < 1 || (size_t)lvl0 + (size_t)nlvl + 1 > S.own_lvl.size()) fail("level array");
+      const uint16_t *rp = &S.own_rptr[(size_t)orp0];
+      const int32_t nown = rp[nseg];
+      if (own0 < 0 || (size_t)own0 + (size_t)nown > S.own_val.size() || nown > S.band_own[(size_t)b]) fail("own entries");
+      if (own_csr != nown) fail("own entries lost");
+      if (S.own_lvl[(size_t)lvl0] != 0 || S.own_lvl[(size_t)lvl0 + (size_t)nlvl] != nd) fail("level ends");
+      std::vector<int32_t> lev((size_t)std::max(1, nd), -1);
+      for (int32_t lv = 0; lv < nlvl; ++lv) {
+        const int32_t a = S.own_lvl[(size_t)lvl0 + (size_t)lv], e = S.own_lvl[(size_t)lvl0 + (size_t)lv + 1];
+        if (e < a || e > nd) fail("levels not monotone");
+        for (int32_t r = a; r < e; ++r) lev[(size_t)r] = lv;
+      }
+      for (size_t sg = 0; sg < nseg; ++sg) {
+        const int32_t eb = rp[sg], ee = rp[sg + 1], k = (int32_t)(sg / (size_t)nd), r = (int32_t)(sg % (size_t)nd);
+        if (ee < eb || ee > nown) fail("own offsets");
+        for (int32_t e = eb; e < ee; ++e) {
+          const int32_t q = S.own_src[(size_t)own0 + (size_t)e];
+          if (k < nch) {
+            if (q >= C || nd + k * C + q >= nb) fail("a source entry filed under the wrong chunk");
+            if (e > eb && S.own_src[(size_t)own0 + (size_t)e - 1] >= q) fail("source entries not ascending");
+          } else {
+            if (q >= nd) fail("a dependent entry reads a source slot");
+            if (!(lev[(size_t)q] < lev[(size_t)r])) fail("a dependent row reads a row of its own or a later level");
+          }
+        }
+      }
+      // against the triangle itself: row r's entries, chunk by chunk and then the dependent ones, are its own CSR entries
+      for (int32_t r = 0; r < nd; ++r) {
+        const int32_t sl = S.oslot[(size_t)(s0 + r)];
+        std::vector<std::pair<int32_t, double>> want, got;
+        for (int32_t k = P.csplit[(size_t)sl]; k < A.ptr[(size_t)sl + 1]; ++k) want.push_back({P.srcslot[(size_t)k], real_(A.val[(size_t)k])});
+        for (int32_t k = 0; k <= nch; ++k)
+          for (int32_t e = rp[(size_t)k * (size_t)nd + (size_t)r]; e < rp[(size_t)k * (size_t)nd + (size_t)r + 1]; ++e) {
+            const int32_t q = S.own_src[(size_t)own0 + (size_t)e];
+            got.push_back({S.oslot[(size_t)(s0 + (k < nch ? nd + k * C + q : q))], real_(S.own_val[(size_t)own0 + (size_t)e])});
+          }
+        std::sort(want.begin(), want.end()), std::sort(got.begin(), got.end());
+        if (want != got) fail("own entries differ from the triangle's");
+      }
+      for (int f = 0; f < 2; ++f) {
+        const LsStream<T> &E = f ? S.fused : S.plain;
+        if (!E.on) continue;
+        const int32_t e0 = E.base[(size_t)c];
+        const uint16_t *wp = &E.wptr[(size_t)c * 33];
+        if (e0 < 0 || (size_t)e0 + (size_t)wp[32] > E.col.size() || wp[0] != 0) fail("outside-entry runs");
+        for (int w = 0; w < 16; ++w) {
+          if (wp[2 * w + 1] < wp[2 * w] || wp[2 * w + 2] < wp[2 * w + 1]) fail("outside-entry runs not monotone");
+          for (int32_t e = wp[2 * w]; e < wp[2 * w + 1]; ++e) {
+            const int32_t t = E.tag[(size_t)e0 + (size_t)e];
+            if (t >= nd || (t & 15) != w) fail("a dependent run names another wave's row");
+          }
+          for (int32_t e = wp[2 * w + 1]; e < wp[2 * w + 2]; ++e) {
+            const int32_t t = E.tag[(size_t)e0 + (size_t)e];
+            if (t >= kLsMaxSlots || nd + w + 16 * t >= nb) fail("a source run names a row outside the component");
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Tile form of what a dense-own component band walks (round 4; kernel k_band_ct).  The entries [split, csplit) of a
 // component's rows -- sources finished by earlier launches -- are a small sparse matrix (rows x distinct sources) whose
 // rows share most of their sources (measured on the reference's 1M-row hierarchies: a 16-row strip of a component

@@ -3417,6 +3417,202 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Sparse-own L band with streamed sources (host.hpp build_ls_plan).  One component per workgroup (1,024 threads), R = 64.
+// The component's rows are its DEPENDENT rows (they have entries inside the component; new local index < nd) and its
+// SOURCES (they have none: their value is final once their outside entries are subtracted).  Wave w owns the dependent
+// rows w, w + 16, ... and the sources nd + w + 16 q (register slot q < CW * NCH; chunk q / CW of C = 16 CW rows).
+//   phase 0  the component's own entries / segment offsets / levels into LDS; the dependent rows' ids
+//   phase 1  every row load of the wave is requested up front (dependent rows and all source slots; clamped rows, no
+//            conditional global access); the dependent rows' right-hand sides minus their outside entries go to LDS
+//            (k_band_cd's walk: items of 64, eight gathers per batch, the running row's sum in a register); the sources are
+//            formed in registers the same way and stored (unless RowSkip says nobody reads them from memory)
+//   phase 2  chunk by chunk: the waves deposit their slots of chunk k, barrier, every dependent row subtracts its entries
+//            into the chunk (segment k of its own list), barrier
+//   phase 3  the dependent rows level by level in LDS over the last segment (k_band_cd<true, sparse>'s loop); stored as
+//            they finish
+// Per row: right-hand side, outside entries, own entries to sources by ascending source, own entries to dependent rows --
+// the order host.hpp ls_reorder_own gives the lists k_band_cd / k_band_cs walk: the same bits at every batch width.
+// LDS: (dependent rows + C) x 512 B + the own entries: two workgroups per compute unit (<= 64 VGPRs without scratch up to
+// nine register slots: the instances engine.hip ls_kernel lists).
+// ---------------------------------------------------------------------------------------------
+template <int CW, int NCH>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)))
+    k_band_ls(int32_t c0, const int32_t *__restrict__ desc, const int32_t *__restrict__ rowid, const int32_t *__restrict__ oslot,
+              const int32_t *__restrict__ ebase, const uint16_t *__restrict__ ewptr, const int32_t *__restrict__ ecol,
+              const double *__restrict__ eval, const uint8_t *__restrict__ etag, const double *__restrict__ own_val,
+              const uint8_t *__restrict__ own_src, const uint16_t *__restrict__ own_rptr, const uint8_t *__restrict__ own_lvl,
+              double *w, int32_t lds_dep, int32_t own_cap, int32_t rptr_cap, FirstL<double> fl, RowSkip rs) {
+  extern __shared__ double ls_tb[];  // [lds_dep][64] dependent rows, [16 CW][64] chunk; own values, row ids, offsets, own sources, levels
+  constexpr int NS = CW * NCH, C = 16 * CW;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t comp = c0 + (int32_t)blockIdx.x;
+  const int32_t *dsc = desc + (int64_t)comp * 8;
+  const int32_t s0 = dsc[0], nb = dsc[1], nd = dsc[2], own0 = dsc[3], orp0 = dsc[4], lvl0 = dsc[5], nlvl = dsc[6], nch = dsc[7];
+  double *chunk = ls_tb + (size_t)lds_dep * 64;
+  double *ow_val = chunk + C * 64;
+  int32_t *s_rowid = reinterpret_cast<int32_t *>(ow_val + own_cap);
+  uint16_t *ow_rptr = reinterpret_cast<uint16_t *>(s_rowid + ((lds_dep + 1) & ~1));
+  uint8_t *ow_src = reinterpret_cast<uint8_t *>(ow_rptr + rptr_cap);
+  uint8_t *ow_lvl = ow_src + own_cap;
+  const bool first_l = fl.on();
+  const double *rhs = first_l ? fl.bin.get() : (const double *)w;
+  const int64_t rstride = first_l ? fl.ldb : 64;
+  const int rlane = first_l ? min(lane, fl.nrhs - 1) : lane;
+  // ---- phase 0
+  const int32_t nseg = (nch + 1) * nd;
+  const int32_t nown = own_rptr[orp0 + nseg];
+  for (int32_t t = (int32_t)threadIdx.x; t < nown; t += 1024) {
+    ow_val[t] = own_val[own0 + t];
+    ow_src[t] = own_src[own0 + t];
+  }
+  for (int32_t t = (int32_t)threadIdx.x; t <= nseg; t += 1024) ow_rptr[t] = own_rptr[orp0 + t];
+  for (int32_t t = (int32_t)threadIdx.x; t <= nlvl; t += 1024) ow_lvl[t] = own_lvl[lvl0 + t];
+  // ---- phase 1: lane j holds the scalars of the wave's j-th dependent row (j < 16) and of its source slot j (j < NS)
+  const int32_t dr = min(wave + 16 * lane, nb - 1), sr = min(nd + wave + 16 * lane, nb - 1);  // (clamped: every load is valid)
+  const int32_t g_rid = rowid[s0 + sr];
+  int32_t d_i = rowid[s0 + dr], g_i = g_rid;
+  const int d_f = rs.flag ? (int)rs.flag[oslot[s0 + dr]] : 0, g_f = rs.flag ? (int)rs.flag[oslot[s0 + sr]] : 0;
+  if (wave + 16 * lane < nd) s_rowid[dr] = (d_f & 1) ? ~d_i : d_i;  // (negative: not stored)
+  const bool g_store = !(g_f & 1);
+  double d_s = 1.0, g_s = 1.0;
+  if (first_l) {
+    d_i = fl.p[d_i], g_i = fl.p[g_i];
+    d_s = fl.s[d_i], g_s = fl.s[g_i];
+  }
+  const int32_t eb0 = ebase[comp];
+  const uint16_t *wp = ewptr + (int64_t)comp * 33 + 2 * wave;
+  const int32_t ed0 = eb0 + (int32_t)wp[0], es0 = eb0 + (int32_t)wp[1], es1 = eb0 + (int32_t)wp[2];
+  // first items of the wave's two entry runs: requested before the right-hand sides are waited for
+  const int32_t ad = min(ed0 + lane, max(es0 - 1, ed0)), as = min(es0 + lane, max(es1 - 1, es0));  // (the arrays are padded)
+  int32_t colv = ecol[ad], lrv = etag[ad];
+  double valv = eval[ad];
+  int32_t scol = ecol[as], stag = etag[as];
+  double sval = eval[as];
+  // the source slots' right-hand sides: all in flight from here on
+  double t_[NS];
+#pragma unroll
+  for (int q = 0; q < NS; ++q) t_[q] = rhs[(int64_t)rl32(g_i, q) * rstride + rlane];
+  // the dependent rows' right-hand sides into LDS, four at a time
+  for (int j = 0; wave + 16 * j < nd; j += 4) {
+    double u_[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) u_[q] = rhs[(int64_t)rl32(d_i, min(j + q, 15)) * rstride + rlane];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = wave + 16 * (j + q);
+      if (r < nd) ls_tb[(r << 6) + lane] = first_l ? (lane < fl.nrhs ? rl64(d_s, min(j + q, 15)) * u_[q] : 0.0) : u_[q];
+    }
+  }
+  // the dependent rows' outside entries (k_band_cd phase 1b)
+  {
+    int cur_r = -1;
+    double acc = 0.0;
+    for (int32_t e = ed0; e < es0; e += 64) {
+      const int cnt = min(64, es0 - e);
+      const int32_t an = min(e + 64 + lane, es0 - 1);
+      const int32_t colv2 = ecol[an], lrv2 = etag[an];
+      const double valv2 = eval[an];
+      for (int t = 0; t < cnt; t += 8) {
+        int32_t j_[8], r_[8];
+        double a_[8], xv_[8];
+#pragma unroll
+        for (int b2 = 0; b2 < 8; ++b2) {
+          const int idx = min(t + b2, cnt - 1);
+          j_[b2] = rl32(colv, idx);
+          a_[b2] = rl64(valv, idx);
+          r_[b2] = rl32(lrv, idx);
+        }
+#pragma unroll
+        for (int b2 = 0; b2 < 8; ++b2) xv_[b2] = w[((int64_t)j_[b2] << 6) + lane];
+#pragma unroll
+        for (int b2 = 0; b2 < 8; ++b2)
+          if (t + b2 < cnt) {
+            if (r_[b2] != cur_r) {  // (wave-uniform)
+              if (cur_r >= 0) ls_tb[(cur_r << 6) + lane] = acc;
+              cur_r = r_[b2];
+              acc = ls_tb[(cur_r << 6) + lane];
+            }
+            acc = acc - a_[b2] * xv_[b2];
+          }
+      }
+      colv = colv2, valv = valv2, lrv = lrv2;
+    }
+    if (cur_r >= 0) ls_tb[(cur_r << 6) + lane] = acc;
+  }
+  // the sources: scale, outside entries (the same walk, the sums in the slots' registers), store
+  if (first_l) {
+#pragma unroll
+    for (int q = 0; q < NS; ++q) t_[q] = lane < fl.nrhs ? rl64(g_s, q) * t_[q] : 0.0;
+  }
+  for (int32_t e = es0; e < es1; e += 64) {
+    const int cnt = min(64, es1 - e);
+    const int32_t an = min(e + 64 + lane, es1 - 1);
+    const int32_t scol2 = ecol[an], stag2 = etag[an];
+    const double sval2 = eval[an];
+    for (int t = 0; t < cnt; t += 8) {
+      int32_t j_[8], r_[8];
+      double a_[8], xv_[8];
+#pragma unroll
+      for (int b2 = 0; b2 < 8; ++b2) {
+        const int idx = min(t + b2, cnt - 1);
+        j_[b2] = rl32(scol, idx);
+        a_[b2] = rl64(sval, idx);
+        r_[b2] = (t + b2 < cnt) ? rl32(stag, idx) : -1;
+      }
+#pragma unroll
+      for (int b2 = 0; b2 < 8; ++b2) xv_[b2] = w[((int64_t)j_[b2] << 6) + lane];
+#pragma unroll
+      for (int b2 = 0; b2 < 8; ++b2) {
+        const double pr = a_[b2] * xv_[b2];
+#pragma unroll
+        for (int q = 0; q < NS; ++q)
+          if (r_[b2] == q) t_[q] = t_[q] - pr;  // (wave-uniform)
+      }
+    }
+    scol = scol2, sval = sval2, stag = stag2;
+  }
+#pragma unroll
+  for (int q = 0; q < NS; ++q) {
+    const bool st = rl32((int32_t)g_store, q) != 0 && nd + wave + 16 * q < nb;  // (wave-uniform)
+    if (st) w[((int64_t)rl32(g_rid, q) << 6) + lane] = t_[q];
+  }
+  // ---- phase 2: the sources pass through the chunk buffer
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    if (k < nch) {  // (workgroup-uniform)
+#pragma unroll
+      for (int j = 0; j < CW; ++j) chunk[((wave + 16 * j) << 6) + lane] = t_[k * CW + j];
+      __syncthreads();
+      for (int r = wave; r < nd; r += 16) {
+        const int eb = ow_rptr[k * nd + r], ee = ow_rptr[k * nd + r + 1];
+        if (ee > eb) {
+          double a2 = ls_tb[(r << 6) + lane];
+          for (int e = eb; e < ee; ++e) a2 = a2 - ow_val[e] * chunk[((int)ow_src[e] << 6) + lane];
+          ls_tb[(r << 6) + lane] = a2;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (nch == 0) __syncthreads();  // (a component without dependent rows: nothing follows, but phase 0 wrote LDS)
+  // ---- phase 3: the dependent rows, depth level by depth level
+  const uint16_t *rp3 = ow_rptr + nch * nd;
+  for (int lv = 0; lv < nlvl; ++lv) {
+    const int r_lo = ow_lvl[lv], r_hi = ow_lvl[lv + 1];
+    for (int r = r_lo + wave; r < r_hi; r += 16) {
+      double a2 = ls_tb[(r << 6) + lane];
+      const int eb = rp3[r], ee = rp3[r + 1];
+      for (int e = eb; e < ee; ++e) a2 = a2 - ow_val[e] * ls_tb[((int)ow_src[e] << 6) + lane];
+      if (ee > eb) ls_tb[(r << 6) + lane] = a2;
+      const int32_t rid = s_rowid[r];
+      if (rid >= 0) w[((int64_t)rid << 6) + lane] = a2;
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Column-sliced component band (round 3).  The same plan, descriptors and packed streams as k_band_cd, but a workgroup
 // solves ONE component for a SLICE of 16 right-hand-side columns: blockIdx.x = component-workgroup * nsl + slice, and
 // every step of the solve is column-separable, so the nsl slices of a component never talk to each other.  Why:

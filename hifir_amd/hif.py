@@ -214,6 +214,14 @@ class HIF:
                 "rows_not_stored_L", "rows_not_stored_U", "host_copy_repairs", "nsp_basis_bytes"]
         return {key: float(s[i]) for i, key in enumerate(keys[:max(0, k)])}
 
+    def ls_stats(self):
+        """Sparse-own L bands that run with streamed sources (hifamd_stats_ext slots 23-25): rows streamed as sources, rows
+        kept in LDS as dependent rows, rows of the source chunk (0: no band runs that way)."""
+        s = np.zeros(32)
+        k = lib().hifamd_stats_ext(self._h, _p(s), 32)
+        keys = ["ls_streamed_sources", "ls_lds_rows", "ls_chunk_rows"]
+        return {key: float(s[23 + i]) if 23 + i < k else 0.0 for i, key in enumerate(keys)}
+
     def level_stats(self, level):
         s = np.zeros(16)
         k = lib().hifamd_level_stats(self._h, int(level), _p(s), 16)

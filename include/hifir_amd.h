@@ -152,7 +152,9 @@ HifAmdStatus hifamd_stats(HifAmdHdl h, double *stats16);
  * 19 / 20 rows (all levels) whose L / U result the FIRST solve of a level does not store because nothing reads it from
  * memory (real handles, sparse-own levels; HIFIR_AMD_SKIP_ROWS=0: none), 21 arrays of the host copy that hifamd_finalize found
  * changed since hifamd_add_level -- not by this library -- and rebuilt from the imported arrays (a warning names them on stderr;
- * anything it cannot rebuild is refused), 22 bytes of the null-space bases resident in HBM (hifamd_set_nsp_basis, both ops).
+ * anything it cannot rebuild is refused), 22 bytes of the null-space bases resident in HBM (hifamd_set_nsp_basis, both ops),
+ * 23 / 24 rows of sparse-own L bands that are streamed as sources / kept in LDS as dependent rows (kernel k_band_ls), 25 rows
+ * of that kernel's source chunk (0: no band runs through it).
  * -1 for a NULL handle. */
 int hifamd_stats_ext(HifAmdHdl h, double *out, int cap);
 /* Per-level sizes (what the SURVEY 8(d) byte formula needs level by level): 0 m, 1 n, 2 nnz(L_B), 3 nnz(U_B), 4 nnz(E),
