@@ -45,6 +45,8 @@ SIGNATURES = {
     "hifamd_stats_ext": (_int, [_vp, _vp, _int]),
     "hifamd_level_stats": (_int, [_vp, _int, _vp, _int]),
     "hifamd_launch_map": (_int, [_vp, _vp, _int]),
+    "hifamd_kernel_census": (_int, [_vp, _vp, _int]),
+    "hifamd_kernel_family_name": (C.c_char_p, [_int]),
     "hifamd_level_schedule": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "hifamd_solve": (_int, [_vp, _vp, _vp, _i64]),
     "hifamd_solve_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64]),

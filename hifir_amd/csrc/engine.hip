@@ -7,11 +7,14 @@
 // alg/IterRefine.hpp:77-165.  There is NO host fallback: every compute path needs a HIP device.
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <tuple>
 #include <type_traits>
 
@@ -367,6 +370,44 @@ struct GraphKey {  // one graph per SHAPE: the caller's pointers are read from a
   }
 };
 
+// Kernel families of the launch census (hifamd_kernel_census): one per kernel the dispatch can choose between.  THE order of
+// the C call's output; kFamilyNames below and hifir_amd/hif.py KERNEL_FAMILIES follow it (tests/test_abi_and_host.py compares them)
+enum KernelFamily {
+  KF_BAND_CT1, KF_BAND_CT2, KF_BAND_CT4, KF_BAND_CD, KF_BAND_CD_SPARSE, KF_BAND_CS, KF_BAND_CS_SPARSE, KF_BAND_US, KF_BAND_LS,
+  KF_BAND_CT_Z, KF_BAND_CS_Z, KF_BAND_CD_Z,
+  KF_TRSV_BAND, KF_TRSV_BAND_P, KF_TRSV_WIDE, KF_THIN_UPDATE,
+  KF_SPMM_TILE_RB1, KF_SPMM_TILE_RB2, KF_SPMM_TILE4_RB1, KF_SPMM_TILE4_RB2, KF_SPMM_TILE_Z, KF_SPMM_EPI, KF_SPMM_EPI_NARROW,
+  KF_TOP_GEMM, KF_TOP_REDUCE, KF_STRIP_GEMM, KF_STRIP_GEMM4, KF_TRI_GEMM, KF_DENSE_GEMM, KF_ZCOMBINE,
+  KF_GATHER_SCALE, KF_SCATTER_SCALE, KF_SCATTER_SCALE_LIST,
+  KF_BAND_SPLIT_PREFIX,  // k_trsv_wide as the chip-wide prefix pass of a split component band (HIFIR_AMD_CD_SPLIT_MIN)
+  KF_ROW_GATHER,         // the row permutation in front of the adjoint's dense block
+  KF_PROD,               // every kernel of the product M b that the apply does not share (k_gather_div ... k_scatter_div)
+  KF_COUNT
+};
+static const char *const kFamilyNames[KF_COUNT] = {
+    "band_ct1", "band_ct2", "band_ct4", "band_cd", "band_cd_sparse", "band_cs", "band_cs_sparse", "band_us", "band_ls",
+    "band_ct_z", "band_cs_z", "band_cd_z",
+    "trsv_band", "trsv_band_p", "trsv_wide", "thin_update",
+    "spmm_tile_rb1", "spmm_tile_rb2", "spmm_tile4_rb1", "spmm_tile4_rb2", "spmm_tile_z", "spmm_epi", "spmm_epi_narrow",
+    "top_gemm", "top_reduce", "strip_gemm", "strip_gemm4", "tri_gemm", "dense_gemm", "zcombine",
+    "gather_scale", "scatter_scale", "scatter_scale_list",
+    "band_split_prefix", "row_gather", "prod"};
+// launches per family: [0, KF_COUNT) on every level, [KF_COUNT, 2 KF_COUNT) those of them on a level >= 1
+typedef std::array<int32_t, 2 * KF_COUNT> Census;
+// Graph capture, instantiation and launch are serialized across the handles of a process: distinct handles may be used from
+// distinct host threads (hifir_amd.h), and the runtime's graph calls have not proved safe to interleave between threads (a
+// host-side crash inside two concurrent applies of tests/test_gpu_parity.py::test_two_handles_from_two_threads).  Only the
+// enqueue is inside the lock -- the kernels of two handles still overlap on the device -- and an uncontended lock costs
+// nanoseconds per apply.
+static std::mutex &graph_mutex() {
+  static std::mutex m;
+  return m;
+}
+static std::atomic<uint64_t> &census_clock() {
+  static std::atomic<uint64_t> c{0};
+  return c;
+}
+
 struct GraphEntry {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -374,6 +415,7 @@ struct GraphEntry {
   int64_t launches = 0;
   uint64_t stamp = 0;
   std::vector<int32_t> map;  // per launch: 16 * level + stage (Engine::launch_map)
+  Census census{};           // launches by kernel family (Engine::kernel_census)
 };
 
 class EngineBase {
@@ -428,6 +470,16 @@ class Engine : public EngineBase {
   std::vector<int32_t> cur_map, last_map;
   void mark(size_t level, int stage, int64_t c0, int64_t c1) {
     for (int64_t c = c0; c < c1; ++c) cur_map.push_back((int32_t)(16 * level + stage));
+  }
+  // launches by kernel family of the apply being enqueued, kept like the launch map (host-side bookkeeping at the launch
+  // sites); last_census: of the apply launched last, summed over the twin lanes (hifamd_kernel_census).  census_seq orders
+  // the applies of a handle's two engines: the call reports the one that ran last, forwards or adjoint.
+  Census cur_census{}, last_census{};
+  int cur_level = 0;
+  uint64_t census_seq = 0;
+  void tally(int family, int n = 1) {
+    cur_census[(size_t)family] += n;
+    if (cur_level >= 1) cur_census[(size_t)(KF_COUNT + family)] += n;
   }
   bool use_graph = true;
   int min_logR = 6;
@@ -491,6 +543,7 @@ class Engine : public EngineBase {
   int ct_mode = 1;       // HIFIR_AMD_CT=0: dense-own component bands walk their entries one by one (k_band_cd / k_band_cs) instead of
                          // multiplying 16 x 4 coefficient tiles on the matrix cores (k_band_ct)
   int act_cols = 64;     // columns of the 64-column arena that the tile being enqueued actually uses (enqueue_apply)
+  int xcd_remap = 1;     // HIFIR_AMD_XCD=0: workgroups numbered as the hardware deals them (one device-wide word, set by the last finalize)
   int band_pipe = 1;     // 1: k_trsv_band_p (next row's head behind the last gathers), 0: k_trsv_band at R = 64 too
   BandOptions band_opt;  // how triangles are cut into bands (host.hpp)
   DevBuf errflag;        // sticky error word: a bounded spin of k_trsv_band expired
@@ -578,6 +631,7 @@ class Engine : public EngineBase {
     fuse_gather = env_int("HIFIR_AMD_FUSE_S1", 1) != 0;
     spmm_tiles = env_int("HIFIR_AMD_SPMM_TILES", 1) != 0;
     use_twin = env_int("HIFIR_AMD_TWIN", 1);
+    xcd_remap = env_int("HIFIR_AMD_XCD", 1);
     band_opt.thin_rows = env_int("HIFIR_AMD_THIN_ROWS", 96);
     band_opt.band_depth = env_int("HIFIR_AMD_BAND_DEPTH", 32);
     band_opt.max_wgs = env_int("HIFIR_AMD_BAND_WGS", 1024);
@@ -728,6 +782,25 @@ class Engine : public EngineBase {
     host.levels.push_back(std::move(H));
   }
 
+  // The adjoint engine and the twin lanes are built on first use, long after the handle: they run with the options the
+  // handle read from the environment when it was created, not with what the environment holds when they are built.
+  void inherit_options(const Engine<T> &P) {
+    use_graph = P.use_graph, min_logR = P.min_logR, band_opt = P.band_opt, gemm_waves = P.gemm_waves;
+    fuse_gather = P.fuse_gather, spmm_tiles = P.spmm_tiles, top_gemm = P.top_gemm, fuse_f = P.fuse_f;
+    carry_wgs = P.carry_wgs, spmm_split = P.spmm_split, fuse_out = P.fuse_out, tail_rows = P.tail_rows;
+    cd_dbg = P.cd_dbg, cs_mode = P.cs_mode, cs_max_wgs = P.cs_max_wgs;
+    ct_mode = P.ct_mode, ct_mode_z = P.ct_mode_z, ct_mode_real = P.ct_mode_real;
+    skip_rows = P.skip_rows, narrow_tiles = P.narrow_tiles, us_mode = P.us_mode, ls_mode = P.ls_mode, ls_chunk = P.ls_chunk;
+    list_early = P.list_early, spmm_rb = P.spmm_rb, spmm_tiles_z = P.spmm_tiles_z, spmm_split_blocks = P.spmm_split_blocks;
+    ct_wide_wgs = P.ct_wide_wgs, ct_wide4_wgs = P.ct_wide4_wgs, cs_sparse = P.cs_sparse, narrow_spmm = P.narrow_spmm;
+    cd_split_min = P.cd_split_min, cd_split_wgs = P.cd_split_wgs;
+    // (these five were left to the environment of the moment until the variant tests built handles under a switch and
+    // solved transposed and in two lanes after it was gone)
+    band_pipe = P.band_pipe, top_last_arriver = P.top_last_arriver, use_twin = P.use_twin;
+    device_inverses = P.device_inverses, xcd_remap = P.xcd_remap;
+    tail_probe_tol = P.tail_probe_tol, tail_max_growth = P.tail_max_growth;
+  }
+
   Engine<T> &adjoint_engine() {
     if (adjoint) throw Error(HIFAMD_HIFIR_ERROR, "internal error: adjoint of the adjoint engine");
     if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
@@ -736,39 +809,7 @@ class Engine : public EngineBase {
       E->adjoint = true;
       E->stream = stream;
       E->owns_stream = false;
-      E->use_graph = use_graph;
-      E->min_logR = min_logR;
-      E->band_opt = band_opt;
-      E->gemm_waves = gemm_waves;
-      E->fuse_gather = fuse_gather;
-      E->spmm_tiles = spmm_tiles;
-      E->top_gemm = top_gemm;
-      E->fuse_f = fuse_f;
-      E->carry_wgs = carry_wgs;
-      E->spmm_split = spmm_split;
-      E->fuse_out = fuse_out;
-      E->tail_rows = tail_rows;
-      E->cd_dbg = cd_dbg;
-      E->cs_mode = cs_mode;
-      E->cs_max_wgs = cs_max_wgs;
-      E->ct_mode = ct_mode;
-      E->ct_mode_z = ct_mode_z;
-      E->ct_mode_real = ct_mode_real;
-      E->skip_rows = skip_rows;
-      E->narrow_tiles = narrow_tiles;
-      E->us_mode = us_mode;
-      E->ls_mode = ls_mode;
-      E->ls_chunk = ls_chunk;
-      E->list_early = list_early;
-      E->spmm_rb = spmm_rb;
-      E->spmm_tiles_z = spmm_tiles_z;
-      E->spmm_split_blocks = spmm_split_blocks;
-      E->ct_wide_wgs = ct_wide_wgs;
-      E->ct_wide4_wgs = ct_wide4_wgs;
-      E->cs_sparse = cs_sparse;
-      E->narrow_spmm = narrow_spmm;
-      E->cd_split_min = cd_split_min;
-      E->cd_split_wgs = cd_split_wgs;
+      E->inherit_options(*this);
       for (const auto &P : host.levels) E->add_level_adjoint(P);
       if (host.has_dense && host.dense.kind == 2) {  // LUP: ?getrs 'T' / ?gemv 'C' (LUP.hpp:150,187)
         E->host.dense.kind = 2;
@@ -811,39 +852,7 @@ class Engine : public EngineBase {
       std::unique_ptr<Engine<T>> E(new Engine<T>(device));
       E->is_twin = true;
       E->adjoint = adjoint;
-      E->use_graph = use_graph;
-      E->min_logR = min_logR;
-      E->band_opt = band_opt;
-      E->gemm_waves = gemm_waves;
-      E->fuse_gather = fuse_gather;
-      E->spmm_tiles = spmm_tiles;
-      E->top_gemm = top_gemm;
-      E->fuse_f = fuse_f;
-      E->carry_wgs = carry_wgs;
-      E->spmm_split = spmm_split;
-      E->fuse_out = fuse_out;
-      E->tail_rows = tail_rows;
-      E->cd_dbg = cd_dbg;
-      E->cs_mode = cs_mode;
-      E->cs_max_wgs = cs_max_wgs;
-      E->ct_mode = ct_mode;
-      E->ct_mode_z = ct_mode_z;
-      E->ct_mode_real = ct_mode_real;
-      E->skip_rows = skip_rows;
-      E->narrow_tiles = narrow_tiles;
-      E->us_mode = us_mode;
-      E->ls_mode = ls_mode;
-      E->ls_chunk = ls_chunk;
-      E->list_early = list_early;
-      E->spmm_rb = spmm_rb;
-      E->spmm_tiles_z = spmm_tiles_z;
-      E->spmm_split_blocks = spmm_split_blocks;
-      E->ct_wide_wgs = ct_wide_wgs;
-      E->ct_wide4_wgs = ct_wide4_wgs;
-      E->cs_sparse = cs_sparse;
-      E->narrow_spmm = narrow_spmm;
-      E->cd_split_min = cd_split_min;
-      E->cd_split_wgs = cd_split_wgs;
+      E->inherit_options(*this);
       E->max_nrhs = max_nrhs;
       E->Rmax = Rmax;
       E->host.has_dense = host.has_dense;
@@ -1373,7 +1382,7 @@ class Engine : public EngineBase {
       zt2.alloc(rows * (size_t)Rmax * 2 * sizeof(double));
     }
     {
-      const int remap = env_int("HIFIR_AMD_XCD", 1);
+      const int remap = xcd_remap;
       HIP_OK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xcd_remap), &remap, sizeof(int), 0, hipMemcpyHostToDevice, xfer_stream()));
       HIP_OK(hipStreamSynchronize(xfer_stream()));
     }
@@ -1616,6 +1625,7 @@ class Engine : public EngineBase {
       if (cd_two) {
         const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
         const bool touched = fused && have_carried;  // [ptr, split) was folded in (first touch included) by the previous launch
+        tally(KF_BAND_SPLIT_PREFIX);
         hipLaunchKernelGGL((k_trsv_wide<D, LOWER, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
                            (touched ? M.split : M.ptr).template as<int32_t>(), M.csplit.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(),
                            M.rowid.as<int32_t>(), L.d.as<D>(), w, v, logR, touched ? 0 : 1, (D *)nullptr, 0, touched ? no_fl() : fl);
@@ -1629,6 +1639,7 @@ class Engine : public EngineBase {
                           M.blk_slot0[(size_t)qb0] == M.band_slot_ptr[b];
       if (pre && !cd_two && !(fused && have_carried)) {  // (a fused band whose predecessor could not carry it: its own launch)
         const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
+        tally(KF_TRSV_WIDE);
         hipLaunchKernelGGL((k_trsv_wide<D, LOWER, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
                            M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(),
                            M.rowid.as<int32_t>(), L.d.as<D>(), w, v, logR, 1, direct ? blk_tmp.as<D>() : (D *)nullptr,
@@ -1660,6 +1671,7 @@ class Engine : public EngineBase {
           ++count;
           continue;
         }
+        tally(KF_TRSV_BAND_P);
         hipLaunchKernelGGL((k_trsv_band_p<D, LOWER>), dim3((unsigned)(g1 - g0) + extra), dim3(1024), 0, st, g0,
                            M.wg_slot.as<int32_t>(), M.ptr.as<int32_t>(),
                            M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(), M.srcslot.as<int32_t>(),
@@ -1673,6 +1685,7 @@ class Engine : public EngineBase {
         ++count;
         continue;
       }
+      tally(KF_TRSV_BAND);
       hipLaunchKernelGGL((k_trsv_band<D, LOWER>), dim3((unsigned)(g1 - g0)), dim3(1024), 0, st, g0,
                          M.wg_grp_ptr.as<int32_t>(), M.grp_slot_ptr.as<int32_t>(), M.ptr.as<int32_t>(),
                          M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(), M.srcslot.as<int32_t>(),
@@ -1708,10 +1721,12 @@ class Engine : public EngineBase {
     }
     auto kern = nct == 1 ? k_top_gemm<1> : (nct == 2 ? k_top_gemm<2> : (nct == 3 ? k_top_gemm<3> : k_top_gemm<4>));
     const bool fused_sum = top_last_arriver && nks > 1 && tiles <= kTopGemmTilesMax && gemm_cnt.p;
+    tally(KF_TOP_GEMM);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nks), dim3(1024), kTopGemmLds, st, nt, nt, kper, G, lda, X, rowmap,
                        Out, gemm_part.as<double>(), pad, fused_sum ? gemm_cnt.as<unsigned>() : (unsigned *)nullptr);
     ++count;
     if (nks > 1 && !fused_sum) {
+      tally(KF_TOP_REDUCE);
       hipLaunchKernelGGL(k_top_reduce, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, nt, nks,
                          (const double *)gemm_part.as<double>(), pad, rowmap, Out, nct);
       ++count;
@@ -1725,6 +1740,7 @@ class Engine : public EngineBase {
       const size_t b = (size_t)L.top_bandL;
       const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
       const int nt = (int)L.top_n;
+      tally(KF_TRSV_WIDE);
       hipLaunchKernelGGL((k_trsv_wide<double, true, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
                          M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(),
                          M.rowid.as<int32_t>(), L.d.as<double>(), L.w.as<double>(), L.v.as<double>(), logR, 1,
@@ -1737,6 +1753,7 @@ class Engine : public EngineBase {
         return;
       }
       ++count;
+      tally(top_gemm == 1 ? KF_STRIP_GEMM : KF_STRIP_GEMM4);
       if (top_gemm == 1)
         hipLaunchKernelGGL(k_strip_gemm_d<4>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, ktop, L.topG.as<double>(), ktop,
                            (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0, L.v.as<double>());
@@ -1788,6 +1805,7 @@ class Engine : public EngineBase {
         return true;
       }
       ++count;
+      tally(KF_STRIP_GEMM4);
       hipLaunchKernelGGL(k_strip_gemm4_d<2>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, kt, tailG.as<double>(), kt,
                          (const double *)cin, (const int32_t *)nullptr, (double *)zout);
       return true;
@@ -1856,6 +1874,7 @@ class Engine : public EngineBase {
         const int nslc = (ncols + nct - 1) / nct;
         const unsigned grid = (unsigned)(((g1 - g0 + 7) / 8) * 8 * nslc) + 4 * extra;
         auto kct = nct == 4 ? k_band_ct<LOWER, 4> : (nct == 2 ? k_band_ct<LOWER, 2> : k_band_ct<LOWER, 1>);
+        tally(nct == 4 ? KF_BAND_CT4 : (nct == 2 ? KF_BAND_CT2 : KF_BAND_CT1));
         hipLaunchKernelGGL(kct, dim3(grid), dim3(256), ct_lds_bytes(nct), st, g0,
                            M.wg_grp_ptr.as<int32_t>(), M.ct_desc.as<int32_t>(), M.ptr.as<int32_t>(), M.split.as<int32_t>(),
                            M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(), L.w.as<double>(),
@@ -1870,6 +1889,7 @@ class Engine : public EngineBase {
         const int32_t lds_black = std::max(1, M.us_band_nbk[band]);
         const size_t lds2 = us_lds_bytes(lds_black, own_cap2);
         if (lds2 <= 160 * 1024) {
+          tally(KF_BAND_US);
           hipLaunchKernelGGL(k_band_us, dim3((unsigned)(g1 - g0)), dim3(1024), lds2, st, M.us_band_c0[band], M.us_desc.as<int32_t>(),
                              M.us_rowid.as<int32_t>(), M.us_oslot.as<int32_t>(), M.us_mptr.as<int32_t>(), M.us_mcol.as<int32_t>(),
                              M.us_mval.as<double>(), M.us_own_val.as<double>(), M.us_own_src.as<uint8_t>(), M.us_own_rptr.as<uint16_t>(),
@@ -1898,12 +1918,14 @@ class Engine : public EngineBase {
           RowSkip a_rs = rs;
           void *args[] = {&a_c0, &a_desc, &a_rowid, &a_oslot, &a_eb, &a_ew, &a_ec, &a_ev, &a_et, &a_ov, &a_os, &a_or, &a_ol, &a_w,
                           &a_dep, &a_own, &a_rp, &a_fl, &a_rs};
+          tally(KF_BAND_LS);
           HIP_OK(hipLaunchKernel(kls, dim3((unsigned)(g1 - g0)), dim3(1024), args, lds2, st));
           return;
         }
       }
       if (cs_mode && (nsl < 4 || g1 - g0 <= cs_max_wgs || (cs_sparse && M.cd_sparse)) && fits) {
         auto kcs = M.cd_sparse ? k_band_cs<LOWER, true> : k_band_cs<LOWER, false>;
+        tally(M.cd_sparse ? KF_BAND_CS_SPARSE : KF_BAND_CS);
         hipLaunchKernelGGL(kcs, dim3((unsigned)((g1 - g0) * nsl) + 4 * extra), dim3(256), cs_lds_bytes(M.cd_sparse, M.own_cap), st, g0,
                            M.wg_grp_ptr.as<int32_t>(), (with_f ? M.f_desc : M.cd_desc).template as<int32_t>(), M.ptr.as<int32_t>(),
                            M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(),
@@ -1915,6 +1937,7 @@ class Engine : public EngineBase {
         return;
       }
       auto kern = M.cd_sparse ? k_band_cd<LOWER, true> : k_band_cd<LOWER, false>;
+      tally(M.cd_sparse ? KF_BAND_CD_SPARSE : KF_BAND_CD);
       hipLaunchKernelGGL(kern, dim3((unsigned)(g1 - g0) + extra), dim3(1024), lds, st, g0,
                          M.wg_grp_ptr.as<int32_t>(), (with_f ? M.f_desc : M.cd_desc).template as<int32_t>(), M.ptr.as<int32_t>(),
                          M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(),
@@ -1930,6 +1953,7 @@ class Engine : public EngineBase {
       if (ct_mode && M.ct_on && !M.cd_sparse) {  // coefficient tiles (round 4): 16-column slices at every batch width
         const size_t rows = (size_t)((band_opt.cd_rows + 31) & ~(int64_t)31);
         const size_t ldsz = rows * (2 * 16 + 3) * sizeof(double) + rows * 3 * sizeof(int32_t) + 32 * sizeof(int32_t);
+        tally(KF_BAND_CT_Z);
         hipLaunchKernelGGL(k_band_ct_z<LOWER>, dim3((unsigned)((g1 - g0) * nslz)), dim3(256), ldsz, st, g0, M.wg_grp_ptr.as<int32_t>(),
                            M.ct_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(),
                            M.tinv.as<double>(), M.ct_sptr.as<int32_t>(), M.ct_src.as<int32_t>(), M.ct_coef.as<double>(), pre ? 0 : 1,
@@ -1938,6 +1962,7 @@ class Engine : public EngineBase {
       }
       if (M.cd_sparse) {  // sparse-own components (round 4): 16-column slices at every batch width
         const int32_t rows = (int32_t)band_opt.cd_sparse_rows;
+        tally(KF_BAND_CS_Z);
         hipLaunchKernelGGL((k_band_cs_z<LOWER, true>), dim3((unsigned)((g1 - g0) * nslz)), dim3(256), csz_lds_bytes(true, M.own_cap), st, g0,
                            M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
                            L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
@@ -1947,6 +1972,7 @@ class Engine : public EngineBase {
       }
       if (cs_mode && nslz < 4 && (int64_t)(g1 - g0) * nslz < (1LL << 30)) {  // a narrow batch: only the slices it has
         const int32_t rows = (int32_t)((band_opt.cd_rows + 31) & ~(int64_t)31);
+        tally(KF_BAND_CS_Z);
         hipLaunchKernelGGL((k_band_cs_z<LOWER, false>), dim3((unsigned)((g1 - g0) * nslz)), dim3(256), csz_lds_bytes(false, 0), st, g0,
                            M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
                            L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
@@ -1954,6 +1980,7 @@ class Engine : public EngineBase {
                            (const uint16_t *)nullptr, (const uint8_t *)nullptr, lu);
         return;
       }
+      tally(KF_BAND_CD_Z);
       hipLaunchKernelGGL(k_band_cd_z<LOWER>, dim3((unsigned)(g1 - g0)), dim3(1024), cd_lds_bytes_z(), st, g0, M.wg_grp_ptr.as<int32_t>(),
                          M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(),
                          M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(), pre ? 0 : 1,
@@ -1976,6 +2003,7 @@ class Engine : public EngineBase {
     const double *Are = A.as<double>(), *Aim = Are + plane_elems(rows_total, lda);
     const dim3 grid((unsigned)((rows_total + 15) / 16), ((2u << logR) + 15) / 16);
     double *t1 = zt1.as<double>(), *t2 = zt2.as<double>();
+    tally(KF_DENSE_GEMM, 2), tally(KF_ZCOMBINE);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, rows_total, rows_valid, kend, tri, Are, lda,
                        (const double *)X, logR + 1, (const int32_t *)nullptr, t1, (const double *)nullptr, (double *)nullptr);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, rows_total, rows_valid, kend, tri, Aim, lda,
@@ -1991,6 +2019,7 @@ class Engine : public EngineBase {
     const unsigned pairs = (unsigned)(((nb + 15) / 16 + 1) / 2);
     const dim3 grid(pairs, ((2u << logR) + 15) / 16);
     double *t1 = zt1.as<double>(), *t2 = zt2.as<double>();
+    tally(KF_TRI_GEMM, 2), tally(KF_ZCOMBINE);
     hipLaunchKernelGGL(k_tri_gemm_d<16>, grid, dim3(1024), 0, st, nb, Are, lda, (const double *)X, logR + 1,
                        (const int32_t *)nullptr, t1, (const double *)nullptr, (double *)nullptr);
     hipLaunchKernelGGL(k_tri_gemm_d<16>, grid, dim3(1024), 0, st, nb, Aim, lda, (const double *)X, logR + 1,
@@ -2025,6 +2054,7 @@ class Engine : public EngineBase {
       if (A.tl_nblk > 0 && A.tl_nblk < spmm_split_blocks && logR == 6 && spmm_split) {
         auto k4 = A.tl_rb == 2 ? (nct == 1 ? k_spmm_tile4<2, 1> : nct == 2 ? k_spmm_tile4<2, 2> : nct == 3 ? k_spmm_tile4<2, 3> : k_spmm_tile4<2, 4>)
                                : (nct == 1 ? k_spmm_tile4<1, 1> : nct == 2 ? k_spmm_tile4<1, 2> : nct == 3 ? k_spmm_tile4<1, 3> : k_spmm_tile4<1, 4>);
+        tally(A.tl_rb == 2 ? KF_SPMM_TILE4_RB2 : KF_SPMM_TILE4_RB1);
         hipLaunchKernelGGL(k4, dim3((unsigned)A.tl_nblk), dim3(256), 0, st, nrows, A.tl_nblk, A.tl_gptr.as<int32_t>(),
                            A.tl_ucol.as<int32_t>(), A.tl_coef.as<double>(), (const double *)x, bin, ldb, nrhs, L.p.as<int32_t>(),
                            L.s.as<double>(), roff, out);
@@ -2034,6 +2064,7 @@ class Engine : public EngineBase {
         const unsigned grid = (unsigned)std::min<int64_t>((A.tl_nblk + 3) / 4, 256 * 16);
         auto k1 = A.tl_rb == 2 ? (nct == 1 ? k_spmm_tile<2, 1> : nct == 2 ? k_spmm_tile<2, 2> : nct == 3 ? k_spmm_tile<2, 3> : k_spmm_tile<2, 4>)
                                : (nct == 1 ? k_spmm_tile<1, 1> : nct == 2 ? k_spmm_tile<1, 2> : nct == 3 ? k_spmm_tile<1, 3> : k_spmm_tile<1, 4>);
+        tally(A.tl_rb == 2 ? KF_SPMM_TILE_RB2 : KF_SPMM_TILE_RB1);
         hipLaunchKernelGGL(k1, dim3(grid), dim3(256), 0, st, nrows, A.tl_nblk, A.tl_gptr.as<int32_t>(),
                            A.tl_ucol.as<int32_t>(), A.tl_coef.as<double>(), (const double *)x, bin, ldb, nrhs, L.p.as<int32_t>(),
                            L.s.as<double>(), roff, out);
@@ -2044,6 +2075,7 @@ class Engine : public EngineBase {
       if (A.tl_nblk > 0 && logR == 6) {  // complex coupling block on coefficient tiles: one 16-column slice per grid row
         const unsigned gx = (unsigned)std::min<int64_t>((A.tl_nblk + 3) / 4, 256 * 16);
         const unsigned gy = (unsigned)std::min(4, (act_cols + 15) / 16);
+        tally(KF_SPMM_TILE_Z);
         hipLaunchKernelGGL(k_spmm_tile_z, dim3(gx, gy), dim3(256), 0, st, nrows, A.tl_nblk, A.tl_gptr.as<int32_t>(),
                            A.tl_ucol.as<int32_t>(), A.tl_coef.as<double>(), (const cplx *)x, bin, ldb, nrhs, L.p.as<int32_t>(),
                            L.s.as<double>(), roff, (cplx *)out);
@@ -2053,16 +2085,19 @@ class Engine : public EngineBase {
     // a narrow batch in the 64-column arena: 64 / R rows per wave (R = 16 or 32 lanes per row)
     if (logR == 6 && narrow_spmm && act_cols <= 32) {
       const int lr = act_cols <= 16 ? 4 : 5;
+      tally(KF_SPMM_EPI_NARROW);
       hipLaunchKernelGGL((k_spmm_epi_narrow<D>), dim3(grid_for(nrows, lr)), dim3(256), 0, st, nrows, A.ptr.as<int32_t>(),
                          A.col.as<int32_t>(), A.val.as<D>(), x, bin, ldb, nrhs, L.p.as<int32_t>(), L.s.as<double>(), roff, out, lr);
       return;
     }
+    tally(KF_SPMM_EPI);
     hipLaunchKernelGGL((k_spmm_epi<D>), dim3(grid_for(nrows, logR)), dim3(256), 0, st, nrows, A.ptr.as<int32_t>(),
                        A.col.as<int32_t>(), A.val.as<D>(), x, bin, ldb, nrhs, L.p.as<int32_t>(), L.s.as<double>(), roff, out,
                        logR);
   }
 
   void launch_s7_list(hipStream_t st, const DevLevel &L, const D *v, int64_t first, int64_t cnt, OutP yout, int64_t ldy, int nrhs) {
+    tally(KF_SCATTER_SCALE_LIST);
     hipLaunchKernelGGL((k_scatter_scale_list<D>), dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (cnt + 15) / 16))), dim3(256), 0,
                        st, v, L.qinv.as<int32_t>(), L.t.as<double>(), L.s7_list.as<int32_t>() + first, cnt, yout, ldy, nrhs);
   }
@@ -2092,12 +2127,14 @@ class Engine : public EngineBase {
     const bool last = (l + 1 == lv.size());
     // S1 (:359, :402) fused into the L solve that follows it (kernels FirstL): the R = 64 band pipeline only
     const bool fuse_s1 = fuse_gather && logR == 6 && band_pipe && m > 0;
+    cur_level = (int)l;
     const FL fl{bin, ldb, nrhs, L.p.as<int32_t>(), L.s.as<double>()};
     const bool fuse_f_lv = fuse_s1 && L.L.f_fused;  // S5 fused as well (level with thin F rows, all-component L plan)
     const bool fuse_s7_lv = fuse_out && logR == 6 && m > 0 && L.s7_n >= 0 && s7_kernel_ok(L);
     int64_t early_rows = 0;  // rows of the S7 list already sent out on the side stream
     int64_t c0 = count;
     if (m && !fuse_s1) {  // S1  :359
+      tally(KF_GATHER_SCALE);
       hipLaunchKernelGGL((k_gather_scale<D>), dim3(grid_for(m, logR)), dim3(256), 0, st, bin, ldb, nrhs,
                          L.p.as<int32_t>(), L.s.as<double>(), m, w, logR);
       ++count;
@@ -2117,10 +2154,11 @@ class Engine : public EngineBase {
         launch_dense(st, w + m * R, v + m * R, logR, rank, count);  // :371-381
         mark(l, 4, c0, count);
       } else if ((int64_t)l + 1 == tail_level && logR == 6 && (!host.has_dense || eff_rank(rank) == dn.rank) &&  // (the rank it was built with)
-                 launch_tail(st, w + m * R, v + m * R, count)) {
+                 (cur_level = (int)l + 1, launch_tail(st, w + m * R, v + m * R, count))) {
         mark(l + 1, 4, c0, count);  // (levels l+1 ... and the dense block as one product)
       } else
         enqueue_level(st, l + 1, in_direct(w + m * R), R, out_direct(v + m * R), R, (int)R, logR, rank, count);  // :383-388
+      cur_level = (int)l;
       // S7 of the child's rows (:411) needs nothing of this level's second solve: it leaves now, on the side stream, beside
       // S5 / S6 (whose component bands are latency-bound and leave the memory system room); joined at the end of the level
       if (fuse_s7_lv && list_early && L.s7_child > 0) {
@@ -2140,6 +2178,7 @@ class Engine : public EngineBase {
           launch_spmm(st, L.F, m, v + m * R, bin, ldb, nrhs, L, (int64_t)0, w, logR);
           ++count;
         } else if (!fuse_s1) {
+          tally(KF_GATHER_SCALE);
           hipLaunchKernelGGL((k_gather_scale<D>), dim3(grid_for(m, logR)), dim3(256), 0, st, bin, ldb, nrhs,
                              L.p.as<int32_t>(), L.s.as<double>(), m, w, logR);
           ++count;
@@ -2164,6 +2203,7 @@ class Engine : public EngineBase {
       }
       if (early_rows) side_join(st, l);
     } else {
+      tally(KF_SCATTER_SCALE);
       hipLaunchKernelGGL((k_scatter_scale<D>), dim3(grid_for(n, logR)), dim3(256), 0, st, v, L.qinv.as<int32_t>(),
                          L.t.as<double>(), n, yout, ldy, nrhs, logR);
       ++count;
@@ -2241,7 +2281,9 @@ class Engine : public EngineBase {
     const int64_t R = 1LL << logR;
     D *w = L.w.as<D>(), *v = L.v.as<D>(), *g = L.pg.as<D>(), *cy = L.pc.as<D>(), *r = L.pr.as<D>();
     const bool last = (l + 1 == lv.size());
+    cur_level = (int)l;
     // g = b[q] / t[q], all n rows  (:76, :97)
+    tally(KF_PROD);
     hipLaunchKernelGGL((k_gather_div<D>), dim3(grid_for(n, logR)), dim3(256), 0, st, bin, ldb, nrhs, L.q.as<int32_t>(),
                        L.t.as<double>(), n, g, logR);
     ++count;
@@ -2250,9 +2292,11 @@ class Engine : public EngineBase {
         launch_dense_mul(st, g + m * R, cy + m * R, logR, rank, count);
       else
         enqueue_prod_level(st, l + 1, in_direct(g + m * R), R, out_direct(cy + m * R), R, (int)R, logR, rank, count);
+      cur_level = (int)l;
     }
     if (m) {
       // cy[0:m] = D (U + I) g   (:101-103);  r[0:m] = (L + I) cy   (:106-108)
+      tally(KF_PROD, 2);
       hipLaunchKernelGGL((k_prod_rows<D, true>), dim3(grid_for(m, logR)), dim3(256), 0, st, m, L.U.ptr.as<int32_t>(),
                          L.U.col.as<int32_t>(), L.U.val.as<D>(), L.U.rowid.as<int32_t>(), (const D *)g, L.d.as<D>(), cy,
                          logR);
@@ -2261,10 +2305,12 @@ class Engine : public EngineBase {
                          (const D *)nullptr, r, logR);
       count += 2;
       if (L.F_ncols) {  // w = F g[m:n]; r += w   (:112-115)
+        tally(KF_PROD);
         hipLaunchKernelGGL((k_spmm_prod<D, 0>), dim3(grid_for(m, logR)), dim3(256), 0, st, m, L.F.ptr.as<int32_t>(),
                            L.F.col.as<int32_t>(), L.F.val.as<D>(), (const D *)(g + m * R), w, r, (const D *)nullptr, logR);
         ++count;
       } else if (nm) {  // no F: the reference's y(1:m) still holds D(U+I)g when the solve below reads it (:121)
+        tally(KF_PROD);
         hipLaunchKernelGGL((k_vec_op<D>), dim3(vec_grid(m * R)), dim3(256), 0, st, 1, m, (int)R, w, R, (const D *)cy, R,
                            (const D *)nullptr, (int64_t)0);
         ++count;
@@ -2273,6 +2319,7 @@ class Engine : public EngineBase {
     if (nm) {
       if (m) {
         launch_ldu(st, L, logR, count);  // v = (LDU)^{-1} w   (:121)
+        tally(KF_PROD);
         hipLaunchKernelGGL((k_vec_op<D>), dim3(vec_grid(m * R)), dim3(256), 0, st, 2, m, (int)R, v, R, (const D *)g, R,
                            (const D *)nullptr, (int64_t)0);  // v += g   (:123)
         ++count;
@@ -2281,10 +2328,12 @@ class Engine : public EngineBase {
         // transposed product of a level WITHOUT F: the reference's F.multiply_t_low writes F.ncols() = 0
         // entries (prec_prod.hpp:223), so work[m:n] still holds the permuted input when y[m:n] is added
         // (:225) -- reproduced literally (no factorization yields such a level; synthetic tests do)
+        tally(KF_PROD);
         hipLaunchKernelGGL((k_vec_op<D>), dim3(vec_grid(nm * R)), dim3(256), 0, st, 3, nm, (int)R, r + m * R, R,
                            (const D *)(g + m * R), R, (const D *)(cy + m * R), R);
       } else {
         // r[m:n] = E v + cy[m:n]   (:125-127)
+        tally(KF_PROD);
         hipLaunchKernelGGL((k_spmm_prod<D, 1>), dim3(grid_for(nm, logR)), dim3(256), 0, st, nm, L.E.ptr.as<int32_t>(),
                            L.E.col.as<int32_t>(), L.E.val.as<D>(), (const D *)v, r + m * R, (D *)nullptr,
                            (const D *)(cy + m * R), logR);
@@ -2292,6 +2341,7 @@ class Engine : public EngineBase {
       ++count;
     }
     // y = r[p_inv] / s   (:132)
+    tally(KF_PROD);
     hipLaunchKernelGGL((k_scatter_div<D>), dim3(grid_for(n, logR)), dim3(256), 0, st, (const D *)r, L.pinv.as<int32_t>(),
                        L.s.as<double>(), n, yout, ldy, nrhs, logR);
     ++count;
@@ -2309,6 +2359,7 @@ class Engine : public EngineBase {
                         int kind = 0, D *const *slots = nullptr, int tfirst = 0, int tstride = 1) {
     int64_t count = 0;
     cur_map.clear();
+    cur_census.fill(0);
     for (int64_t c0 = 64 * (int64_t)tfirst; c0 < nrhs; c0 += 64 * (int64_t)tstride) {
       const int64_t nc = std::min<int64_t>(64, nrhs - c0);
       const int logR = pick_logR(nc);
@@ -2362,12 +2413,15 @@ class Engine : public EngineBase {
         HIP_OK(hipEventRecord(ev_join[(size_t)(k - 1)], Tw.stream));
         HIP_OK(hipStreamWaitEvent(st, ev_join[(size_t)(k - 1)], 0));
         total += Tw.last_launches;
+        for (size_t f = 0; f < last_census.size(); ++f) last_census[f] += Tw.last_census[f];
       }
       last_launches = total;
+      census_seq = ++census_clock();
       if (kind == 0) apply_nsp(dX, ldx, nrhs, st);
       return;
     }
     launch_part(dB, ldb, dX, ldx, nrhs, rank, st, kind, 0, 1);
+    census_seq = ++census_clock();
     if (kind == 0) apply_nsp(dX, ldx, nrhs, st);
   }
 
@@ -2587,8 +2641,10 @@ class Engine : public EngineBase {
     if (!use_graph) {
       last_launches = enqueue_apply(st, dB, ldb, dX, ldx, nrhs, rank, kind, nullptr, tfirst, tstride);
       last_map = cur_map;
+      last_census = cur_census;
       return;
     }
+    std::lock_guard<std::mutex> graph_lock(graph_mutex());
     GraphKey key{ldb, ldx, nrhs, host.has_dense ? eff_rank(rank) : 0, kind, tfirst, tstride};
     auto it = graphs.find(key);
     if (it == graphs.end()) {
@@ -2609,6 +2665,7 @@ class Engine : public EngineBase {
       try {
         ge.launches = enqueue_apply(stream, dB, ldb, dX, ldx, nrhs, rank, kind, (D *const *)ge.slots, tfirst, tstride);
         ge.map = cur_map;
+        ge.census = cur_census;
       } catch (...) {
         hipGraph_t g = nullptr;
         (void)hipStreamEndCapture(stream, &g);
@@ -2624,6 +2681,7 @@ class Engine : public EngineBase {
     it->second.stamp = ++clock;
     last_launches = it->second.launches;
     last_map = it->second.map;
+    last_census = it->second.census;
     // hand this call's pointers to the graph: a stream-ordered 16-byte copy from a pinned ring slot
     if (!io_ring) HIP_OK(hipHostMalloc((void **)&io_ring, kIoRing * 2 * sizeof(void *), hipHostMallocDefault));
     if (io_next && io_next % kIoRing == 0) HIP_OK(hipStreamSynchronize(st));  // never overtake a pending slot
@@ -3360,6 +3418,12 @@ class Engine : public EngineBase {
     o[14] = bytes_inverses + bytes_top + bytes_tail;
     o[15] = capture_ms;
   }
+  // of this handle's last batched apply, whichever of its two engines ran it
+  int kernel_census(int32_t *o, int cap) const {
+    const Engine<T> &E = (adj && adj->census_seq > census_seq) ? *adj : *this;
+    for (int i = 0; i < cap && i < (int)E.last_census.size(); ++i) o[i] = E.last_census[(size_t)i];
+    return (int)E.last_census.size();
+  }
   int launch_map(int32_t *o, int cap) const {
     for (int i = 0; i < cap && i < (int)last_map.size(); ++i) o[i] = last_map[(size_t)i];
     return (int)last_map.size();
@@ -3439,6 +3503,7 @@ void Engine<double>::launch_dense(hipStream_t st, const double *cin, double *zou
   const unsigned g = (unsigned)((nd + 15) / 16);  // one workgroup per 16-row strip (4 waves split K)
   double *tmp = dn.tmp.as<double>();
   if (dn.lup) {  // LUP::solve (LUP.hpp:141-152): ?getrs, here one product with the explicit inverse; rank is ignored
+    tally(KF_DENSE_GEMM);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, nd, nd, 0,
                        dn.QH.as<double>(), nd, cin, logR, (const int32_t *)nullptr, zout, (const double *)nullptr,
                        (double *)nullptr);
@@ -3446,6 +3511,7 @@ void Engine<double>::launch_dense(hipStream_t st, const double *cin, double *zou
     return;
   }
   if (dn.symm) {  // SYEIG::solve (SYEIG.hpp:181-200): z = V(:,to(1:rk)) diag(1/w) V(:,to(1:rk))^H c
+    tally(KF_DENSE_GEMM, 2);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, nd, 0,
                        dn.QH.as<double>(), nd, cin, logR, (const int32_t *)nullptr, tmp, (const double *)nullptr,
                        (double *)nullptr);
@@ -3457,6 +3523,7 @@ void Engine<double>::launch_dense(hipStream_t st, const double *cin, double *zou
   }
   if (adjoint) {  // QRCP::_solve_t (QRCP.hpp:413-452): z = Q(:,1:rk) R(1:rk,1:rk)^{-H} (P^T c)(1:rk)
     double *tmp2 = dn.tmp2.as<double>();
+    tally(KF_ROW_GATHER), tally(KF_DENSE_GEMM, 2);
     hipLaunchKernelGGL((k_row_gather<double>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
                        (int64_t)nd, tmp2, logR);
     // T1[i] = sum_{k<=i} conj(Rinv(k,i)) c[jpvt[k]], i < rk (rows >= rk come out as zeros)
@@ -3470,6 +3537,7 @@ void Engine<double>::launch_dense(hipStream_t st, const double *cin, double *zou
     return;
   }
   // T1 = Q^H(1:rk, :) c   (rows >= rk come out as zeros and are never read)
+  tally(KF_DENSE_GEMM, 2);
   hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, nd, 0, dn.QH.as<double>(), nd, cin, logR,
                      (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
   // z[jpvt[i]] = sum_{k>=i} Rinv(i,k) T1[k], i < rk; zero rows beyond rk
@@ -3493,6 +3561,7 @@ void Engine<zdouble>::launch_dense(hipStream_t st, const cplx *cin, cplx *zout, 
   }
   if (adjoint) {
     cplx *tmp2 = dn.tmp2.as<cplx>();
+    tally(KF_ROW_GATHER);
     hipLaunchKernelGGL((k_row_gather<cplx>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
                        (int64_t)nd, tmp2, logR);
     ++count;
@@ -3513,12 +3582,14 @@ void Engine<double>::launch_dense_mul(hipStream_t st, const double *cin, double 
   const dim3 grid(g, ((1u << logR) + 15) / 16);
   double *tmp = dn.tmp.as<double>();
   if (dn.lup) {  // LUP::multiply (LUP.hpp:181-188): z = A c (adjoint engine: A^H c)
+    tally(KF_DENSE_GEMM);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, nd, nd, 0, dn.Rm.as<double>(), nd, cin, logR,
                        (const int32_t *)nullptr, zout, (const double *)nullptr, (double *)nullptr);
     ++count;
     return;
   }
   if (dn.symm) {  // SYEIG::multiply (SYEIG.hpp:256-273): z = V(:,to(1:rk)) diag(w) V(:,to(1:rk))^H c
+    tally(KF_DENSE_GEMM, 2);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, nd, 0, dn.Rm.as<double>(), nd, cin, logR,
                        (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, nd, rk, 0, dn.Qm.as<double>(), nd, (const double *)tmp,
@@ -3527,6 +3598,7 @@ void Engine<double>::launch_dense_mul(hipStream_t st, const double *cin, double 
     return;
   }
   if (adjoint) {
+    tally(KF_DENSE_GEMM, 2);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, nd, 0, dn.QH.as<double>(), nd, cin, logR,
                        (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
     hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, rk, 2, dn.Rm.as<double>(), nd, (const double *)tmp,
@@ -3535,6 +3607,7 @@ void Engine<double>::launch_dense_mul(hipStream_t st, const double *cin, double 
     return;
   }
   double *tmp2 = dn.tmp2.as<double>();
+  tally(KF_ROW_GATHER), tally(KF_DENSE_GEMM, 2);
   hipLaunchKernelGGL((k_row_gather<double>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
                      (int64_t)nd, tmp2, logR);
   hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, rk, 1, dn.Rm.as<double>(), nd, (const double *)tmp2,
@@ -3563,6 +3636,7 @@ void Engine<zdouble>::launch_dense_mul(hipStream_t st, const cplx *cin, cplx *zo
     return;
   }
   cplx *tmp2 = dn.tmp2.as<cplx>();
+  tally(KF_ROW_GATHER);
   hipLaunchKernelGGL((k_row_gather<cplx>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
                      (int64_t)nd, tmp2, logR);
   ++count;
@@ -3579,6 +3653,8 @@ void Engine<double>::launch_dense_block(hipStream_t st, const DevLevel &L, const
   const int32_t r0 = M.blk_slot0[(size_t)q], r1 = M.blk_slot1[(size_t)q], nb = r1 - r0;
   double *x = LOWER ? L.w.as<double>() : L.v.as<double>();
   double *tb = blk_tmp.as<double>();
+  tally(KF_TRI_GEMM);
+  if (!rhs_ready) tally(KF_THIN_UPDATE);
   if (!rhs_ready)  // (the first block of a band gets its right-hand side from the prefix pass)
     hipLaunchKernelGGL((k_thin_update<double>), dim3(grid_for(nb, logR)), dim3(256), 0, st, r0, r1, M.ptr.as<int32_t>(),
                        M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.srcslot.as<int32_t>(),
@@ -3608,6 +3684,7 @@ void Engine<zdouble>::launch_dense_block(hipStream_t st, const DevLevel &L, cons
   cplx *x = LOWER ? L.w.as<cplx>() : L.v.as<cplx>();
   cplx *tb = blk_tmp.as<cplx>();
   if (!rhs_ready) {
+    tally(KF_THIN_UPDATE);
     hipLaunchKernelGGL((k_thin_update<cplx>), dim3(grid_for(nb, logR)), dim3(256), 0, st, r0, r1, M.ptr.as<int32_t>(),
                        M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<cplx>(), M.srcslot.as<int32_t>(),
                        M.rowid.as<int32_t>(), (const cplx *)x, tb, logR);
@@ -4021,6 +4098,15 @@ int64_t hifamd_schur_rank(HifAmdHdl h) { QUERY(q_schur_rank(ENG_D), q_schur_rank
 int hifamd_launch_map(HifAmdHdl h, int32_t *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;
   return h->vt == HIFAMD_D ? ENG_D->launch_map(out, cap) : ENG_Z->launch_map(out, cap);
+}
+int hifamd_kernel_census(HifAmdHdl h, int32_t *out, int cap) {
+  if (!h || !h->eng || (cap > 0 && !out)) return -1;
+  const bool fin = h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized;
+  if (!fin) return 0;
+  return h->vt == HIFAMD_D ? ENG_D->kernel_census(out, cap) : ENG_Z->kernel_census(out, cap);
+}
+const char *hifamd_kernel_family_name(int family) {
+  return (family >= 0 && family < hifamd::KF_COUNT) ? hifamd::kFamilyNames[family] : nullptr;
 }
 int hifamd_level_stats(HifAmdHdl h, int level, double *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;

@@ -700,7 +700,10 @@ BandPlan plan_bands_cd(const Csr<T> &A, const Schedule &S, bool lower, const Ban
       // (sparse plans bag everything up to half a component; a pass with few rows gets smaller bags, so that its
       //  gathers are spread over the whole chip instead of a few dozen workgroups)
       const size_t small = sparse ? (size_t)opt.cd_rows / 2 : 8;
-      const size_t bagcap = sparse ? std::max<size_t>(16, std::min<size_t>((size_t)opt.cd_rows, rows.size() / 256)) : 32;
+      // (never more rows than a component may have: with fewer than 32 rows per component the 32-row bags were refused
+      //  by check_band_plan as oversized components, "internal error: band plan ... component size")
+      const size_t bagcap = std::min<size_t>((size_t)opt.cd_rows,
+                                             sparse ? std::max<size_t>(16, std::min<size_t>((size_t)opt.cd_rows, rows.size() / 256)) : 32);
       int64_t bagw = 0;
       for (auto &r : crow) {
         if (r.size() > small) {

@@ -237,6 +237,19 @@ class HIF:
         lib().hifamd_launch_map(self._h, _p(o), int(k))
         return [(int(v) // 16, int(v) % 16) for v in o[:k]]
 
+    def kernel_census(self, lower=False):
+        """{kernel family: launches} of the last batched apply, forwards or transposed, summed over its lanes
+        (hifamd_kernel_census).  lower=True: only the launches on a level >= 1.  Every family is present; the families and
+        their order are the library's (hifamd_kernel_family_name)."""
+        k = lib().hifamd_kernel_census(self._h, None, 0)
+        if k <= 0:
+            return {}
+        o = np.zeros(k, dtype=np.int32)
+        lib().hifamd_kernel_census(self._h, _p(o), int(k))
+        nf = k // 2
+        names = [lib().hifamd_kernel_family_name(f).decode() for f in range(nf)]
+        return {name: int(o[(nf if lower else 0) + f]) for f, name in enumerate(names)}
+
     def level_bytes(self, nrhs):
         """B_alg(nrhs) of SURVEY 8(d) level by level and stage by stage: {level: {stage: bytes}} with the stage codes of
         launch_map(); the dense block's bytes sit at stage 4 of the level that owns it."""

@@ -166,6 +166,16 @@ int hifamd_level_stats(HifAmdHdl h, int level, double *out, int cap);
  * E, 4 dense block / tail operator, 5 S5 product with F, 6 second LDU solve (with the fused S5 / S7), 7 S7 scatter
  * (prec_solve.hpp:359-411).  Returns the number of launches; writes min(cap, that). */
 int hifamd_launch_map(HifAmdHdl h, int32_t *out, int cap);
+/* Which kernels the LAST batched apply launched, by kernel family (for tests: does a shape or a setting reach the kernel it
+ * is meant to reach?).  Host-side bookkeeping at the launch sites, kept with the graph of the shape like the launch map and
+ * summed over the lanes of a batch wider than 64 columns; of the forward or the adjoint apply, whichever ran last.
+ * out[f] = launches of family f on every level, out[N + f] = those of them on a level >= 1 (the tail operator counts for
+ * the first level it replaces), f < N; hifamd_kernel_family_name(f) names the families in order ("band_ct1", "band_ct2",
+ * ..., NULL from f = N on).  A family is what the dispatch distinguishes: a kernel, and where the planner or a
+ * HIFIR_AMD_* switch chooses between instantiations, the instantiation.  Returns 2 N (writes min(cap, that)); 0 before
+ * hifamd_finalize, -1 for a NULL handle. */
+int hifamd_kernel_census(HifAmdHdl h, int32_t *out, int cap);
+const char *hifamd_kernel_family_name(int family);
 /* level schedule of one triangular factor (host-side analysis; usable without a GPU):
  * which = 0 (L_B) / 1 (U_B).  *nwf = number of wavefronts; if order != NULL it receives the m row
  * ids in processing order and wf_ptr (nwf+1 entries) the wavefront boundaries into it. */

@@ -42,6 +42,38 @@ def test_no_silent_fallback_without_gpu():
         M.solve(d["b"])  # not finalized -> HIFAMD_BAD_PREC, never a CPU result
 
 
+def test_kernel_census_without_an_apply():
+    """hifamd_kernel_census beside hifamd_launch_map: -1 for a NULL handle or a NULL array with room asked for, 0 before
+    hifamd_finalize (nothing was launched), and the family names are the engine's enum in order, distinct, NULL past the end."""
+    L = hifir_amd.lib()
+    out = np.zeros(128, dtype=np.int32)
+    p = out.ctypes.data_as(ctypes.c_void_p)
+    assert L.hifamd_kernel_census(None, p, 128) == -1 and L.hifamd_launch_map(None, p, 128) == -1
+    levels, _ = load_hier("p2d_5")
+    M = hifir_amd.HIF()
+    assert L.hifamd_kernel_census(M._h, None, 4) == -1
+    assert L.hifamd_kernel_census(M._h, p, 128) == 0 and L.hifamd_launch_map(M._h, p, 128) == 0
+    M.add_level(levels[0])
+    M.set_dense(levels[0]["dense"])
+    assert L.hifamd_kernel_census(M._h, p, 128) == 0 and not out.any()
+    assert M.kernel_census() == {} and M.kernel_census(lower=True) == {}
+    names = []
+    while L.hifamd_kernel_family_name(len(names)) is not None:
+        names.append(L.hifamd_kernel_family_name(len(names)).decode())
+    assert L.hifamd_kernel_family_name(-1) is None
+    assert len(names) == len(set(names)) >= 34 and 2 * len(names) <= 128
+    for fam in ("band_ct1", "band_ct2", "band_ct4", "band_cd", "band_cd_sparse", "band_cs", "band_cs_sparse", "band_us", "band_ls",
+                "band_ct_z", "band_cs_z", "band_cd_z", "trsv_band", "trsv_band_p", "trsv_wide", "thin_update", "spmm_tile_rb1",
+                "spmm_tile_rb2", "spmm_tile4_rb1", "spmm_tile4_rb2", "spmm_tile_z", "spmm_epi", "spmm_epi_narrow", "top_gemm",
+                "top_reduce", "strip_gemm", "strip_gemm4", "tri_gemm", "dense_gemm", "zcombine", "gather_scale", "scatter_scale",
+                "scatter_scale_list", "band_split_prefix"):
+        assert fam in names, fam
+    # the enum and the name table of engine.hip have the same length (a family added to one only would shift every name)
+    src = open(os.path.join(ROOT, "hifir_amd", "csrc", "engine.hip")).read()
+    enum = re.search(r"enum KernelFamily \{(.*?)KF_COUNT", src, flags=re.S).group(1)
+    assert [n[3:].lower() for n in re.findall(r"\bKF_[A-Z0-9_]+", enum)] == names
+
+
 def test_import_validation():
     levels, _ = load_hier("p2d_30")
     lv = dict(levels[0])

@@ -6,11 +6,10 @@ import os
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 import hifir_amd
 from oracle import orc
-from util import load_hier, relerr
+from util import forest_levels, load_hier, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -19,58 +18,8 @@ BASE_ENV = {"HIFIR_AMD_CD_SPARSE_MIN_ROWS": "0", "HIFIR_AMD_DENSE_BLOCK": "2048"
 SWITCHES = ("HIFIR_AMD_LS", "HIFIR_AMD_SKIP_ROWS", "HIFIR_AMD_LS_CHUNK")
 
 
-def _ccs(A):
-    A = sp.csc_matrix(A)
-    A.sort_indices()
-    return A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64)
-
-
-def _forest(m, leaves, spine, rng, lower):
-    """Strict triangle made of blocks of `leaves` rows without entries and `spine` rows that read 2-3 leaves and 0-2 earlier
-    spine rows of their block (now and then a row of an earlier block): components of ~leaves + spine rows, two thirds of
-    them pure sources -- the shape of level 0 of a PDE hierarchy, with more sources than one chunk holds."""
-    rows, cols = [], []
-    blk = leaves + spine
-    for b0 in range(0, m, blk):
-        nl = min(leaves, m - b0)
-        for i in range(b0 + nl, min(m, b0 + blk)):
-            src = set(int(b0 + rng.integers(nl)) for _ in range(2 + int(rng.integers(2))))
-            if i > b0 + nl:
-                src |= set(int(b0 + nl + rng.integers(i - b0 - nl)) for _ in range(int(rng.integers(3))))
-            if b0 > 0 and rng.integers(5) == 0:
-                src.add(int(rng.integers(b0)))
-            for j in src:
-                rows.append(i), cols.append(j)
-    A = sp.csr_matrix((rng.uniform(-0.4, 0.4, len(rows)), (rows, cols)), shape=(m, m))
-    if lower:
-        return A
-    # the mirrored pattern as a strict upper triangle (row i reads LATER rows)
-    P = sp.csr_matrix((np.ones(m), (np.arange(m), m - 1 - np.arange(m))), shape=(m, m))
-    return (P @ A @ P).tocsr()
-
-
-def _synthetic_levels():
-    rng = np.random.default_rng(11)
-    n0, m0 = 7000, 6300
-    nd = n0 - m0
-    lv = dict(m=m0, n=n0)
-    E = sp.random(nd, m0, density=0.004, random_state=np.random.RandomState(3), format="csr")
-    F = sp.random(m0, nd, density=0.002, random_state=np.random.RandomState(4), format="csr")
-    for k, M in (("L", _forest(m0, 120, 60, rng, True)), ("U", _forest(m0, 120, 60, rng, False)), ("E", E), ("F", F)):
-        lv[k + "_colptr"], lv[k + "_rowind"], lv[k + "_vals"] = _ccs(M)
-    lv["d"] = rng.uniform(0.5, 2.0, m0) * rng.choice([-1.0, 1.0], m0)
-    lv["s"], lv["t"] = rng.uniform(0.5, 2.0, n0), rng.uniform(0.5, 2.0, n0)
-    lv["p"] = rng.permutation(n0).astype(np.int32)
-    lv["q"] = rng.permutation(n0).astype(np.int32)
-    lv["p_inv"] = np.argsort(lv["p"]).astype(np.int32)
-    lv["q_inv"] = np.argsort(lv["q"]).astype(np.int32)
-    D = rng.normal(size=(nd, nd)) + 6.0 * np.eye(nd)
-    lv["dense_n"], lv["dense"] = nd, D.ravel(order="F")
-    return [lv]
-
-
 def _levels(name):
-    return _synthetic_levels() if name == "synthetic" else load_hier(name)[0]
+    return forest_levels() if name == "synthetic" else load_hier(name)[0]
 
 
 class _Env:

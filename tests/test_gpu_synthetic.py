@@ -1,51 +1,31 @@
 """GPU (-m gpu): synthetic hierarchies that no factorization would produce, to reach the corners of
 the band planner and of the apply driver: very deep chains (1 row per wavefront), a thin run whose
 block inverse blows up (must fall back to the sequential, backward-stable scheme), random
-multi-level hierarchies with random permutations/scalings, empty blocks (m = 0, m = n, F absent)."""
+multi-level hierarchies with random permutations/scalings, empty blocks (m = 0, m = n, F absent).
+The degenerate shapes, the deep chains, one random hierarchy and the non-finite column also run as complex128 handles
+(values, pivots and right-hand sides with imaginary parts of their own: k_band_cs_z, k_band_cd_z, k_spmm_tile_z,
+k_zcombine), at the same tolerances; bit-exact assertions are made for real data only."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
 import hifir_amd
 from oracle import orc
-from util import relerr
+from util import dense_block, rand_rhs, relerr
+from util import rand_tri as _rand_tri
+from util import synth_level as _level
 
 pytestmark = pytest.mark.gpu
 
-
-def _ccs(A):
-    A = sp.csc_matrix(A)
-    A.sort_indices()
-    return A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64)
+REAL, CPLX = np.float64, np.complex128
 
 
-def _level(m, n, L, U, E, F, rng, with_F=True):
-    lv = dict(m=m, n=n)
-    for k, M in (("L", L), ("U", U), ("E", E), ("F", F)):
-        cp, ri, v = _ccs(M)
-        lv[k + "_colptr"], lv[k + "_rowind"], lv[k + "_vals"] = cp, ri, v
-    if not with_F:
-        lv["F_colptr"], lv["F_rowind"], lv["F_vals"] = np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0)
-    lv["d"] = rng.uniform(0.5, 2.0, m) * rng.choice([-1.0, 1.0], m)
-    lv["s"], lv["t"] = rng.uniform(0.5, 2.0, n), rng.uniform(0.5, 2.0, n)
-    lv["p"] = rng.permutation(n).astype(np.int32)
-    lv["q"] = rng.permutation(n).astype(np.int32)
-    lv["p_inv"] = np.argsort(lv["p"]).astype(np.int32)
-    lv["q_inv"] = np.argsort(lv["q"]).astype(np.int32)
-    return lv
-
-
-def _rand_tri(m, density, lower, rng, scale=0.3):
-    A = sp.random(m, m, density=density, random_state=np.random.RandomState(rng.integers(1 << 30)), format="csr")
-    A.data = rng.uniform(-scale, scale, A.nnz)
-    return sp.tril(A, -1) if lower else sp.triu(A, 1)
-
-
-def _check(levels, nrhs, exact_expected, tol=1e-12, seed=0):
-    M = hifir_amd.HIF.from_levels(levels, max_nrhs=min(nrhs, 64))
-    O = orc.Oracle(levels)
+def _check(levels, nrhs, exact_expected, tol=1e-12, seed=0, dtype=REAL):
+    M = hifir_amd.HIF.from_levels(levels, max_nrhs=min(nrhs, 64), dtype=dtype)
+    O = orc.Oracle(levels, dtype=dtype)
     n = int(levels[0]["n"])
-    B = np.random.default_rng(seed).uniform(-1, 1, size=(n, nrhs))
+    B = rand_rhs(np.random.default_rng(seed), (n, nrhs), dtype)
+    exact_expected = exact_expected and dtype is REAL
     X, Xo = M.solve_mrhs(B), O.solve_batch(B, threads=4)
     if exact_expected:
         assert np.array_equal(X, Xo), relerr(X, Xo)
@@ -62,8 +42,20 @@ def _check(levels, nrhs, exact_expected, tol=1e-12, seed=0):
     return M
 
 
-@pytest.mark.parametrize("coef,exact", [(-2.0, True), (-0.5, False)])
+CHAINS = pytest.mark.parametrize("coef,exact", [(-2.0, True), (-0.5, False)])
+
+
+@CHAINS
 def test_deep_chain_and_growth_fallback(coef, exact):
+    _deep_chain_and_growth_fallback(coef, exact, REAL)
+
+
+@CHAINS
+def test_deep_chain_and_growth_fallback_complex(coef, exact):
+    _deep_chain_and_growth_fallback(coef, exact, CPLX)
+
+
+def _deep_chain_and_growth_fallback(coef, exact, dtype):
     # L = I + coef * subdiagonal: 400 wavefronts of one row each.  coef = -2: the block inverse has
     # entries up to 2^399 -> the planner must keep the sequential scheme (then bit-exact);
     # coef = -0.5: benign -> block-dense path (tolerance).
@@ -73,52 +65,70 @@ def test_deep_chain_and_growth_fallback(coef, exact):
     # same for U (coef = -2: |x| grows to ~2^800 < 1.8e308, still finite)
     U = sp.diags([np.full(m - 1, coef)], [1], shape=(m, m)) if coef == -2.0 else \
         sp.diags([rng.uniform(-0.4, 0.4, m - 1)], [1], shape=(m, m))
-    lv = _level(m, m, L, U, sp.csr_matrix((0, m)), sp.csr_matrix((m, 0)), rng)
-    lv["d"] = np.ones(m)
-    _check([lv], 64, exact_expected=exact)
+    if dtype is CPLX:  # a phase per entry: the moduli, and with them the growth of the block inverse, stay as they are
+        L = sp.diags([L.diagonal(-1) * np.exp(1j * rng.uniform(-1, 1, m - 1))], [-1], shape=(m, m))
+        U = sp.diags([U.diagonal(1) * np.exp(1j * rng.uniform(-1, 1, m - 1))], [1], shape=(m, m))
+    lv = _level(m, m, L, U, sp.csr_matrix((0, m)), sp.csr_matrix((m, 0)), rng, dtype=dtype)
+    lv["d"] = np.ones(m, dtype=dtype)
+    _check([lv], 64, exact_expected=exact, dtype=dtype)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_random_two_level_hierarchy_with_dense_tail(seed):
+    _random_two_level_hierarchy_with_dense_tail(seed, REAL)
+
+
+def test_random_two_level_hierarchy_with_dense_tail_complex():
+    _random_two_level_hierarchy_with_dense_tail(1, CPLX)
+
+
+def _random_two_level_hierarchy_with_dense_tail(seed, dtype):
     rng = np.random.default_rng(seed)
     n0, m0 = 3000, 2300
     n1, m1 = n0 - m0, 520
     nd = n1 - m1
-    lv0 = _level(m0, n0, _rand_tri(m0, 0.004, True, rng), _rand_tri(m0, 0.004, False, rng),
+    lv0 = _level(m0, n0, _rand_tri(m0, 0.004, True, rng, dtype=dtype), _rand_tri(m0, 0.004, False, rng, dtype=dtype),
                  sp.random(n0 - m0, m0, density=0.01, random_state=np.random.RandomState(seed), format="csr"),
-                 sp.random(m0, n0 - m0, density=0.01, random_state=np.random.RandomState(seed + 7), format="csr"), rng)
-    lv1 = _level(m1, n1, _rand_tri(m1, 0.02, True, rng), _rand_tri(m1, 0.02, False, rng),
+                 sp.random(m0, n0 - m0, density=0.01, random_state=np.random.RandomState(seed + 7), format="csr"), rng, dtype=dtype)
+    lv1 = _level(m1, n1, _rand_tri(m1, 0.02, True, rng, dtype=dtype), _rand_tri(m1, 0.02, False, rng, dtype=dtype),
                  sp.random(nd, m1, density=0.05, random_state=np.random.RandomState(seed + 1), format="csr"),
-                 sp.random(m1, nd, density=0.05, random_state=np.random.RandomState(seed + 2), format="csr"), rng)
-    D = rng.normal(size=(nd, nd)) + 4.0 * np.eye(nd)
-    lv1["dense_n"], lv1["dense"] = nd, D.ravel(order="F")
+                 sp.random(m1, nd, density=0.05, random_state=np.random.RandomState(seed + 2), format="csr"), rng, dtype=dtype)
+    lv1["dense_n"], lv1["dense"] = nd, dense_block(nd, 4.0, rng, dtype)
     for nrhs in (1, 7, 64):
-        _check([lv0, lv1], nrhs, exact_expected=False, tol=1e-12, seed=seed)
+        _check([lv0, lv1], nrhs, exact_expected=False, tol=1e-12, seed=seed, dtype=dtype)
 
 
 def test_degenerate_shapes():
+    _degenerate_shapes(REAL)
+
+
+def test_degenerate_shapes_complex():
+    _degenerate_shapes(CPLX)
+
+
+def _degenerate_shapes(dtype):
     rng = np.random.default_rng(5)
+    tri = lambda m, density, lower: _rand_tri(m, density, lower, rng, dtype=dtype)  # noqa: E731
     # (a) m == n: last level without dense block, single LDU
     m = 257
-    a = _level(m, m, _rand_tri(m, 0.05, True, rng), _rand_tri(m, 0.05, False, rng), sp.csr_matrix((0, m)),
-               sp.csr_matrix((m, 0)), rng)
-    _check([a], 5, exact_expected=False)
+    a = _level(m, m, tri(m, 0.05, True), tri(m, 0.05, False), sp.csr_matrix((0, m)), sp.csr_matrix((m, 0)), rng, dtype=dtype)
+    _check([a], 5, exact_expected=False, dtype=dtype)
     # (b) F absent although n > m (prec_solve.hpp:400-403), dense tail
     n, m = 300, 200
-    b = _level(m, n, _rand_tri(m, 0.05, True, rng), _rand_tri(m, 0.05, False, rng),
+    b = _level(m, n, tri(m, 0.05, True), tri(m, 0.05, False),
                sp.random(n - m, m, density=0.1, random_state=np.random.RandomState(3), format="csr"),
-               sp.csr_matrix((m, 0)), rng, with_F=False)
-    b["dense_n"], b["dense"] = n - m, (rng.normal(size=(n - m, n - m)) + 5 * np.eye(n - m)).ravel(order="F")
-    _check([b], 9, exact_expected=False)
+               sp.csr_matrix((m, 0)), rng, with_F=False, dtype=dtype)
+    b["dense_n"], b["dense"] = n - m, dense_block(n - m, 5, rng, dtype)
+    _check([b], 9, exact_expected=False, dtype=dtype)
     # (c) m == 0: everything deferred to the dense block
     n = 64
-    c = _level(0, n, sp.csr_matrix((0, 0)), sp.csr_matrix((0, 0)), sp.csr_matrix((n, 0)), sp.csr_matrix((0, n)), rng)
-    c["dense_n"], c["dense"] = n, (rng.normal(size=(n, n)) + 6 * np.eye(n)).ravel(order="F")
-    _check([c], 3, exact_expected=False)
+    c = _level(0, n, sp.csr_matrix((0, 0)), sp.csr_matrix((0, 0)), sp.csr_matrix((n, 0)), sp.csr_matrix((0, n)), rng, dtype=dtype)
+    c["dense_n"], c["dense"] = n, dense_block(n, 6, rng, dtype)
+    _check([c], 3, exact_expected=False, dtype=dtype)
     # (d) empty triangles (diagonal leading block): one wavefront
     m = 1000
-    d = _level(m, m, sp.csr_matrix((m, m)), sp.csr_matrix((m, m)), sp.csr_matrix((0, m)), sp.csr_matrix((m, 0)), rng)
-    _check([d], 64, exact_expected=True)
+    d = _level(m, m, sp.csr_matrix((m, m)), sp.csr_matrix((m, m)), sp.csr_matrix((0, m)), sp.csr_matrix((m, 0)), rng, dtype=dtype)
+    _check([d], 64, exact_expected=True, dtype=dtype)
 
 
 def test_rank_deficient_dense_block_all_operators():
@@ -217,6 +227,14 @@ def test_tail_operator_with_ill_conditioned_coarse_level(monkeypatch):
 
 
 def test_non_finite_column_does_not_poison_later_solves():
+    _non_finite_column_does_not_poison_later_solves(REAL)
+
+
+def test_non_finite_column_does_not_poison_later_solves_complex():
+    _non_finite_column_does_not_poison_later_solves(CPLX)
+
+
+def _non_finite_column_does_not_poison_later_solves(dtype):
     # level 0 with fewer than 32 leading rows (the tail product's right-hand side then sits right in front of rows that
     # the same solve writes) -- a solve with a NaN column, then a finite solve on the same handle: exact same result as
     # on a fresh handle (round 2's product read up to 31 rows behind its panel through zero columns: 0 x NaN)
@@ -225,29 +243,35 @@ def test_non_finite_column_does_not_poison_later_solves():
     n1 = n0 - m0
     m1 = 420
     nd = n1 - m1
-    lv0 = _level(m0, n0, _rand_tri(m0, 0.2, True, rng), _rand_tri(m0, 0.2, False, rng),
+    tri = lambda m, density, lower: _rand_tri(m, density, lower, rng, dtype=dtype)  # noqa: E731
+    lv0 = _level(m0, n0, tri(m0, 0.2, True), tri(m0, 0.2, False),
                  sp.random(n1, m0, density=0.05, random_state=np.random.RandomState(1), format="csr"),
-                 sp.random(m0, n1, density=0.05, random_state=np.random.RandomState(2), format="csr"), rng)
-    lv1 = _level(m1, n1, _rand_tri(m1, 0.02, True, rng), _rand_tri(m1, 0.02, False, rng),
+                 sp.random(m0, n1, density=0.05, random_state=np.random.RandomState(2), format="csr"), rng, dtype=dtype)
+    lv1 = _level(m1, n1, tri(m1, 0.02, True), tri(m1, 0.02, False),
                  sp.random(nd, m1, density=0.05, random_state=np.random.RandomState(3), format="csr"),
-                 sp.random(m1, nd, density=0.05, random_state=np.random.RandomState(4), format="csr"), rng)
-    lv1["dense_n"], lv1["dense"] = nd, (rng.normal(size=(nd, nd)) + 4 * np.eye(nd)).ravel(order="F")
+                 sp.random(m1, nd, density=0.05, random_state=np.random.RandomState(4), format="csr"), rng, dtype=dtype)
+    lv1["dense_n"], lv1["dense"] = nd, dense_block(nd, 4, rng, dtype)
     levels = [lv0, lv1]
-    O = orc.Oracle(levels)
-    B = rng.uniform(-1, 1, size=(n0, 64))
-    Mf = hifir_amd.HIF.from_levels(levels, max_nrhs=64)
+    O = orc.Oracle(levels, dtype=dtype)
+    B = rand_rhs(rng, (n0, 64), dtype)
+    Mf = hifir_amd.HIF.from_levels(levels, max_nrhs=64, dtype=dtype)
     Xf = Mf.solve_mrhs(B)
-    M = hifir_amd.HIF.from_levels(levels, max_nrhs=64)
+    M = hifir_amd.HIF.from_levels(levels, max_nrhs=64, dtype=dtype)
     Bn = B.copy()
     Bn[:, 5] = np.nan
     Bn[3, 9] = np.inf
     Xn = M.solve_mrhs(Bn)
     assert not np.isfinite(Xn[:, 5]).any() or np.isnan(Xn[:, 5]).any()
     good = [c for c in range(64) if c not in (5, 9)]
-    assert np.array_equal(Xn[:, good], Xf[:, good])  # columns are independent of each other
     X2 = M.solve_mrhs(B)
     assert np.isfinite(X2).all()
-    assert np.array_equal(X2, Xf)
+    if dtype is REAL:
+        assert np.array_equal(Xn[:, good], Xf[:, good])  # columns are independent of each other
+        assert np.array_equal(X2, Xf)
+    else:  # (no bit-exact assertions for complex data: the clean columns and the later solve at the oracle's bar instead)
+        Xo = O.solve_batch(B, threads=4)
+        assert relerr(Xn[:, good], Xo[:, good]) <= 1e-12
+        assert relerr(X2, Xf) <= 1e-12
     for c in (0, 5, 9, 63):
         assert relerr(X2[:, c], O.solve(B[:, c].copy())) <= 1e-12
 

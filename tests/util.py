@@ -62,3 +62,153 @@ def stokes_kkt(nx, omega=0.1, eps=1e-8):
 
 def relerr(x, ref):
     return float(np.abs(x - ref).max() / max(np.abs(ref).max(), 1e-300))
+
+
+# ---- synthetic hierarchies (no factorization produces them): the generators of test_gpu_synthetic.py, test_gpu_ls_band.py and
+# test_gpu_variants.py.  dtype=np.complex128 gives every value an imaginary part of its own.
+def ccs(A, dtype=np.float64):
+    A = sp.csc_matrix(A)
+    A.sort_indices()
+    return A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(dtype)
+
+
+def _imag(A, rng, dtype, scale):
+    """A with independent imaginary parts on its pattern (complex dtype), A itself otherwise."""
+    A = sp.csr_matrix(A)
+    if np.dtype(dtype).kind != "c":
+        return A
+    return sp.csr_matrix((A.data + 1j * rng.uniform(-scale, scale, A.nnz), A.indices, A.indptr), shape=A.shape)
+
+
+def synth_level(m, n, L, U, E, F, rng, with_F=True, dtype=np.float64):
+    lv = dict(m=m, n=n)
+    z = np.dtype(dtype).kind == "c"
+    for k, M in (("L", L), ("U", U), ("E", E), ("F", F)):
+        if z and not np.iscomplexobj(M.data if sp.issparse(M) else M):  # (triangles from rand_tri already are complex)
+            M = _imag(M, rng, dtype, 0.5)
+        cp, ri, v = ccs(M, dtype)
+        lv[k + "_colptr"], lv[k + "_rowind"], lv[k + "_vals"] = cp, ri, v
+    if not with_F:
+        lv["F_colptr"], lv["F_rowind"], lv["F_vals"] = np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, dtype)
+    lv["d"] = rng.uniform(0.5, 2.0, m) * rng.choice([-1.0, 1.0], m)
+    if z:
+        lv["d"] = lv["d"] * np.exp(1j * rng.uniform(-1.0, 1.0, m))
+    lv["s"], lv["t"] = rng.uniform(0.5, 2.0, n), rng.uniform(0.5, 2.0, n)
+    lv["p"] = rng.permutation(n).astype(np.int32)
+    lv["q"] = rng.permutation(n).astype(np.int32)
+    lv["p_inv"] = np.argsort(lv["p"]).astype(np.int32)
+    lv["q_inv"] = np.argsort(lv["q"]).astype(np.int32)
+    return lv
+
+
+def rand_tri(m, density, lower, rng, scale=0.3, dtype=np.float64):
+    A = sp.random(m, m, density=density, random_state=np.random.RandomState(rng.integers(1 << 30)), format="csr")
+    A.data = rng.uniform(-scale, scale, A.nnz)
+    if np.dtype(dtype).kind == "c":
+        A = A.astype(np.complex128)
+        A.data = A.data + 1j * rng.uniform(-scale, scale, A.nnz)
+    return sp.tril(A, -1) if lower else sp.triu(A, 1)
+
+
+def dense_block(nd, shift, rng, dtype=np.float64, scale=1.0):
+    """Column-major values of a dense last level: scale * normal + shift * I."""
+    D = rng.normal(size=(nd, nd))
+    if scale != 1.0:
+        D *= scale
+    D = D + shift * np.eye(nd)
+    if np.dtype(dtype).kind == "c":
+        D = D + 1j * scale * rng.normal(size=(nd, nd))
+    return D.astype(dtype).ravel(order="F")
+
+
+def rand_rhs(rng, shape, dtype=np.float64):
+    B = rng.uniform(-1, 1, size=shape)
+    if np.dtype(dtype).kind == "c":
+        B = B + 1j * rng.uniform(-1, 1, size=shape)
+    return B.astype(dtype)
+
+
+def forest(m, leaves, spine, rng, lower):
+    """Strict triangle made of blocks of `leaves` rows without entries and `spine` rows that read 2-3 leaves and 0-2 earlier
+    spine rows of their block (now and then a row of an earlier block): components of ~leaves + spine rows, two thirds of
+    them pure sources -- the shape of level 0 of a PDE hierarchy, with more sources than one chunk holds."""
+    rows, cols = [], []
+    blk = leaves + spine
+    for b0 in range(0, m, blk):
+        nl = min(leaves, m - b0)
+        for i in range(b0 + nl, min(m, b0 + blk)):
+            src = set(int(b0 + rng.integers(nl)) for _ in range(2 + int(rng.integers(2))))
+            if i > b0 + nl:
+                src |= set(int(b0 + nl + rng.integers(i - b0 - nl)) for _ in range(int(rng.integers(3))))
+            if b0 > 0 and rng.integers(5) == 0:
+                src.add(int(rng.integers(b0)))
+            for j in src:
+                rows.append(i), cols.append(j)
+    A = sp.csr_matrix((rng.uniform(-0.4, 0.4, len(rows)), (rows, cols)), shape=(m, m))
+    if lower:
+        return A
+    # the mirrored pattern as a strict upper triangle (row i reads LATER rows)
+    P = sp.csr_matrix((np.ones(m), (np.arange(m), m - 1 - np.arange(m))), shape=(m, m))
+    return (P @ A @ P).tocsr()
+
+
+def forest_levels():
+    """One level of 7,000 rows (6,300 leading) whose triangles are forests, with E, F and a dense last level."""
+    rng = np.random.default_rng(11)
+    n0, m0 = 7000, 6300
+    nd = n0 - m0
+    lv = dict(m=m0, n=n0)
+    E = sp.random(nd, m0, density=0.004, random_state=np.random.RandomState(3), format="csr")
+    F = sp.random(m0, nd, density=0.002, random_state=np.random.RandomState(4), format="csr")
+    for k, M in (("L", forest(m0, 120, 60, rng, True)), ("U", forest(m0, 120, 60, rng, False)), ("E", E), ("F", F)):
+        lv[k + "_colptr"], lv[k + "_rowind"], lv[k + "_vals"] = ccs(M)
+    lv["d"] = rng.uniform(0.5, 2.0, m0) * rng.choice([-1.0, 1.0], m0)
+    lv["s"], lv["t"] = rng.uniform(0.5, 2.0, n0), rng.uniform(0.5, 2.0, n0)
+    lv["p"] = rng.permutation(n0).astype(np.int32)
+    lv["q"] = rng.permutation(n0).astype(np.int32)
+    lv["p_inv"] = np.argsort(lv["p"]).astype(np.int32)
+    lv["q_inv"] = np.argsort(lv["q"]).astype(np.int32)
+    D = rng.normal(size=(nd, nd)) + 6.0 * np.eye(nd)
+    lv["dense_n"], lv["dense"] = nd, D.ravel(order="F")
+    return [lv]
+
+
+def clustered_tri(m, block, per_row, crown, rng, scale=0.15, cross=0.007):
+    """Strict lower triangle of independent clusters: row i of a `block`-row cluster reads up to `per_row` earlier rows of its
+    cluster (>= 4 nonzeros per row on average, components of `block` rows: what the planner gives dense-own component bands),
+    now and then a row of an earlier cluster, and the last `crown` rows read rows from anywhere before them (the merged top
+    of an elimination forest: no component holds them, they end up in the block-dense rest / the level's top operator)."""
+    rows, cols = [], []
+    body = m - crown
+    for b0 in range(0, body, block):
+        for i in range(b0 + 1, min(body, b0 + block)):
+            src = set(int(b0 + x) for x in rng.choice(i - b0, size=min(i - b0, per_row), replace=False))
+            if b0 > 0 and rng.random() < cross:
+                src.add(int(rng.integers(b0)))
+            for j in src:
+                rows.append(i), cols.append(j)
+    for i in range(body, m):
+        for j in set(int(x) for x in rng.integers(i, size=per_row)):
+            rows.append(i), cols.append(j)
+    return sp.csr_matrix((rng.uniform(-scale, scale, len(rows)), (rows, cols)), shape=(m, m))
+
+
+def transposed_pattern(L, rng, scale=0.15):
+    """Strict upper triangle on the transposed pattern of L (a structurally symmetric pair, as a PDE gives) with values of
+    its own."""
+    U = sp.csr_matrix(L.T)
+    U.data = rng.uniform(-scale, scale, U.nnz)
+    return U
+
+
+def shared_coupling(nrows, ncols, rng, scale=0.1):
+    """Coupling block whose rows share columns, and whose columns share rows: every group of 16 rows is dense on one group
+    of 16 columns (what the tiled Schur products are built for: >= 8 nonzeros per row and each column of a 16-row block
+    used 16 times -- in the block and, for the adjoint apply, in its transpose)."""
+    rows, cols = [], []
+    for r0 in range(0, nrows, 16):
+        c0 = 16 * int(rng.integers(max(1, ncols // 16)))
+        for i in range(r0, min(nrows, r0 + 16)):
+            for j in range(c0, min(ncols, c0 + 16)):
+                rows.append(i), cols.append(j)
+    return sp.csr_matrix((rng.uniform(-scale, scale, len(rows)), (rows, cols)), shape=(nrows, ncols))
