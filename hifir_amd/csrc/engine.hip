@@ -3443,12 +3443,22 @@ class Engine : public EngineBase {
     // the coefficient tiles of the component bands, the factors with their plan arrays
     double arena = 0.0, tiles = 0.0, factors = 0.0, skip_w = 0.0, skip_v = 0.0;
     double ls_src = 0.0, ls_dep = 0.0, ls_c = 0.0;  // k_band_ls: rows streamed, rows kept in LDS, the largest chunk (rows)
+    double cd_comps = 0.0, cd_shared = 0.0, ls_nch = 0.0;  // components of component bands, workgroups with several, most chunks (k_band_ls)
     for (const auto &L : lv) {
+      for (size_t b = 0; b < L->L.ls_band_ok.size() && b < L->L.ls_band_nch.size(); ++b)
+        if (L->L.ls_band_ok[b]) ls_nch = std::max(ls_nch, (double)L->L.ls_band_nch[b]);
       ls_src += (double)L->L.ls_sources, ls_dep += (double)L->L.ls_deps, ls_c = std::max(ls_c, (double)L->L.ls_chunk_rows);
       arena += (double)L->arena.bytes;
       skip_w += (double)L->skip_w;
       skip_v += (double)L->skip_v;
       for (const DevCsr *M : {&L->L, &L->U, &L->E, &L->F}) {
+        for (size_t b = 0; b < M->band_cd.size() && b + 1 < M->band_wg_ptr.size(); ++b) {
+          if (!M->band_cd[b]) continue;
+          for (int32_t g = M->band_wg_ptr[b]; g < M->band_wg_ptr[b + 1] && (size_t)g + 1 < M->host_wg_grp_ptr.size(); ++g) {
+            const int32_t nc = M->host_wg_grp_ptr[(size_t)g + 1] - M->host_wg_grp_ptr[(size_t)g];
+            cd_comps += (double)nc, cd_shared += nc > 1 ? 1.0 : 0.0;
+          }
+        }
         tiles += (double)(M->ct_sptr.bytes + M->ct_src.bytes + M->ct_coef.bytes + M->ct_desc.bytes);
         factors += (double)(M->ptr.bytes + M->col.bytes + M->val.bytes + M->rowid.bytes + M->srcslot.bytes + M->split.bytes + M->csplit.bytes +
                             M->cd_desc.bytes + M->mid_col.bytes + M->mid_val.bytes + M->mid_lrow.bytes + M->own_val.bytes + M->f_col.bytes +
@@ -3459,7 +3469,8 @@ class Engine : public EngineBase {
                         (double)tail_level, tail_probe_err, tail_max_abs, (double)tail_rejected, tail_probe_tol, tail_max_growth,
                         (double)levels_from_cache, analysis_seconds, arena, (double)Rmax, tiles, factors, (double)max_nrhs,
                         skip_w, skip_v, (double)host_repairs,
-                        (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0)), ls_src, ls_dep, ls_c};
+                        (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0)), ls_src, ls_dep, ls_c,
+                        cd_comps, cd_shared, ls_nch};
     const int nv = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < cap && i < nv; ++i) o[i] = v[i];
     return nv;

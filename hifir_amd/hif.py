@@ -212,15 +212,18 @@ class HIF:
                 "tail_probe_relerr", "tail_max_abs", "tail_rejected", "tail_probe_tol", "tail_max_growth",
                 "analysis_cached_levels", "analysis_s", "arena_bytes", "arena_cols", "tile_bytes", "factor_bytes", "max_nrhs",
                 "rows_not_stored_L", "rows_not_stored_U", "host_copy_repairs", "nsp_basis_bytes"]
-        return {key: float(s[i]) for i, key in enumerate(keys[:max(0, k)])}
+        out = {key: float(s[i]) for i, key in enumerate(keys[:max(0, k)])}
+        # component bands (slots 26 / 27): their components, and the workgroups that own more than one of them
+        out.update({key: float(s[26 + i]) for i, key in enumerate(("cd_components", "cd_shared_workgroups")) if 26 + i < k})
+        return out
 
     def ls_stats(self):
-        """Sparse-own L bands that run with streamed sources (hifamd_stats_ext slots 23-25): rows streamed as sources, rows
-        kept in LDS as dependent rows, rows of the source chunk (0: no band runs that way)."""
+        """Sparse-own L bands that run with streamed sources (hifamd_stats_ext slots 23-25 and 28): rows streamed as sources,
+        rows kept in LDS as dependent rows, rows of the source chunk (0: no band runs that way), most chunks of one component."""
         s = np.zeros(32)
         k = lib().hifamd_stats_ext(self._h, _p(s), 32)
-        keys = ["ls_streamed_sources", "ls_lds_rows", "ls_chunk_rows"]
-        return {key: float(s[23 + i]) if 23 + i < k else 0.0 for i, key in enumerate(keys)}
+        slots = {"ls_streamed_sources": 23, "ls_lds_rows": 24, "ls_chunk_rows": 25, "ls_max_chunks": 28}
+        return {key: float(s[i]) if i < k else 0.0 for key, i in slots.items()}
 
     def level_stats(self, level):
         s = np.zeros(16)

@@ -154,7 +154,10 @@ HifAmdStatus hifamd_stats(HifAmdHdl h, double *stats16);
  * changed since hifamd_add_level -- not by this library -- and rebuilt from the imported arrays (a warning names them on stderr;
  * anything it cannot rebuild is refused), 22 bytes of the null-space bases resident in HBM (hifamd_set_nsp_basis, both ops),
  * 23 / 24 rows of sparse-own L bands that are streamed as sources / kept in LDS as dependent rows (kernel k_band_ls), 25 rows
- * of that kernel's source chunk (0: no band runs through it).
+ * of that kernel's source chunk (0: no band runs through it),
+ * 26 components of all component bands (L and U, every level), 27 workgroups of those bands that own more than one
+ * component (the planner chains components once a band has more than 8 * HIFIR_AMD_BAND_WGS of them, and bags small
+ * ones), 28 the largest number of source chunks per component of any band that runs through k_band_ls.
  * -1 for a NULL handle. */
 int hifamd_stats_ext(HifAmdHdl h, double *out, int cap);
 /* Per-level sizes (what the SURVEY 8(d) byte formula needs level by level): 0 m, 1 n, 2 nnz(L_B), 3 nnz(U_B), 4 nnz(E),

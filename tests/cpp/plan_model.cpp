@@ -1,7 +1,9 @@
 // Development tool (host only, no GPU): loads a hierarchy file written by hifamd_save, analyzes every level with the
 // engine's default planner options (or the HIFIR_AMD_* overrides below) and writes, per band and per component, the
 // quantities the band-time model of tests/band_model.py prices: rows, entries the band kernel walks itself, entries
-// carried by the previous launch, distinct sources, 16x4 coefficient tiles, the longest wave chunk, own nonzeros.
+// carried by the previous launch, distinct sources, 16x4 coefficient tiles, the longest wave chunk, own nonzeros; and
+// what tests/test_shape_ladders_host.py asserts of the shape ladders: components per workgroup, the streamed kernels'
+// rows in LDS and longest wave run per component, the chunk k_band_ls would run a band with.
 //   g++ -O2 -std=c++17 -pthread -I hifir_amd/csrc tests/cpp/plan_model.cpp -o /tmp/plan_model
 //   /tmp/plan_model hier.hifamd > plan.jsonl
 #include "import.hpp"
@@ -56,6 +58,8 @@ struct Sink {
       const Csr<double> &A = tri ? H.Ur : H.Lr;
       CtTiles Tw;
       build_ct_tiles(P, A, Tw);
+      LsPlan<double> Ls;  // L: which bands k_band_ls would take, their chunk (16-row units) and chunks per component
+      if (!tri) build_ls_plan(P, A, (const Csr<double> *)nullptr, 0, env_int("HIFIR_AMD_LS_CHUNK", 0), Ls);
       for (int64_t b = 0; b < P.nbands(); ++b) {
         const int32_t g0 = P.band_wg_ptr[(size_t)b], g1 = P.band_wg_ptr[(size_t)b + 1];
         const int32_t c0 = P.wg_grp_ptr[(size_t)g0], c1 = P.wg_grp_ptr[(size_t)g1];
@@ -78,6 +82,10 @@ struct Sink {
         if (!P.band_cd[(size_t)b]) {
           std::printf("}\n");
           continue;
+        }
+        if (!tri && P.cd_sparse) {
+          const bool ok = Ls.any && Ls.band_ok[(size_t)b];
+          std::printf(", \"ls\": %d, \"ls_cw\": %d, \"ls_nch\": %d", (int)ok, ok ? Ls.band_cw[(size_t)b] : 0, ok ? Ls.band_nch[(size_t)b] : 0);
         }
         if (!Tw.sptr.empty()) {  // coefficient tiles of the band (what k_band_ct multiplies) and its longest wave
           int64_t tw = 0;
@@ -123,6 +131,33 @@ struct Sink {
           const int32_t nl = P.cd_sparse ? P.cd_desc[(size_t)c * kCdDescWords + 24] : 0;
           std::printf("%s[%d,%ld,%zu,%ld,%ld,%d,%ld,%d]", c == c0 ? "" : ",", nb, (long)walked, all.size(), (long)tiles16, (long)tiles32, ck, (long)own, nl);
         }
+        // sparse-own bands, per component: [rows kept in LDS, outside entries of the longest wave run] under the wave
+        // assignment of the streamed kernels.  L (k_band_ls): dependent rows (rows with own entries) first, wave w owns the
+        // dependent rows w, w + 16, ... and the sources nd + w, nd + w + 16, ...; each is one run of outside entries.
+        // U (k_band_us): black rows (rows another row of the component reads) first, wave w walks its rows one by one
+        if (P.cd_sparse) {
+          std::printf("], \"streams\": [");
+          for (int32_t c = c0; c < c1; ++c) {
+            const int32_t a = P.grp_slot_ptr[(size_t)c], nb = P.grp_slot_ptr[(size_t)c + 1] - a;
+            std::vector<uint8_t> kept((size_t)nb, 0);
+            for (int32_t r = 0; r < nb; ++r)
+              for (int32_t k = P.csplit[(size_t)(a + r)]; k < A.ptr[(size_t)(a + r) + 1]; ++k)
+                kept[(size_t)(tri ? P.srcslot[(size_t)k] - a : r)] = 1;
+            std::vector<int32_t> order;
+            for (int pass = 1; pass >= 0; --pass)
+              for (int32_t r = 0; r < nb; ++r)
+                if (kept[(size_t)r] == pass) order.push_back(r);
+            int32_t nk = 0;
+            for (int32_t r = 0; r < nb; ++r) nk += kept[(size_t)r];
+            int64_t run[32] = {0}, longest = 0;
+            for (int32_t q = 0; q < nb; ++q) {
+              const int32_t sl = a + order[(size_t)q];
+              run[q < nk ? 2 * (q % 16) : 2 * ((q - nk) % 16) + 1] += P.csplit[(size_t)sl] - P.split[(size_t)sl];
+            }
+            for (int w = 0; w < 32; ++w) longest = std::max(longest, run[w]);
+            std::printf("%s[%d,%ld]", c == c0 ? "" : ",", nk, (long)longest);
+          }
+        }
         // workgroup -> number of components (bags share a workgroup)
         std::printf("], \"wg_comps\": [");
         for (int32_t g = g0; g < g1; ++g) std::printf("%s%d", g == g0 ? "" : ",", P.wg_grp_ptr[(size_t)g + 1] - P.wg_grp_ptr[(size_t)g]);
@@ -142,6 +177,8 @@ int main(int argc, char **argv) {
   Sink S;
   BandOptions &o = S.opt;
   o.max_wg_rows = 16384;
+  o.max_wgs = env_int("HIFIR_AMD_BAND_WGS", 1024);
+  o.cd_sparse_min_rows = env_int("HIFIR_AMD_CD_SPARSE_MIN_ROWS", 4096);
   o.dense_block = env_int("HIFIR_AMD_DENSE_BLOCK", 2048);
   o.fuse_reorder = o.dense_block > 0;
   o.fuse_max_wgs = env_int("HIFIR_AMD_BAND_FUSE_WGS", 512);

@@ -19,6 +19,12 @@ launch census (HIF.kernel_census), and five checks per (variant, hierarchy):
 
 The oracle's answers do not depend on the environment: they are computed once per hierarchy and shared.
 
+The SHAPE of the work varies too: `ladder` / `ladderz` give the dense-own component kernels every component size from 9 to
+128 rows (every strip count, tile remainder and operand padding), `shapes` / `shapesz` give the sparse-own ones components
+by source / dependent-row class in two tiers with outside entries (util.py; test_shape_ladders_host.py asserts on the CPU
+which classes arrive), and the band_wgs=1 rows chain several components onto every workgroup (the kernels' loop over a
+workgroup's components, which a default plan enters only with more than 8,192 components in a band).
+
 Not reached here: the grid cap of the per-wave Schur product (k_spmm_tile with more than 16,384 blocks, i.e. more than a
 million rows in one coupling block) stays with test_gpu_fullsize.py.
 
@@ -31,8 +37,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import (clustered_tri, dense_block, forest, forest_levels, load_hier, rand_rhs, rand_tri, shared_coupling, synth_level,
-                  transposed_pattern)
+from util import (clustered_tri, dense_block, forest, forest_levels, ladder_levels, load_hier, rand_rhs, rand_tri, shapes_levels,
+                  shared_coupling, synth_level, transposed_pattern)
 
 TOL = 1e-12
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,6 +122,11 @@ HIERS = {
     "young": lambda: load_hier("young1c")[0],        # complex, 841 rows
     "synthz": lambda: _synth(np.complex128),
     "blocksz": lambda: _blocks(np.complex128),
+    # the shape ladders (util.py; test_shape_ladders_host.py asserts on the CPU what the planner makes of them)
+    "ladder": ladder_levels,                         # 8,520 rows, one level: dense-own components of 9 ... 128 rows, each size once
+    "shapes": shapes_levels,                         # 7,731 rows, one level: sparse-own components by source / dependent-row class, two tiers
+    "ladderz": lambda: ladder_levels(np.complex128),
+    "shapesz": lambda: shapes_levels(np.complex128),
 }
 REAL = ("deep", "tuned", "forest", "synth", "blocks", "leaves")
 CPLX = ("kkt", "young", "synthz", "blocksz")
@@ -149,7 +160,8 @@ class V:
     kernel; need / deny: census families that must be > 0 / == 0 at width 64; need16 / deny16: the same at width 16; lower:
     families that must run on a level >= 1; count64: exact launch counts at width 64; also: further hierarchies that run the
     variant for checks 1-3 and 5 and the deny lists (whatever kernels they reach: need / lower / count64 are not asked); same_bits: the handle has the bits of the handle created under `ref` (the environment without the
-    switch), a claim of DESIGN.md, a code comment or an existing test; bands: the switch changes the band count of the
+    switch), a claim of DESIGN.md, a code comment or an existing test -- True: on every hierarchy of the row, a tuple: on
+    those hierarchies only; bands: the switch changes the band count of the
     plan (stats()["bands"]; or the statistic named) against `ref`; xfail: a finding that is not fixed yet (strict)."""
 
     def __init__(self, name, env, on, need=(), deny=(), need16=(), deny16=(), lower=(), count64=None, same_bits=False, ref=None,
@@ -160,6 +172,8 @@ class V:
 
 
 T0 = {"TAIL_ROWS": "0"}
+W1 = {"BAND_WGS": "1"}  # eight workgroups per component band: every band of more than eight components chains them (c_first .. c_last)
+NOFUSE = {"FUSE_S1": "0", "FUSE_F": "0", "FUSE_S7": "0"}
 NOCD = {"CD_ROWS": "0", "TOP_ROWS": "0"}  # the depth-cut flag bands of round 1 everywhere
 TILE_ANY = ("spmm_tile_rb1", "spmm_tile_rb2", "spmm_tile4_rb1", "spmm_tile4_rb2")
 CT_ANY = ("band_ct1", "band_ct2", "band_ct4")
@@ -183,8 +197,13 @@ VARIANTS = [
     V("default-leaves", {}, ("leaves",), need=("band_ls", "band_us", "spmm_tile4_rb1"), need16=("band_cs_sparse",)),
     V("default-blocksz", {}, ("blocksz",), need=("band_cd_z", "spmm_tile_z", "zcombine"), need16=("band_cs_z",), lower=("band_cd_z",)),
     V("default-synthz", {}, ("synthz",), need=("band_cs_z",)),
+    # (the shape ladders: every dense-own component size 9 ... 128, the sparse-own shapes of test_shape_ladders_host.py)
+    V("default-ladder", {}, ("ladder",), need=("band_ct1",)),
+    V("default-shapes", {}, ("shapes",), need=("band_ls", "band_us"), need16=("band_cs_sparse",)),
+    V("default-ladderz", {}, ("ladderz",), need=("band_cd_z",), need16=("band_cs_z",)),
+    V("default-shapesz", {}, ("shapesz",), need=("band_cs_z",)),
     # -- the recursion through every level (the tail operator off)
-    V("tail0", T0, ("deep", "blocks"), lower=("spmm_tile4_rb1", "trsv_wide", "tri_gemm"), also=("tuned", "synth", "leaves")),
+    V("tail0", T0, ("deep", "blocks"), lower=("spmm_tile4_rb1", "trsv_wide", "tri_gemm"), also=("tuned", "synth", "leaves", "ladder")),
     V("tail0-blocks", T0, ("blocks",), need=("top_gemm", "top_reduce"),
       lower=("band_ct1", "spmm_tile4_rb1", "top_gemm", "top_reduce", "scatter_scale_list")),
     # (leaves: the second L solve of both levels takes F along -- one Schur product per level and direction is left)
@@ -204,15 +223,15 @@ VARIANTS = [
     V("fusions=0-z", {"FUSE_S1": "0", "FUSE_F": "0", "FUSE_S7": "0"}, ("kkt", "synthz", "blocksz"),
       need=("gather_scale", "scatter_scale"), deny=("scatter_scale_list",)),
     # -- wide coefficient tiles (widths <= 16 always take one tile: the width check compares ct1 with ct2 / ct4 bit for bit)
-    V("ct_wide=0", {"CT_WIDE": "0"}, ("blocks",), need=("band_ct2",), deny=("band_ct1", "band_ct4"), need16=("band_ct1",),
+    V("ct_wide=0", {"CT_WIDE": "0"}, ("blocks", "ladder"), need=("band_ct2",), deny=("band_ct1", "band_ct4"), need16=("band_ct1",),
       deny16=("band_ct2", "band_ct4"), same_bits=True, also=GOLD),
-    V("ct_wide4=0", {"CT_WIDE": "0", "CT_WIDE4": "0"}, ("blocks",), need=("band_ct4",), deny=("band_ct1", "band_ct2"),
+    V("ct_wide4=0", {"CT_WIDE": "0", "CT_WIDE4": "0"}, ("blocks", "ladder"), need=("band_ct4",), deny=("band_ct1", "band_ct2"),
       need16=("band_ct1",), deny16=("band_ct2", "band_ct4"), same_bits=True, also=GOLD),
     V("tail0-ct_wide=0", _u(T0, {"CT_WIDE": "0"}), ("blocks", "leaves"), need=("band_ct2",), lower=("band_ct2",), same_bits=True,
       ref=T0, also=("deep",)),
     V("tail0-ct_wide4=0", _u(T0, {"CT_WIDE": "0", "CT_WIDE4": "0"}), ("blocks", "leaves"), need=("band_ct4",), lower=("band_ct4",),
       same_bits=True, ref=T0, also=("deep",)),
-    V("ct=0", {"CT": "0"}, ("blocks",), need=("band_cd",), deny=CT_ANY, need16=("band_cs",), deny16=CT_ANY, also=GOLD),
+    V("ct=0", {"CT": "0"}, ("blocks", "ladder"), need=("band_cd",), deny=CT_ANY, need16=("band_cs",), deny16=CT_ANY, also=GOLD),
     V("tail0-ct=0", _u(T0, {"CT": "0"}), ("blocks", "leaves"), deny=CT_ANY, lower=("band_cd",)),
     V("ct_real=0", {"CT_REAL": "0"}, ("blocks",), need=("band_cd",), deny=CT_ANY),
     # -- Schur products
@@ -241,8 +260,8 @@ VARIANTS = [
     V("tail0-narrow_tiles=0-split=0", _u(T0, {"NARROW_TILES": "0", "SPMM_SPLIT": "0"}), ("deep", "blocks"), need16=("spmm_tile_rb1",),
       same_bits=True, ref=_u(T0, {"SPMM_SPLIT": "0"})),
     # -- column slices
-    V("cs=0", {"CS": "0"}, ("tuned", "forest", "leaves"), need16=("band_cd_sparse",), deny16=("band_cs", "band_cs_sparse"),
-      same_bits=True, also=("blocks",)),
+    V("cs=0", {"CS": "0"}, ("tuned", "forest", "leaves", "shapes"), need16=("band_cd_sparse",), deny16=("band_cs", "band_cs_sparse"),
+      same_bits=True, also=("blocks", "shapesz")),
     V("cs=0-ct=0", {"CS": "0", "CT": "0"}, ("blocks",), need16=("band_cd",), deny16=("band_cs", "band_cs_sparse"), same_bits=True,
       ref={"CT": "0"}),
     V("cs_max_wgs", {"CS_MAX_WGS": "100000"}, ("tuned", "forest", "leaves"), need=("band_cs_sparse",), deny=("band_cd_sparse", "band_us", "band_ls"),
@@ -251,10 +270,11 @@ VARIANTS = [
       ref={"CT": "0"}),
     V("tail0-cs_max_wgs", _u(T0, {"CS_MAX_WGS": "100000"}), ("leaves",), need=("band_cs", "band_cs_sparse"), lower=("band_cs",),
       same_bits=True, ref=T0),
-    V("cs_sparse", {"CS_SPARSE": "1", "CD_SPARSE_MIN_ROWS": "0"}, ("deep", "tuned", "forest", "leaves"), need=("band_cs_sparse",),
-      deny=("band_us", "band_ls", "band_cd_sparse")),
-    V("us=0", {"US": "0"}, ("tuned", "forest", "leaves"), need=("band_cd_sparse",), deny=("band_us",)),
-    V("cd_sparse_min_rows=0", {"CD_SPARSE_MIN_ROWS": "0"}, ("deep",), need=("band_us", "band_ls"), need16=("band_cs_sparse",)),
+    V("cs_sparse", {"CS_SPARSE": "1", "CD_SPARSE_MIN_ROWS": "0"}, ("deep", "tuned", "forest", "leaves", "shapes"), need=("band_cs_sparse",),
+      deny=("band_us", "band_ls", "band_cd_sparse"), also=("shapesz",)),
+    V("us=0", {"US": "0"}, ("tuned", "forest", "leaves", "shapes"), need=("band_cd_sparse",), deny=("band_us",), also=("shapesz",)),
+    V("cd_sparse_min_rows=0", {"CD_SPARSE_MIN_ROWS": "0"}, ("deep", "shapes"), need=("band_us", "band_ls"), need16=("band_cs_sparse",),
+      also=("shapesz",)),
     # -- operator products
     V("top_gemm=1", {"TOP_GEMM": "1"}, ("blocks",), need=("strip_gemm", "strip_gemm4"), deny=("top_gemm", "top_reduce"), also=GOLD),
     V("top_gemm=2", {"TOP_GEMM": "2"}, ("blocks",) + GOLD, need=("strip_gemm4",), deny=("top_gemm", "top_reduce", "strip_gemm")),
@@ -300,7 +320,7 @@ VARIANTS = [
     V("top_rows=0", {"TOP_ROWS": "0"}, ("blocks",), need=("tri_gemm",), count64={"top_gemm": 1}, also=GOLD),
     V("device_inverses=0", {"DEVICE_INVERSES": "0"}, ("deep", "blocks", "kkt", "blocksz"), same_bits=True),
     # -- the band planner, complex handles
-    V("cd_rows_z=48", {"CD_ROWS_Z": "48"}, ("blocksz",), need=("band_cd_z",), need16=("band_cs_z",), also=("kkt", "young", "synthz")),
+    V("cd_rows_z=48", {"CD_ROWS_Z": "48"}, ("blocksz", "ladderz"), need=("band_cd_z",), need16=("band_cs_z",), also=("kkt", "young", "synthz")),
     V("cd_rows_z=16", {"CD_ROWS_Z": "16"}, ("blocksz",), need=("band_cd_z",), bands="band_workgroups"),
     V("cd_sparse_rows_z=64", {"CD_SPARSE_ROWS_Z": "64"}, ("synthz",), need=("band_cs_z",), bands="band_workgroups", also=("kkt", "young", "blocksz")),
     V("cd_nnz_z", {"CD_NNZ_Z": "200"}, ("blocksz",), need=("band_cd_z",), bands="band_workgroups", also=("kkt", "young", "synthz")),
@@ -311,6 +331,37 @@ VARIANTS = [
     V("ct_z-cd_nnz_z", {"CT_Z": "1", "CD_NNZ_Z": "200"}, ("blocksz",), need=("band_ct_z",), also=("kkt", "young")),
     V("cs=0-z", {"CS": "0"}, ("blocksz",), need16=("band_cd_z",), deny16=("band_cs_z",), also=("kkt", "young")),
     V("tail0-ct_z", _u(T0, {"CT_Z": "1"}), ("blocksz",), lower=("band_ct_z", "spmm_tile_z")),
+    V("ct_z-ladderz", {"CT_Z": "1"}, ("ladderz",), need=("band_ct_z",), deny=("band_cd_z",), need16=("band_ct_z",)),
+    # -- workgroups that own several components (the kernels' loop c_first .. c_last with LDS reused from one component to
+    # the next; by default only a band of more than 8,192 components has them).  test_band_wgs_rows_share_workgroups asserts
+    # for every hierarchy of these rows that the plan does chain components; test_shape_ladders_host.py that EVERY component
+    # band of blocks, leaves, forest, ladder and shapes does (so the streamed kernels, one component per workgroup by
+    # construction, must step aside: the deny list of the sparse row).
+    # The bits of the handle without the switch are claimed on ladder only.  There the switch moves whole components
+    # between workgroups and nothing else: one band per triangle, no outside entries, no top operator, no carried prefix,
+    # and a row's sum is its right-hand side and the inverse product over the component's local rows from k = 0 -- the
+    # component's place in the slot order enters none of it.  Elsewhere the sums do change, and the oracle bar alone
+    # holds: on shapes, leaves, forest and tuned a band with chained components no longer qualifies for the streamed
+    # kernels, so host.hpp ls_reorder_own leaves its rows' own entries in CSR order instead of sources first (measured on
+    # shapes: 9e-16 between the two handles); on blocks the workgroup count of a band also decides what the combined top
+    # takes (HIFIR_AMD_TOP_WGS) and which bands carry a prefix (HIFIR_AMD_CD_FUSE_WGS), and the slot order of the sources
+    # orders the coefficient tiles.
+    V("band_wgs=1", W1, ("blocks", "ladder"), need=("band_ct1",), same_bits=("ladder",), also=("tuned",)),
+    V("band_wgs=1-sparse", W1, ("leaves", "forest", "shapes"), need=("band_cd_sparse",), deny=("band_ls", "band_us"),
+      need16=("band_cs_sparse",)),
+    V("band_wgs=1-ct=0", _u(W1, {"CT": "0"}), ("blocks", "ladder"), need=("band_cd",), deny=CT_ANY, need16=("band_cs",),
+      same_bits=("ladder",), ref={"CT": "0"}),
+    V("band_wgs=1-ct_wide=0", _u(W1, {"CT_WIDE": "0"}), ("blocks", "ladder"), need=("band_ct2",), deny=("band_ct1", "band_ct4"),
+      need16=("band_ct1",), same_bits=True, ref=W1),
+    V("band_wgs=1-ct_wide4=0", _u(W1, {"CT_WIDE": "0", "CT_WIDE4": "0"}), ("blocks", "ladder"), need=("band_ct4",),
+      deny=("band_ct1", "band_ct2"), need16=("band_ct1",), same_bits=True, ref=W1),
+    V("tail0-band_wgs=1", _u(T0, W1), ("blocks",), lower=("band_ct1", "spmm_tile4_rb1")),
+    V("tail0-band_wgs=1-leaves", _u(T0, W1), ("leaves",), need=("band_cd_sparse",), lower=("band_cd", "band_ct1")),
+    V("band_wgs=1-fusions=0", _u(W1, NOFUSE), ("blocks", "leaves", "shapes"), need=("gather_scale", "scatter_scale"),
+      deny=("scatter_scale_list", "band_ls", "band_us")),
+    V("band_wgs=1-z", W1, ("blocksz", "ladderz"), need=("band_cd_z",), need16=("band_cs_z",)),
+    V("band_wgs=1-z-sparse", W1, ("shapesz",), need=("band_cs_z",)),  # (sparse-own complex components run the slice kernel at every width)
+    V("band_wgs=1-ct_z", _u(W1, {"CT_Z": "1"}), ("blocksz", "ladderz"), need=("band_ct_z",), deny=("band_cd_z",), need16=("band_ct_z",)),
     # -- execution
     V("twin=0", {"TWIN": "0"}, ("deep", "tuned", "blocks", "kkt", "blocksz"), same_bits=True),
     V("xcd=0", {"XCD": "0"}, ("deep", "tuned", "forest", "blocks", "leaves", "kkt", "blocksz"), same_bits=True),
@@ -456,7 +507,7 @@ def judge(v, r):
             assert r[c][f] > 0, (c, f, "never launched on a level >= 1")
     if v.same_bits or v.bands:
         ref = _reference(h, v.ref)
-        if v.same_bits:
+        if v.same_bits is True or (v.same_bits and r["hier"] in v.same_bits):
             assert np.array_equal(r["X64"], ref["X"]), _colerr(r["X64"], ref["X"])
             assert np.array_equal(r["X64T"], ref["XT"]), _colerr(r["X64T"], ref["XT"])
         if v.bands and reach:
@@ -473,6 +524,22 @@ CASES = [pytest.param(v, hier, id=f"{v.name}-{hier}",
 @pytest.mark.parametrize("v,hier", CASES)
 def test_variant(v, hier):
     judge(v, measure(v, hier))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("v,hier", [pytest.param(v, hier, id=f"{v.name}-{hier}") for v in VARIANTS if v.env.get("BAND_WGS") == "1"
+                                    for hier in v.on + v.also])
+def test_band_wgs_rows_share_workgroups(v, hier):
+    """No band_wgs=1 row is vacuous: the handle's plan has workgroups that own several components, and has none without
+    the switch (hifamd_stats_ext slots 26 / 27)."""
+    h = _hier(hier)
+    for env, shared in ((v.env, True), ({k: x for k, x in v.env.items() if k != "BAND_WGS"}, False)):
+        M = _handle(h, env)
+        se = M.stats_ext()
+        M.close()
+        print(f"VARIANT {v.name} on {hier}, BAND_WGS={env.get('BAND_WGS')}: components {se['cd_components']:.0f} "
+              f"cd_shared_workgroups {se['cd_shared_workgroups']:.0f}")
+        assert se["cd_components"] > 0 and (se["cd_shared_workgroups"] > 0) == shared, se
 
 
 # ---- the table guard (CPU) ----------------------------------------------------------------------------------------------

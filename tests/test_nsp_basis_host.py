@@ -152,7 +152,10 @@ def test_refusals_in_order_without_a_gpu():
 def test_stats_ext_reports_the_basis_bytes():
     M, d = _import("neu2d_32_symm")
     se = M.stats_ext()
-    assert list(se)[-1] == "nsp_basis_bytes" and se["nsp_basis_bytes"] == 0.0 and len(se) == 23
+    assert list(se)[22] == "nsp_basis_bytes" and se["nsp_basis_bytes"] == 0.0
+    # (slots 23-25 are ls_stats(); the component-band counts of slots 26 / 27 follow the 23 keys, zero before finalize)
+    assert list(se)[23:] == ["cd_components", "cd_shared_workgroups"] and len(se) == 25
+    assert se["cd_components"] == 0.0 and se["cd_shared_workgroups"] == 0.0
 
 
 def test_cpp_facade_nsp_basis_compiles(tmp_path):

@@ -212,3 +212,144 @@ def shared_coupling(nrows, ncols, rng, scale=0.1):
             for j in range(c0, min(ncols, c0 + 16)):
                 rows.append(i), cols.append(j)
     return sp.csr_matrix((rng.uniform(-scale, scale, len(rows)), (rows, cols)), shape=(nrows, ncols))
+
+
+# ---- shape ladders (test_shape_ladders_host.py checks what the planner makes of them; test_gpu_variants.py, test_gpu_ls_band.py
+# and test_gpu_wide_batch.py solve them)
+def ladder_tri(sizes, per_row, rng, scale=0.15):
+    """Strict lower triangle of independent clusters of the given sizes, one after the other: row i of a cluster reads
+    min(i, per_row) earlier rows of it (clustered_tri without crown and cross entries, every cluster a size of its own).
+    With scale 0.15 and per_row = 6 a row's absolute sum stays below 0.9: the inverse of every cluster's unit triangle is
+    bounded by 1 / (1 - 0.9) = 10, the regime clustered_tri's hierarchies are solved in."""
+    rows, cols = [], []
+    b0 = 0
+    for sz in sizes:
+        for i in range(1, sz):
+            for x in rng.choice(i, size=min(i, per_row), replace=False):
+                rows.append(b0 + i), cols.append(b0 + int(x))
+        b0 += sz
+    return sp.csr_matrix((rng.uniform(-scale, scale, len(rows)), (rows, cols)), shape=(b0, b0))
+
+
+LADDER_SIZES = tuple(range(9, 129))
+
+
+def ladder_levels(dtype=np.float64, seed=51):
+    """One level + dense block, 8,520 rows: L is a ladder of 120 clusters of 9, 10, ... 128 rows in shuffled order with up to
+    six nonzeros per row, U its transposed pattern -- every strip count, every tile remainder and every operand padding of
+    the dense-own component kernels once per triangle."""
+    rng = np.random.default_rng(seed)
+    sizes = rng.permutation(LADDER_SIZES)
+    m0, nd = int(sizes.sum()), 300
+    n0 = m0 + nd
+    L = ladder_tri(sizes, 6, rng)
+    lv = synth_level(m0, n0, L, transposed_pattern(L, rng), shared_coupling(nd, m0, rng),
+                     sp.random(m0, nd, density=0.002, random_state=np.random.RandomState(4), format="csr"), rng, dtype=dtype)
+    lv["dense_n"], lv["dense"] = nd, dense_block(nd, 6.0, rng, dtype, scale=0.2)
+    return [lv]
+
+
+def shape_forest(shapes, rng, outside=()):
+    """Strict lower triangle of components of prescribed shape, in two tiers.  shapes: (ns, nd) pairs, tier 1 -- ns leaves
+    (rows without entries) followed by nd spine rows; every leaf is read by some spine row, every spine row but the first
+    reads an earlier spine row 1 to 6 rows back (the component stays whole, its depth varies) and up to two more leaves;
+    nd = 0 gives ns rows that belong to nothing.  outside: (ns, nd, leaf_out, spine_out) tuples, tier 2 behind tier 1 -- the
+    same components, whose leaves read leaf_out >= 1 and whose spine rows read spine_out rows of tier 1.  The first
+    outside row of a tier-2 leaf is the deepest row of one of the largest tier-1 components (the tier-2 components take
+    them in turn): a planner that merges components up to a row limit cannot place the leaf before that whole component,
+    so tier 2 is planned behind tier 1 and its entries into tier 1 are outside entries of the second band.  Values: +-0.4 for rows of at most five entries,
+    +-2 / entries beyond (absolute row sums <= 2, no inverses are formed of these triangles).
+    -> (L, comps) with comps = [(tier, first row, ns, nd)]."""
+    rows, cols, comps = [], [], []
+    at = 0
+    anchors = []  # (rows, deepest row) of the tier-1 components
+
+    def component(ns, nd, leaf_out, spine_out, tier, m1):
+        nonlocal at
+        b0 = at
+        anchor = big[len(comps) % len(big)] if tier == 2 else None
+        owner = [[] for _ in range(nd)]
+        for l in range(ns):  # every leaf is read by a spine row: the first ones in turn, the rest at random
+            if nd:
+                owner[l % nd if l < nd else int(rng.integers(nd))].append(l)
+        depth = [0] * (ns + nd)
+        for l in range(ns if tier == 2 else 0):
+            src = {anchor} | set(int(x) for x in rng.integers(m1, size=leaf_out - 1))
+            while len(src) < leaf_out:
+                src.add(int(rng.integers(m1)))
+            for j in src:
+                rows.append(b0 + l), cols.append(j)
+        for k in range(nd):
+            src = set(owner[k]) | set(int(x) for x in rng.integers(ns, size=int(rng.integers(3))) if ns)
+            if k:
+                src.add(ns + k - 1 - int(rng.integers(min(k, 6))))
+            depth[ns + k] = 1 + max([depth[j] for j in src], default=-1)
+            for j in src:
+                rows.append(b0 + ns + k), cols.append(b0 + j)
+            out = set()
+            while tier == 2 and len(out) < spine_out:
+                out.add(int(rng.integers(m1)))
+            for j in out:
+                rows.append(b0 + ns + k), cols.append(j)
+        if tier == 1 and nd:
+            anchors.append((ns + nd, b0 + int(np.argmax(depth))))
+        comps.append((tier, b0, ns, nd))
+        at += ns + nd
+
+    for ns, nd in shapes:
+        component(ns, nd, 0, 0, 1, 0)
+    m1 = at
+    big = [row for n, row in anchors if n == max(a[0] for a in anchors)]
+    for ns, nd, leaf_out, spine_out in outside:
+        component(ns, nd, leaf_out, spine_out, 2, m1)
+    cnt = np.bincount(rows, minlength=at)
+    vals = np.array([rng.uniform(-1, 1) * (0.4 if cnt[i] <= 5 else 2.0 / cnt[i]) for i in rows])
+    return sp.csr_matrix((vals, (rows, cols)), shape=(at, at)), comps
+
+
+# tier 1 of the shape hierarchy: (sources, dependent rows) by the classes k_band_ls / k_band_us branch on -- dependent rows 0,
+# 1, 15, 16, 17, 64, 65; sources 0, 1, 15 mod 16; sources = one 64-row chunk, one more, two chunks; the 192-row ones anchor tier 2
+SHAPES_TIER1 = ((40, 0), (31, 1), (17, 1), (33, 15), (15, 15), (48, 16), (16, 16), (1, 16), (47, 17), (64, 17), (64, 64), (65, 64),
+                (65, 33), (100, 50), (120, 60), (128, 64), (127, 65), (128, 64), (127, 65), (128, 1), (113, 15), (96, 65))
+# tier 2: (sources, dependent rows, outside rows per source, per dependent row) -- 129 ... 144 sources (three chunks of 48),
+# wave runs of 4, exactly 64 and 80 outside entries on the sources' side, 80 on the dependent rows' side
+SHAPES_TIER2 = ((140, 40, 1, 0), (64, 32, 1, 0), (64, 32, 16, 0), (64, 32, 20, 0), (64, 32, 1, 40), (96, 48, 2, 1), (130, 30, 3, 2),
+                (144, 48, 1, 1), (129, 63, 1, 0), (33, 15, 5, 3))
+
+
+def _fill_shapes(shapes, rows, draw):
+    shapes = list(shapes)
+    while sum(s[0] + s[1] for s in shapes) < rows:
+        shapes.append(draw())
+    return shapes
+
+
+def shapes_levels(dtype=np.float64, seed=52, tier1=4800, tier2=2500, ns_max=(128, 140), classes=(SHAPES_TIER1, SHAPES_TIER2)):
+    """One level + dense block: L is a shape_forest of the classes above filled up with random shapes to tier1 + tier2 rows
+    (tier 2 has to exceed one block of the dense chain, 2,048 rows, to become a component band), U its transposed
+    pattern, thin E and F."""
+    rng = np.random.default_rng(seed)
+
+    def draw1():
+        ns = int(rng.integers(16, ns_max[0] + 1))
+        return ns, int(rng.integers(1, min(64, 192 - ns) + 1))
+
+    def draw2():
+        ns = int(rng.integers(32, ns_max[1] + 1))
+        return ns, int(rng.integers(8, min(48, 192 - ns) + 1)), int(rng.integers(1, 4)), int(rng.integers(3))
+
+    L, _ = shape_forest(_fill_shapes(classes[0], tier1, draw1), rng, _fill_shapes(classes[1], tier2, draw2) if tier2 else ())
+    m0, nd = L.shape[0], 300
+    n0 = m0 + nd
+    rs = np.random.RandomState
+    lv = synth_level(m0, n0, L, transposed_pattern(L, rng, scale=0.4), sp.random(nd, m0, density=0.004, random_state=rs(3), format="csr"),
+                     sp.random(m0, nd, density=0.002, random_state=rs(4), format="csr"), rng, dtype=dtype)
+    lv["dense_n"], lv["dense"] = nd, dense_block(nd, 6.0, rng, dtype, scale=0.2)
+    return [lv]
+
+
+def short_shapes_levels(ns_top, seed):
+    """2,100 rows of one tier with at most ns_top sources per component (one component band per triangle, no second tier):
+    the chunk counts of k_band_ls that the 128-source components of shapes_levels cannot reach."""
+    tier1 = ((ns_top, 40), (ns_top, 1), (ns_top - 15, 64), (ns_top - 31, 20), (ns_top, 17), (33, 15))
+    return shapes_levels(seed=seed, tier1=2100, tier2=0, ns_max=(ns_top, 0), classes=(tier1, ()))
