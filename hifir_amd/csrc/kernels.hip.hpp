@@ -2717,20 +2717,25 @@ __global__ void __launch_bounds__(1024) k_top_gemm(int nrows, int kvalid, int kp
     const double *ap_ = Ap + (int64_t)min((c_), nchunks - 1) * (64 * 16);                     \
     _Pragma("unroll") for (int u = 0; u < 4; ++u) aa[u] = ap_[u * 64];                        \
   }
-  // panel chunk c into buffer b: 64 rows x 64 columns, 16 bytes per thread and pass (rows >= kvalid: zeros)
+  // panel chunk c into buffer b: 64 rows x 64 columns, 16 bytes per thread and pass (rows >= kvalid: zeros).  The loads
+  // are unconditional too -- a load under a branch makes the compiler drain every outstanding load at the merge, the A
+  // fragments with it: a row >= kvalid reads row kvalid - 1 and SELECTS zero (what lies behind kvalid is never touched),
+  // a chunk index past the end re-reads the last chunk (stored to the idle buffer, never multiplied)
   typedef double v2f64 __attribute__((ext_vector_type(2)));
   const int xr = threadIdx.x >> 5, xc = (threadIdx.x & 31) * 2;  // row 0..31 (+32), columns xc, xc+1
   v2f64 xs0, xs1;
+  bool xk0, xk1;  // (the row is a panel row: selected at the LDS store, behind the products, where the wait belongs)
 #define HIFAMD_TG_XLOAD(c_)                                                                   \
   {                                                                                           \
-    const int r0_ = k0 + 64 * (c_) + xr, r1_ = r0_ + 32;                                      \
-    xs0 = (r0_ < kvalid && xc < 16 * nct) ? *reinterpret_cast<const v2f64 *>(X + ((int64_t)r0_ << 6) + xc) : v2f64{0.0, 0.0}; \
-    xs1 = (r1_ < kvalid && xc < 16 * nct) ? *reinterpret_cast<const v2f64 *>(X + ((int64_t)r1_ << 6) + xc) : v2f64{0.0, 0.0}; \
+    const int r0_ = k0 + 64 * min((c_), nchunks - 1) + xr, r1_ = r0_ + 32;                    \
+    xk0 = r0_ < kvalid && xc < 16 * nct, xk1 = r1_ < kvalid && xc < 16 * nct;                 \
+    xs0 = *reinterpret_cast<const v2f64 *>(X + ((int64_t)min(r0_, kvalid - 1) << 6) + xc);    \
+    xs1 = *reinterpret_cast<const v2f64 *>(X + ((int64_t)min(r1_, kvalid - 1) << 6) + xc);    \
   }
-#define HIFAMD_TG_XSTORE(b_)                                                   \
-  {                                                                            \
-    *reinterpret_cast<v2f64 *>(&xb[b_][xr * XS + xc]) = xs0;                   \
-    *reinterpret_cast<v2f64 *>(&xb[b_][(xr + 32) * XS + xc]) = xs1;            \
+#define HIFAMD_TG_XSTORE(b_)                                                                  \
+  {                                                                                           \
+    *reinterpret_cast<v2f64 *>(&xb[b_][xr * XS + xc]) = xk0 ? xs0 : v2f64{0.0, 0.0};          \
+    *reinterpret_cast<v2f64 *>(&xb[b_][(xr + 32) * XS + xc]) = xk1 ? xs1 : v2f64{0.0, 0.0};   \
   }
 #define HIFAMD_TG_MFMA(aa, b_)                                                                     \
   _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                  \
@@ -2738,20 +2743,38 @@ __global__ void __launch_bounds__(1024) k_top_gemm(int nrows, int kvalid, int kp
     _Pragma("unroll") for (int t = 0; t < NCT; ++t)                                                \
         acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aa[u], bp_[16 * t], acc[t], 0, 0, 0);        \
   }
+  // one chunk: the panel of chunk c + 1 is requested FIRST, the A fragments of chunk c + 2 behind it -- vector loads
+  // return in order, so the wait in front of the panel's LDS store leaves those four A loads in flight (a counted wait,
+  // never vmcnt(0)); the A fragments of chunk c landed with the panel of chunk c, one step ago
+#define HIFAMD_TG_STEP(c_, acur, anew)                                         \
+  {                                                                            \
+    HIFAMD_TG_XLOAD((c_) + 1)                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    HIFAMD_TG_A(anew, (c_) + 2)                                                \
+    __builtin_amdgcn_sched_barrier(0); /* (the requests stay in this order, in front of the products) */ \
+    HIFAMD_TG_MFMA(acur, ((c_) & 1))                                           \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    HIFAMD_TG_XSTORE((((c_) + 1) & 1))                                         \
+    __syncthreads();                                                           \
+  }
+  HIFAMD_TG_XLOAD(0)
   HIFAMD_TG_A(a0, 0)
   HIFAMD_TG_A(a1, 1)
-  HIFAMD_TG_XLOAD(0)
   HIFAMD_TG_XSTORE(0)
   __syncthreads();
-  for (int c = 0; c < nchunks; ++c) {  // (A fragments two chunks ahead in registers, the panel one chunk ahead in LDS)
-    HIFAMD_TG_A(a2, c + 2)
-    if (c + 1 < nchunks) HIFAMD_TG_XLOAD(c + 1)
-    HIFAMD_TG_MFMA(a0, (c & 1))
-    if (c + 1 < nchunks) HIFAMD_TG_XSTORE(((c + 1) & 1))
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) a0[u] = a1[u], a1[u] = a2[u];
+  // (A fragments two chunks ahead in registers, the panel one chunk ahead in LDS; three chunks per trip: the fragment
+  // sets rotate by name)
+  int c = 0;
+  for (; c + 3 <= nchunks; c += 3) {  // (one exit, at the top: the accumulators keep their registers round the loop)
+    HIFAMD_TG_STEP(c, a0, a2)
+    HIFAMD_TG_STEP(c + 1, a1, a0)
+    HIFAMD_TG_STEP(c + 2, a2, a1)
   }
+  if (c < nchunks) {  // the last one or two chunks
+    HIFAMD_TG_STEP(c, a0, a2)
+    if (c + 1 < nchunks) HIFAMD_TG_STEP(c + 1, a1, a0)
+  }
+#undef HIFAMD_TG_STEP
 #undef HIFAMD_TG_A
 #undef HIFAMD_TG_XLOAD
 #undef HIFAMD_TG_XSTORE
@@ -3960,7 +3983,8 @@ __global__ void __launch_bounds__(256) k_band_cs(int32_t wg0, const int32_t *__r
 // entry -- with the tile's four source rows gathered once (a lane loads the 8 bytes of ITS source row k = lane / 16,
 // column lane % 16: the B operand needs no shuffle, no LDS).  The wave then forms t = rhs - acc for its strips (S1 /
 // the pivot division fused as in k_band_cd) straight into LDS; phase 2, the product with the component's explicit
-// inverse, is k_band_cs's.  Column-separable like every kernel here: a column's bits do not depend on the batch width,
+// inverse, makes k_band_cs's sums in k_band_cs's order (its operand sets are requested two ahead, across the strips of
+// a wave).  Column-separable like every kernel here: a column's bits do not depend on the batch width,
 // so this kernel serves narrow batches (nsl < 4) and full ones alike.  Summation order: tile by tile (tolerance-level).
 // ---------------------------------------------------------------------------------------------
 template <bool LOWER, int NCT>
@@ -4009,6 +4033,11 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
   const bool first_l = LOWER && first_u && fl.on();
   const double *rhs = div_u ? (const double *)w : (first_l ? fl.bin.get() : (const double *)x);
   const int64_t rstride = first_l ? fl.ldb : 64;
+  // The batch's input and output blocks arrive as pointers read from memory (IoPtr): the compiler takes them for generic
+  // addresses, and ONE generic access anywhere in the kernel makes every later wait for a load a wait for ALL loads (a
+  // generic access may return out of order) -- phase 2's counted waits would be lost.  Both blocks are device memory:
+  typedef __attribute__((address_space(1))) double gdouble;
+  const gdouble *rhs_g = (const gdouble *)rhs;
   int32_t c_first, c_last;
   if (single_c0 >= 0) {
     c_first = single_c0 + bw;
@@ -4027,7 +4056,7 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
   int32_t *s_oi = s_hp + lds_rows;
   int32_t *s_sptr = s_oi + lds_rows;  // 17 entries (a component has at most 16 strips)
   const bool last_u = !LOWER && lu.on();
-  double *yout = last_u ? lu.out.get() : nullptr;
+  gdouble *yout = last_u ? (gdouble *)lu.out.get() : nullptr;
   constexpr int KU = 8;
   for (int32_t c = c_first; c < c_last; ++c) {
     const int32_t *dsc = ct_desc + (int64_t)c * 28;
@@ -4078,7 +4107,7 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
           const int cx = cc + 16 * ct;
-          tr[ct][j] = rhs[(int64_t)i * rstride + (first_l ? min(cx, fl.nrhs - 1) : cx)];
+          tr[ct][j] = rhs_g[(int64_t)i * rstride + (first_l ? min(cx, fl.nrhs - 1) : cx)];
         }
       }
       const int32_t t0 = s_sptr[s], t1 = (dbg & 1) ? t0 : s_sptr[s + 1];
@@ -4137,70 +4166,107 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
 #pragma unroll
       for (int u = 0; u < KU; ++u) a0[u] = ap_[u * 64];
     }
+    // ---- phase 2 (its requests start here): x = Tinv * t on the matrix cores, one 16-row strip x this slice's columns at
+    // a time; strips are dealt heaviest first in snake order over the four waves (k_band_cs): this wave's strips are
+    // S - 1 - q, q = 4 rnd + (rnd odd ? 3 - wave : wave) while q < S.  The product of a strip runs over its 32-k operand
+    // sets, k ascending; the sets of ALL the wave's strips form ONE sequence of items, walked by two cursors: the
+    // requests run two items ahead of the products, across strip boundaries (each set of the inverse is read once per
+    // solve, from HBM: a round trip that nothing hid cost more than the set's eight matrix instructions).  Three register
+    // sets rotate by name; every request is unconditional -- past the last item the cursor stays and reads that item
+    // again, never multiplied -- so the wait in front of a set's products is COUNTED: it leaves the two younger sets
+    // in flight (a load under a branch makes the compiler wait for everything at the merge)
+    const int Sx = (dbg & 2) ? 0 : S;
+    int nitems = 0;
+    for (int r = 0;; ++r) {
+      const int q = 4 * r + ((r & 1) ? 3 - wave : wave);
+      if (q >= Sx) break;
+      nitems += (min(nb, 16 * (S - q)) + 31) >> 5;
+    }
+    // a cursor: item index, round, set within the strip, sets of the strip, strip
+#define HIFAMD_CT_NEXT(i_, rnd_, t_, ns_, strip_)                         \
+  if (i_ + 1 < nitems) {                                                  \
+    ++i_;                                                                 \
+    if (t_ + 1 < ns_) {                                                   \
+      ++t_;                                                               \
+    } else {                                                              \
+      ++rnd_;                                                             \
+      t_ = 0;                                                             \
+      strip_ = S - 1 - (4 * rnd_ + ((rnd_ & 1) ? 3 - wave : wave));       \
+      ns_ = (min(nb, 16 * (strip_ + 1)) + 31) >> 5;                       \
+    }                                                                     \
+  }
+#define HIFAMD_CT_LOAD(aa)                                                                       \
+  {                                                                                              \
+    const double *ap_ = Ac + ((int64_t)l_strip * lda) * 16 + l16 + (int64_t)(32 * l_t + kq) * 16; \
+    _Pragma("unroll") for (int u = 0; u < KU; ++u) aa[u] = ap_[u * 64];                          \
+    HIFAMD_CT_NEXT(l_i, l_rnd, l_t, l_ns, l_strip)                                               \
+  }
+    int l_i = 0, l_rnd = 0, l_t = 0, l_strip = S - 1 - wave, l_ns = (min(nb, 16 * (S - wave)) + 31) >> 5;
+    double a2[KU];
+    if (nitems > 0) {  // (item 0 is on its way; item 1 follows it before the barrier)
+      HIFAMD_CT_NEXT(l_i, l_rnd, l_t, l_ns, l_strip)
+      HIFAMD_CT_LOAD(a1)
+    }
     // (rows nb .. lda - 1 are zero for the inverse product; lds_rows is a multiple of 32)
     for (int t = nb * W + (int)threadIdx.x; t < lda * W; t += 256) tb[t] = 0.0;
     HIFAMD_CSP(4)
     __syncthreads();
     HIFAMD_CSP(5)
-    // ---- phase 2: x = Tinv * t on the matrix cores, one 16-row strip x this slice's columns per step; strips are dealt
-    // heaviest first in snake order over the four waves (k_band_cs)
-    for (int rnd = 0;; ++rnd) {
-      const int q = 4 * rnd + ((rnd & 1) ? 3 - wave : wave);
-      if (q >= ((dbg & 2) ? 0 : S)) {
-        if (4 * rnd >= S) break;
-        continue;
-      }
-      const int strip = S - 1 - q;
-      const int kend = min(nb, 16 * (strip + 1));
-      const int nsets = (kend + 31) >> 5;
-      const double *Ap = Ac + ((int64_t)strip * lda) * 16 + l16;
+    if (nitems > 0) {
+      int m_i = 0, m_rnd = 0, m_t = 0, m_strip = S - 1 - wave, m_ns = (min(nb, 16 * (S - wave)) + 31) >> 5;
       const double *Bp = tb + l16;
       v4f64 acc0[NCT];
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) acc0[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
-#define HIFAMD_CT_LOAD(aa, t_)                                          \
-  {                                                                     \
-    const double *ap_ = Ap + (int64_t)(32 * (t_) + kq) * 16;            \
-    _Pragma("unroll") for (int u = 0; u < KU; ++u) aa[u] = ap_[u * 64]; \
-  }
-#define HIFAMD_CT_MFMA(aa, t_)                                                              \
+      // the products of the item under the product cursor; behind a strip's last set its rows go out
+#define HIFAMD_CT_MFMA(aa)                                                                  \
   {                                                                                         \
-    const int kb_ = 32 * (t_) + kq;                                                         \
+    const int kb_ = 32 * m_t + kq;                                                          \
     _Pragma("unroll") for (int u = 0; u < KU; ++u) {                                        \
       _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) {                                  \
         const double b0_ = Bp[(kb_ + 4 * u) * W + 16 * ct];                                 \
         acc0[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(aa[u], b0_, acc0[ct], 0, 0, 0);     \
       }                                                                                     \
     }                                                                                       \
+    if (m_t + 1 == m_ns) {                                                                  \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                       \
+        const int row = 16 * m_strip + kq + 4 * r;                                          \
+        if (row < nb) {                                                                     \
+          _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) {                              \
+            const int cx = cc + 16 * ct;                                                    \
+            if (last_u) {                                                                   \
+              if (cx < lu.nrhs) yout[(int64_t)s_oi[row] * lu.ldy + cx] = s_ot[row] * acc0[ct][r]; \
+            } else {                                                                        \
+              x[((int64_t)s_rowid[row] << 6) + cx] = acc0[ct][r];                           \
+            }                                                                               \
+          }                                                                                 \
+        }                                                                                   \
+      }                                                                                     \
+      _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) acc0[ct] = v4f64{0.0, 0.0, 0.0, 0.0}; \
+    }                                                                                       \
+    HIFAMD_CT_NEXT(m_i, m_rnd, m_t, m_ns, m_strip)                                          \
   }
-      int t = 0;
-      if (rnd != 0) HIFAMD_CT_LOAD(a0, 0)  // (the first strip's first set was requested before the barrier)
-      while (t < nsets) {
-        if (t + 1 < nsets) HIFAMD_CT_LOAD(a1, t + 1)
-        HIFAMD_CT_MFMA(a0, t)
-        if (t + 1 >= nsets) break;
-        if (t + 2 < nsets) HIFAMD_CT_LOAD(a0, t + 2)
-        HIFAMD_CT_MFMA(a1, t + 1)
-        t += 2;
+#define HIFAMD_CT_STEP(acur, anew)                                                          \
+  {                                                                                         \
+    HIFAMD_CT_LOAD(anew)                                                                    \
+    __builtin_amdgcn_sched_barrier(0); /* (the requests stay in front of the products) */   \
+    HIFAMD_CT_MFMA(acur)                                                                    \
+  }
+      int i = 0;
+      for (; i + 3 <= nitems; i += 3) {  // (one exit, at the top: no break between a request and its use)
+        HIFAMD_CT_STEP(a0, a2)
+        HIFAMD_CT_STEP(a1, a0)
+        HIFAMD_CT_STEP(a2, a1)
       }
-#undef HIFAMD_CT_LOAD
+      if (i < nitems) {  // the last one or two items: both are in registers or on their way
+        HIFAMD_CT_MFMA(a0)
+        if (i + 1 < nitems) HIFAMD_CT_MFMA(a1)
+      }
+#undef HIFAMD_CT_STEP
 #undef HIFAMD_CT_MFMA
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * strip + kq + 4 * r;
-        if (row < nb) {
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct) {
-            const int cx = cc + 16 * ct;
-            if (last_u) {
-              if (cx < lu.nrhs) yout[(int64_t)s_oi[row] * lu.ldy + cx] = s_ot[row] * acc0[ct][r];
-            } else {
-              x[((int64_t)s_rowid[row] << 6) + cx] = acc0[ct][r];
-            }
-          }
-        }
-      }
     }
+#undef HIFAMD_CT_LOAD
+#undef HIFAMD_CT_NEXT
     __syncthreads();  // (the next component overwrites the LDS block)
   }
   HIFAMD_CSP(6)
