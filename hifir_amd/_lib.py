@@ -30,6 +30,8 @@ SIGNATURES = {
     "hifamd_save": (_int, [_vp, C.c_char_p]),
     "hifamd_save_ex": (_int, [_vp, C.c_char_p, _int]),
     "hifamd_load": (_int, [C.c_char_p, _int, C.POINTER(_vp)]),
+    "hifamd_load_ex": (_int, [C.c_char_p, _int, _int, C.POINTER(_vp)]),
+    "hifamd_set_complex_operators": (_int, [_vp, _int]),
     "hifamd_set_dense": (_int, [_vp, _i64, _vp, _dbl]),
     "hifamd_set_dense_symm": (_int, [_vp, _i64, _vp, _int]),
     "hifamd_set_dense_lup": (_int, [_vp, _i64, _vp]),

@@ -382,6 +382,7 @@ enum KernelFamily {
   KF_BAND_SPLIT_PREFIX,  // k_trsv_wide as the chip-wide prefix pass of a split component band (HIFIR_AMD_CD_SPLIT_MIN)
   KF_ROW_GATHER,         // the row permutation in front of the adjoint's dense block
   KF_PROD,               // every kernel of the product M b that the apply does not share (k_gather_div ... k_scatter_div)
+  KF_TOP_GEMM_Z, KF_TOP_REDUCE_Z,  // top / tail operator products of a complex handle (hifamd_set_complex_operators)
   KF_COUNT
 };
 static const char *const kFamilyNames[KF_COUNT] = {
@@ -391,7 +392,7 @@ static const char *const kFamilyNames[KF_COUNT] = {
     "spmm_tile_rb1", "spmm_tile_rb2", "spmm_tile4_rb1", "spmm_tile4_rb2", "spmm_tile_z", "spmm_epi", "spmm_epi_narrow",
     "top_gemm", "top_reduce", "strip_gemm", "strip_gemm4", "tri_gemm", "dense_gemm", "zcombine",
     "gather_scale", "scatter_scale", "scatter_scale_list",
-    "band_split_prefix", "row_gather", "prod"};
+    "band_split_prefix", "row_gather", "prod", "top_gemm_z", "top_reduce_z"};
 // launches per family: [0, KF_COUNT) on every level, [KF_COUNT, 2 KF_COUNT) those of them on a level >= 1
 typedef std::array<int32_t, 2 * KF_COUNT> Census;
 // Graph capture, instantiation and launch are serialized across the handles of a process: distinct handles may be used from
@@ -515,6 +516,22 @@ class Engine : public EngineBase {
   // launches fewer, same bits, but the agent-scope release / acquire fences write back and invalidate a whole L2 per
   // workgroup: k_top_gemm 40 -> 147 us, the apply 3.67 -> 4.61 ms
   int top_last_arriver = 0;
+  // Complex handles have both operators on request only (hifamd_set_complex_operators, before the first level): bit 0 the
+  // tail operator, bit 1 the combined tops.  Their products run through k_top_gemm_z / k_top_reduce_z whatever the
+  // switches of the real product kernels say.  Real handles: always 0 (they have both operators anyway).
+  int zop_flags = 0;
+  void set_complex_operators(int flags) {
+    if (flags < 0 || flags > 3) throw Error(HIFAMD_MISMATCHED_SIZES, "complex operator flags must be 0 ... 3 (HIFAMD_ZOP_TAIL | HIFAMD_ZOP_TOP)");
+    if (sizeof(T) == sizeof(double)) {
+      if (flags != 0) throw Error(HIFAMD_BAD_PREC, "a real handle already has the tail and the top operators: the flags belong to complex handles");
+      return;
+    }
+    if (finalized || !host.levels.empty())
+      throw Error(HIFAMD_BAD_PREC, "complex operators are a planner option: set them before the first hifamd_add_level");
+    zop_flags = flags;
+    band_opt.top_max = (flags & 2) ? zop_top_max : 0;
+  }
+  int64_t zop_top_max = 0;  // what top_max is for a real handle in the environment this handle was created under
   int cd_dbg = 0;        // development aid (HIFIR_AMD_CD_DBG): phases of k_band_cd switched off for timing experiments
   // Column-sliced component bands (kernels.hip.hpp k_band_cs): a component band of at most cs_max_wgs workgroups is cut
   // into 16-column slices (the heaviest component of a narrow band then runs on four compute units); a batch of fewer
@@ -653,8 +670,9 @@ class Engine : public EngineBase {
     band_opt.cd_sparse_rows = std::min(240, env_int("HIFIR_AMD_CD_SPARSE_ROWS", 192));  // 0: thin triangles keep the flag bands
     band_opt.top_max = env_int("HIFIR_AMD_TOP_ROWS", 4096);      // combined top operator (host.hpp choose_top); 0 = off
     band_opt.top_few_wgs = env_int("HIFIR_AMD_TOP_WGS", 96);
-    // complex handles: no combined top; sparse-own components for shallow thin triangles since round 4 (HIFIR_AMD_CD_SPARSE_ROWS_Z=0:
+    // complex handles: no combined top unless the handle asks for it (set_complex_operators); sparse-own components for shallow thin triangles since round 4 (HIFIR_AMD_CD_SPARSE_ROWS_Z=0:
     // those triangles keep the round-1 flag bands)
+    zop_top_max = band_opt.top_max;
     if (sizeof(T) != sizeof(double))
       band_opt.top_max = 0, band_opt.cd_sparse_rows = std::min(240, env_int("HIFIR_AMD_CD_SPARSE_ROWS_Z", 192)),
       band_opt.cd_max_nnz = env_int("HIFIR_AMD_CD_NNZ_Z", 0);
@@ -688,6 +706,10 @@ class Engine : public EngineBase {
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
+    if (sizeof(T) != sizeof(double) && zop_flags) {
+      HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
+      HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
+    }
     if (sizeof(T) != sizeof(double) && band_opt.cd_rows > 0) {
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cs_z<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(csz_lds_bytes(true, kCdOwnCap), 160 * 1024)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cs_z<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(csz_lds_bytes(true, kCdOwnCap), 160 * 1024)));
@@ -799,6 +821,7 @@ class Engine : public EngineBase {
     band_pipe = P.band_pipe, top_last_arriver = P.top_last_arriver, use_twin = P.use_twin;
     device_inverses = P.device_inverses, xcd_remap = P.xcd_remap;
     tail_probe_tol = P.tail_probe_tol, tail_max_growth = P.tail_max_growth;
+    zop_flags = P.zop_flags, zop_top_max = P.zop_top_max;  // (band_opt, copied above, carries the top_max they chose)
   }
 
   Engine<T> &adjoint_engine() {
@@ -1386,7 +1409,7 @@ class Engine : public EngineBase {
       HIP_OK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xcd_remap), &remap, sizeof(int), 0, hipMemcpyHostToDevice, xfer_stream()));
       HIP_OK(hipStreamSynchronize(xfer_stream()));
     }
-    if (top_rows_max > 0) gemm_part.alloc((size_t)kTopGemmSplits * (size_t)((top_rows_max + 63) / 64 * 64) * 64 * sizeof(double));
+    if (top_rows_max > 0) gemm_part.alloc((size_t)kTopGemmSplits * (size_t)((top_rows_max + 63) / 64 * 64) * 64 * sizeof(T));  // (complex: partial tiles of 128 doubles a row)
     gemm_cnt.alloc(kTopGemmTilesMax * sizeof(unsigned));  // (tops and tails have at most top_max / tail_rows <= 64 x this many rows)
     zero_dev(gemm_cnt.p, gemm_cnt.bytes);
     if (band_opt.dense_block > 0) {  // +32 rows: the MFMA kernel reads whole 32-k operand sets (masked)
@@ -1424,92 +1447,94 @@ class Engine : public EngineBase {
   }
 
   void build_tail_operator() {
-    if constexpr (std::is_same<T, double>::value) {
-      if (tail_rows <= 0 || band_opt.dense_block <= 0 || Rmax != 64 || lv.size() < 2) return;
-      size_t l0 = 0;
-      for (size_t l = 1; l < lv.size(); ++l)
-        if (lv[l]->n <= tail_rows) {
-          l0 = l;
-          break;
-        }
-      if (!l0) return;
-      const int64_t n = lv[l0]->n, ld = round_up32(n);
-      DevBuf I, O;
-      I.alloc((size_t)(n + 32) * 64 * sizeof(double));
-      O.alloc((size_t)(n + 32) * 64 * sizeof(double));
-      std::vector<double> hI((size_t)n * 64), hO((size_t)n * 64), G((size_t)(n * n), 0.0);
-      for (int64_t j0 = 0; j0 < n; j0 += 64) {
-        const int64_t jw = std::min<int64_t>(64, n - j0);
-        std::fill(hI.begin(), hI.end(), 0.0);
-        for (int64_t c = 0; c < jw; ++c) hI[(size_t)((j0 + c) * 64 + c)] = 1.0;
-        copy_h2d(I.p, hI.data(), hI.size() * sizeof(double));
-        int64_t cnt = 0;
-        enqueue_level(stream, l0, in_direct(I.as<D>()), 64, out_direct(O.as<D>()), 64, 64, 6, 0, cnt);
-        HIP_OK(hipStreamSynchronize(stream));
-        copy_d2h(hO.data(), O.p, hO.size() * sizeof(double));
-        for (int64_t c = 0; c < jw; ++c)
-          for (int64_t i = 0; i < n; ++i) G[(size_t)(i + (j0 + c) * n)] = hO[(size_t)(i * 64 + c)];
+    // (complex handles: on request only -- hifamd_set_complex_operators, HIFAMD_ZOP_TAIL)
+    if (!std::is_same<T, double>::value && !(zop_flags & 1)) return;
+    if (tail_rows <= 0 || band_opt.dense_block <= 0 || Rmax != 64 || lv.size() < 2) return;
+    size_t l0 = 0;
+    for (size_t l = 1; l < lv.size(); ++l)
+      if (lv[l]->n <= tail_rows) {
+        l0 = l;
+        break;
       }
-      check_device_error();
-      // Guards (every other explicit operator has one: block inverses and top operators fall back to substitution when
-      // their entries grow beyond dense_max_growth).  G = M_tail^{-1} bakes the sparse levels below l0 AND the (possibly
-      // rank-truncated) dense block into one matrix:
-      //  (1) every entry finite (a singular tail: keep the recursion, which reports what it finds);
-      //  (2) max |G| <= tail_max_growth: the product G c then loses at most that factor against the data;
-      //  (3) a probe: G c against the recursion on a fixed pseudo-random block c, relative difference (max norm, all 64
-      //      columns) <= tail_probe_tol -- an ill-conditioned tail, where the two roads differ by kappa eps, keeps the
-      //      recursion, i.e. the road the oracle comparison is stated for.
-      double gmax = 0.0;
-      for (double g : G) {
-        if (!std::isfinite(g)) {
-          tail_rejected = 1;
-          return;
-        }
-        gmax = std::max(gmax, std::fabs(g));
-      }
-      tail_max_abs = gmax;
-      if (gmax > tail_max_growth) {
-        tail_rejected = 2;
+    if (!l0) return;
+    const int64_t n = lv[l0]->n, ld = round_up32(n);
+    DevBuf I, O;
+    I.alloc((size_t)(n + 32) * 64 * sizeof(T));
+    O.alloc((size_t)(n + 32) * 64 * sizeof(T));
+    std::vector<T> hI((size_t)n * 64), hO((size_t)n * 64), G((size_t)(n * n), T(0));
+    for (int64_t j0 = 0; j0 < n; j0 += 64) {
+      const int64_t jw = std::min<int64_t>(64, n - j0);
+      std::fill(hI.begin(), hI.end(), T(0));
+      for (int64_t c = 0; c < jw; ++c) hI[(size_t)((j0 + c) * 64 + c)] = T(1);
+      copy_h2d(I.p, hI.data(), hI.size() * sizeof(T));
+      int64_t cnt = 0;
+      enqueue_level(stream, l0, in_direct(I.as<D>()), 64, out_direct(O.as<D>()), 64, 64, 6, 0, cnt);
+      HIP_OK(hipStreamSynchronize(stream));
+      copy_d2h(hO.data(), O.p, hO.size() * sizeof(T));
+      for (int64_t c = 0; c < jw; ++c)
+        for (int64_t i = 0; i < n; ++i) G[(size_t)(i + (j0 + c) * n)] = hO[(size_t)(i * 64 + c)];
+    }
+    check_device_error();
+    // Guards (every other explicit operator has one: block inverses and top operators fall back to substitution when
+    // their entries grow beyond dense_max_growth).  G = M_tail^{-1} bakes the sparse levels below l0 AND the (possibly
+    // rank-truncated) dense block into one matrix:
+    //  (1) every entry finite (a singular tail: keep the recursion, which reports what it finds);
+    //  (2) max |G| <= tail_max_growth: the product G c then loses at most that factor against the data;
+    //  (3) a probe: G c against the recursion on a fixed pseudo-random block c (complex handles: real and imaginary
+    //      parts drawn in turn), relative difference (max norm, all 64 columns) <= tail_probe_tol -- an ill-conditioned
+    //      tail, where the two roads differ by kappa eps, keeps the recursion, i.e. the road the oracle comparison is
+    //      stated for.
+    const double *Gd = reinterpret_cast<const double *>(G.data());  // (complex: both parts must be finite)
+    for (size_t i = 0; i < G.size() * (sizeof(T) / sizeof(double)); ++i)
+      if (!std::isfinite(Gd[i])) {
+        tail_rejected = 1;
         return;
       }
-      tailG.upload(mfma_operand(G.data(), n, n, ld), 4096);
-      if (gemm_part.bytes < (size_t)kTopGemmSplits * (size_t)((n + 63) / 64 * 64) * 64 * sizeof(double)) {
-        HIP_OK(hipStreamSynchronize(stream));
-        gemm_part.alloc((size_t)kTopGemmSplits * (size_t)((n + 63) / 64 * 64) * 64 * sizeof(double));
-      }
-      {
-        uint64_t rs = 0x9E3779B97F4A7C15ull;
-        for (double &x : hI) {
-          rs = rs * 6364136223846793005ull + 1442695040888963407ull;
-          x = (double)(int64_t)(rs >> 11) / 9007199254740992.0 * 2.0 - 1.0;
-        }
-        copy_h2d(I.p, hI.data(), hI.size() * sizeof(double));
-        int64_t cnt = 0;
-        enqueue_level(stream, l0, in_direct(I.as<D>()), 64, out_direct(O.as<D>()), 64, 64, 6, 0, cnt);  // the recursion
-        HIP_OK(hipStreamSynchronize(stream));
-        copy_d2h(hO.data(), O.p, hO.size() * sizeof(double));
-        std::vector<double> hP((size_t)n * 64);
-        tail_n = n;  // (launch_tail reads it)
-        launch_tail(stream, I.as<D>(), O.as<D>(), cnt);  // the product
-        HIP_OK(hipStreamSynchronize(stream));
-        copy_d2h(hP.data(), O.p, hP.size() * sizeof(double));
-        tail_n = 0;
-        check_device_error();
-        double num = 0.0, den = 0.0;
-        for (size_t i = 0; i < hP.size(); ++i) {
-          num = std::max(num, std::fabs(hP[i] - hO[i]));
-          den = std::max(den, std::fabs(hO[i]));
-        }
-        tail_probe_err = den > 0.0 ? num / den : num;
-        if (!(tail_probe_err <= tail_probe_tol)) {
-          tailG.release();
-          tail_rejected = 3;
-          return;
-        }
-      }
-      tail_level = (int64_t)l0;
-      tail_n = n;
+    double gmax = 0.0;
+    for (const T &g : G) gmax = std::max(gmax, (double)std::abs(g));
+    tail_max_abs = gmax;
+    if (gmax > tail_max_growth) {
+      tail_rejected = 2;
+      return;
     }
+    tailG.upload(mfma_operand(G.data(), n, n, ld), 4096);
+    if (gemm_part.bytes < (size_t)kTopGemmSplits * (size_t)((n + 63) / 64 * 64) * 64 * sizeof(T)) {
+      HIP_OK(hipStreamSynchronize(stream));
+      gemm_part.alloc((size_t)kTopGemmSplits * (size_t)((n + 63) / 64 * 64) * 64 * sizeof(T));
+    }
+    {
+      uint64_t rs = 0x9E3779B97F4A7C15ull;
+      double *hId = reinterpret_cast<double *>(hI.data());
+      for (size_t i = 0; i < hI.size() * (sizeof(T) / sizeof(double)); ++i) {
+        rs = rs * 6364136223846793005ull + 1442695040888963407ull;
+        hId[i] = (double)(int64_t)(rs >> 11) / 9007199254740992.0 * 2.0 - 1.0;
+      }
+      copy_h2d(I.p, hI.data(), hI.size() * sizeof(T));
+      int64_t cnt = 0;
+      enqueue_level(stream, l0, in_direct(I.as<D>()), 64, out_direct(O.as<D>()), 64, 64, 6, 0, cnt);  // the recursion
+      HIP_OK(hipStreamSynchronize(stream));
+      copy_d2h(hO.data(), O.p, hO.size() * sizeof(T));
+      std::vector<T> hP((size_t)n * 64);
+      tail_n = n;  // (launch_tail reads it)
+      launch_tail(stream, I.as<D>(), O.as<D>(), cnt);  // the product
+      HIP_OK(hipStreamSynchronize(stream));
+      copy_d2h(hP.data(), O.p, hP.size() * sizeof(T));
+      tail_n = 0;
+      check_device_error();
+      double num = 0.0, den = 0.0;
+      for (size_t i = 0; i < hP.size(); ++i) {
+        num = std::max(num, (double)std::abs(hP[i] - hO[i]));
+        den = std::max(den, (double)std::abs(hO[i]));
+      }
+      tail_probe_err = den > 0.0 ? num / den : num;
+      if (!(tail_probe_err <= tail_probe_tol)) {
+        tailG.release();
+        tail_rejected = 3;
+        return;
+      }
+    }
+    tail_level = (int64_t)l0;
+    tail_n = n;
   }
 
   // the sticky error word of the band kernels (a bounded spin expired); checked at sync points
@@ -1732,6 +1757,35 @@ class Engine : public EngineBase {
       ++count;
     }
   }
+  // the same product of a complex handle (kernels.hip.hpp k_top_gemm_z): X, Out the real views [rows][128] of the complex
+  // arrays, G two real planes; tiles and K splits as above -- from nt alone, so that a column's sum order does not depend on
+  // the batch -- and a third grid axis of column groups (32 real = 16 complex columns each; the last one may use one tile).
+  // The K splits are always added by k_top_reduce_z: there is no last-arriver variant of this kernel
+  void launch_top_gemm_z(hipStream_t st, int nt, const double *G, const double *X, const int32_t *rowmap, double *Out,
+                         int64_t &count) {
+    const int lda = (int)round_up32(nt);
+    const int tiles = (nt + 63) / 64;
+    int nks = std::max(1, std::min(kTopGemmSplits, 256 / std::max(1, tiles)));
+    int kper = (int)(((int64_t)(lda + nks - 1) / nks + 63) / 64 * 64);
+    nks = (lda + kper - 1) / kper;
+    const int ntiles = std::min(8, (act_cols + 7) / 8);  // 16-real-column tiles (8 complex columns) in use
+    const int groups = (ntiles + 1) / 2, nct = ntiles - 2 * (groups - 1);
+    const int pad = (nt + 63) / 64 * 64;
+    if (nks > 1 && gemm_part.bytes < (size_t)nks * pad * 128 * sizeof(double)) {  // (sized at finalize; cannot happen)
+      nks = 1;
+      kper = (int)((lda + 63) / 64 * 64);
+    }
+    tally(KF_TOP_GEMM_Z);
+    hipLaunchKernelGGL(nct == 1 ? k_top_gemm_z<1> : k_top_gemm_z<2>, dim3((unsigned)tiles, (unsigned)nks, (unsigned)groups), dim3(1024),
+                       kTopGemmLds, st, nt, nt, kper, G, lda, X, rowmap, Out, gemm_part.as<double>(), pad);
+    ++count;
+    if (nks > 1) {
+      tally(KF_TOP_REDUCE_Z);
+      hipLaunchKernelGGL(k_top_reduce_z, dim3((unsigned)((nt + 1) / 2)), dim3(256), 0, st, nt, nks,
+                         (const double *)gemm_part.as<double>(), pad, rowmap, Out, 16 * ntiles);
+      ++count;
+    }
+  }
   // the level's top rows: t_T = w_T - (sources outside T) by the chip-wide prefix pass, straight into the product's
   // right-hand side; then v_T = G t_T on the matrix cores (G = U_TT^{-1} D_T^{-1} L_TT^{-1}, rows scattered by L's row ids)
   void launch_top(hipStream_t st, const DevLevel &L, int logR, int64_t &count, const FL &fl) {
@@ -1764,8 +1818,18 @@ class Engine : public EngineBase {
         hipLaunchKernelGGL(k_strip_gemm4_d<4>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, ktop, L.topG.as<double>(), ktop,
                            (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0, L.v.as<double>());
     } else {
-      (void)st, (void)L, (void)logR, (void)count, (void)fl;
-      throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle");
+      if (!(zop_flags & 2)) throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle that did not ask for it");
+      const DevCsr &M = L.L;
+      const size_t b = (size_t)L.top_bandL;
+      const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
+      tally(KF_TRSV_WIDE);
+      hipLaunchKernelGGL((k_trsv_wide<cplx, true, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
+                         M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<cplx>(),
+                         M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(), logR, 1,
+                         blk_tmp.as<cplx>(), (int32_t)s1, fl);
+      ++count;  // (the prefix pass)
+      launch_top_gemm_z(st, (int)L.top_n, L.topG.as<double>(), (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0,
+                        L.v.as<double>(), count);
     }
   }
   // one component-dense band (kernels.hip.hpp k_band_cd): real data, R = 64
@@ -1809,9 +1873,9 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL(k_strip_gemm4_d<2>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, kt, tailG.as<double>(), kt,
                          (const double *)cin, (const int32_t *)nullptr, (double *)zout);
       return true;
-    } else {
-      (void)st, (void)cin, (void)zout, (void)count;
-      return false;
+    } else {  // (only a handle that asked for the operator has one: build_tail_operator)
+      launch_top_gemm_z(st, (int)tail_n, tailG.as<double>(), (const double *)cin, nullptr, (double *)zout, count);
+      return true;
     }
   }
   // LDS of k_band_cs_z: two real planes [rows][16], per row two doubles and two int32; sparse-own plans add the own nonzeros
@@ -3470,7 +3534,7 @@ class Engine : public EngineBase {
                         (double)levels_from_cache, analysis_seconds, arena, (double)Rmax, tiles, factors, (double)max_nrhs,
                         skip_w, skip_v, (double)host_repairs,
                         (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0)), ls_src, ls_dep, ls_c,
-                        cd_comps, cd_shared, ls_nch};
+                        cd_comps, cd_shared, ls_nch, (double)zop_flags};
     const int nv = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < cap && i < nv; ++i) o[i] = v[i];
     return nv;
@@ -4001,6 +4065,12 @@ int hifamd_debug_checksums(HifAmdHdl h, uint64_t *out, int cap) {
   return h->vt == HIFAMD_D ? ENG_D->debug_checksums(out, cap) : ENG_Z->debug_checksums(out, cap);
 }
 
+HifAmdStatus hifamd_set_complex_operators(HifAmdHdl h, int flags) {
+  API_BEGIN
+  DISPATCH(ENG_D->set_complex_operators(flags), ENG_Z->set_complex_operators(flags))
+  API_END
+}
+
 static const char kFileMagic[8] = {'H', 'I', 'F', 'A', 'M', 'D', '1', 0};
 
 HifAmdStatus hifamd_save(HifAmdHdl h, const char *path) { return hifamd_save_ex(h, path, 0); }
@@ -4023,7 +4093,9 @@ HifAmdStatus hifamd_save_ex(HifAmdHdl h, const char *path, int flags) {
   API_END
 }
 
-HifAmdStatus hifamd_load(const char *path, int device, HifAmdHdl *out) {
+HifAmdStatus hifamd_load(const char *path, int device, HifAmdHdl *out) { return hifamd_load_ex(path, device, 0, out); }
+
+HifAmdStatus hifamd_load_ex(const char *path, int device, int complex_operators, HifAmdHdl *out) {
   if (!out || !path) {
     set_err("NULL argument");
     return HIFAMD_NULL_OBJ;
@@ -4047,6 +4119,14 @@ HifAmdStatus hifamd_load(const char *path, int device, HifAmdHdl *out) {
   if (st != HIFAMD_SUCCESS) {
     std::fclose(f);
     return st;
+  }
+  if (complex_operators != 0) {  // (a planner choice, not data: between create and the replayed add_level calls)
+    st = hifamd_set_complex_operators(h, complex_operators);
+    if (st != HIFAMD_SUCCESS) {
+      std::fclose(f);
+      hifamd_destroy(h);
+      return st;
+    }
   }
   try {
     DISPATCH(ENG_D->load(f), ENG_Z->load(f))

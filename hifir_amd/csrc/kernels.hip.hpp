@@ -24,6 +24,8 @@
 //   k_thin_update + k_tri_gemm_d   the thin tail of a triangle in block-dense form (host.hpp plan_dense_blocks)
 //   k_gather_div / k_prod_rows / k_spmm_prod / k_scatter_div   prec_prod, alg/prec_prod.hpp:55-147
 //   k_zcombine       complex products as two real MFMA products
+//   k_top_gemm_z / k_top_reduce_z   top and tail operators of a complex handle (hifamd_set_complex_operators): both real
+//                    products in one kernel, combined across neighbouring lanes
 //   k_gm_step / k_gm_finish / k_gm_backsolve / k_gm_combine / k_gm_colop   device-resident Arnoldi process of GMRES
 //   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
 //   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
@@ -2844,6 +2846,178 @@ __global__ void __launch_bounds__(256) k_top_reduce(int nrows, int nks, const do
   double sacc = part[((int64_t)row << 6) + lane];
   for (int q = 1; q < nks; ++q) sacc += part[(((int64_t)q * nrows_pad + row) << 6) + lane];
   Out[((int64_t)(rowmap ? rowmap[row] : row) << 6) + lane] = sacc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same product for complex handles: Out[rowmap[r]] = sum_k G(r, k) X[k], G complex as the two real strip-major
+// planes [re | im] of host.hpp mfma_operand (each ceil(nrows / 16) * 16 * lda doubles), X and Out complex
+// row-interleaved [rows][64], i.e. a real view [rows][128] with (re, im) in neighbouring columns.  gfx950 has no complex
+// matrix instruction: P = G_re X and Q = G_im X are formed on the real view with the SAME B fragments, and complex
+// column j is out_re(j) = P[2j] - Q[2j+1], out_im(j) = P[2j+1] + Q[2j].  In the C/D layout col = lane & 15, so a value's
+// partner sits in the neighbouring lane: ONE cross-lane exchange per accumulator register at the very end combines
+// them.  (The alternative -- de-interleaving X while it is staged and negating the G_im fragments -- needs two panels
+// in LDS and four products per fragment pair with separate B fragments; the exchange costs 8 shuffles per lane and
+// keeps the staging a plain copy, so it is what is done here.)
+// Shape as k_top_gemm: 64-row tiles x K splits (nks, kper from the operator's size alone, never from the batch width:
+// a column's sum order does not depend on the batch), panel chunks of 64 k-rows through LDS at the 80-double row
+// stride, every global access unconditional (clamped indices; rows >= kvalid are selected to zero behind the
+// products).  The column dimension is the grid's third axis: a workgroup takes a group of 32 real columns (two
+// 16-column tiles = 16 complex columns), so its accumulators -- two planes x two tiles -- number what the real kernel's
+// four tiles do.  NCT = tiles in use in the LAST group (a batch of <= 8 columns: one group, one tile); every group in
+// front of it is full.  The K splits are never summed here (no atomics, no fences, no last arriver): nks > 1 writes
+// the combined partial tiles to part[split][row][128] and k_top_reduce_z adds them in split order.
+// ---------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void top_gemm_z_body(int nrows, int kvalid, int kper, const double *__restrict__ A, int lda,
+                                                const double *__restrict__ X, const int32_t *__restrict__ rowmap,
+                                                double *__restrict__ Out, double *__restrict__ part, int nrows_pad,
+                                                double *tg_lds) {
+  constexpr int XS = 80;  // LDS row stride of the panel (doubles)
+  double (*xb)[64 * XS] = reinterpret_cast<double (*)[64 * XS]>(tg_lds);
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int sw = wv & 3, jq = wv >> 2;  // strip within the tile, K quarter within a chunk
+  const int cl = lane & 15, kq = lane >> 4;
+  const int tile = blockIdx.x, ksp = blockIdx.y;
+  const int col0 = 32 * (int)blockIdx.z;  // first real column of this group
+  const int strip = tile * 4 + sw;
+  const int nstrips = (nrows + 15) >> 4;
+  const int64_t plane = (int64_t)nstrips * 16 * lda;  // G_im behind G_re
+  const int k0 = ksp * kper, k1 = min(k0 + kper, lda);
+  const int nchunks = (k1 - k0 + 63) >> 6;
+  v4f64 accP[NT], accQ[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) accP[t] = accQ[t] = v4f64{0.0, 0.0, 0.0, 0.0};
+  const bool live = strip < nstrips;
+  // A fragments of chunk c, both planes: k = k0 + 64 c + 16 jq + 4 u + kq.  Unconditional as in k_top_gemm: a chunk index
+  // past the end re-reads the last chunk, a dead wave the last strip; k >= lda (at most 32 columns: the next strip, the
+  // other plane or the padding behind the operand) meets panel rows >= kvalid, which are zero in LDS
+  const double *Ap = A + ((int64_t)min(strip, nstrips - 1) * lda) * 16 + cl + (int64_t)(k0 + 16 * jq + kq) * 16;
+  double ar0[4], ai0[4], ar1[4], ai1[4];
+#define HIFAMD_TGZ_A(ar, ai, c_)                                                              \
+  {                                                                                           \
+    const double *ap_ = Ap + (int64_t)min((c_), nchunks - 1) * (64 * 16);                     \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) ar[u] = ap_[u * 64];                        \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) ai[u] = ap_[plane + u * 64];                \
+  }
+  // panel chunk c: 64 rows x 32 real columns, 16 bytes per thread (a row >= kvalid reads row kvalid - 1 and selects zero)
+  typedef double v2f64 __attribute__((ext_vector_type(2)));
+  const int xr = threadIdx.x >> 4, xc = (threadIdx.x & 15) * 2;  // row 0..63, columns xc, xc + 1 of the group
+  v2f64 xs0;
+  bool xk0;
+#define HIFAMD_TGZ_XLOAD(c_)                                                                          \
+  {                                                                                                   \
+    const int r0_ = k0 + 64 * min((c_), nchunks - 1) + xr;                                            \
+    xk0 = r0_ < kvalid && xc < 16 * NT;                                                               \
+    xs0 = *reinterpret_cast<const v2f64 *>(X + ((int64_t)min(r0_, kvalid - 1) << 7) + col0 + xc);     \
+  }
+#define HIFAMD_TGZ_XSTORE(b_) *reinterpret_cast<v2f64 *>(&xb[b_][xr * XS + xc]) = xk0 ? xs0 : v2f64{0.0, 0.0};
+#define HIFAMD_TGZ_MFMA(ar, ai, b_)                                                                \
+  _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                  \
+    const double *bp_ = &xb[b_][(16 * jq + 4 * u + kq) * XS + cl];                                 \
+    _Pragma("unroll") for (int t = 0; t < NT; ++t) {                                               \
+      const double bv_ = bp_[16 * t];                                                              \
+      accP[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[u], bv_, accP[t], 0, 0, 0);                \
+      accQ[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[u], bv_, accQ[t], 0, 0, 0);                \
+    }                                                                                              \
+  }
+  // one chunk: the panel of chunk c + 1 is requested first, the A fragments of chunk c + 1 behind it (vector loads return
+  // in order: the wait in front of the panel's LDS store leaves the eight A loads in flight); a double buffer of fragment
+  // sets -- the set being multiplied and the one in flight
+#define HIFAMD_TGZ_STEP(c_, rcur, icur, rnew, inew)                            \
+  {                                                                            \
+    HIFAMD_TGZ_XLOAD((c_) + 1)                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    HIFAMD_TGZ_A(rnew, inew, (c_) + 1)                                         \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    HIFAMD_TGZ_MFMA(rcur, icur, ((c_) & 1))                                    \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    HIFAMD_TGZ_XSTORE((((c_) + 1) & 1))                                        \
+    __syncthreads();                                                           \
+  }
+  HIFAMD_TGZ_XLOAD(0)
+  HIFAMD_TGZ_A(ar0, ai0, 0)
+  HIFAMD_TGZ_XSTORE(0)
+  __syncthreads();
+  int c = 0;
+  for (; c + 2 <= nchunks; c += 2) {
+    HIFAMD_TGZ_STEP(c, ar0, ai0, ar1, ai1)
+    HIFAMD_TGZ_STEP(c + 1, ar1, ai1, ar0, ai0)
+  }
+  if (c < nchunks) HIFAMD_TGZ_STEP(c, ar0, ai0, ar1, ai1)
+#undef HIFAMD_TGZ_STEP
+#undef HIFAMD_TGZ_A
+#undef HIFAMD_TGZ_XLOAD
+#undef HIFAMD_TGZ_XSTORE
+#undef HIFAMD_TGZ_MFMA
+  // K quarters 1..3 hand their tiles to quarter 0 of the same strip, one quarter per round: the order 0, 1, 2, 3
+  // (the panel buffers are the scratch: [sw][plane][t][r][lane], 4 x 2 x 2 x 4 x 64 doubles = 32 KB)
+  double *red = &xb[0][0];
+  for (int q = 1; q < 4; ++q) {
+    if (jq == q) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          red[((((sw * 2 + 0) * 2 + t) * 4 + r) << 6) + lane] = accP[t][r];
+          red[((((sw * 2 + 1) * 2 + t) * 4 + r) << 6) + lane] = accQ[t][r];
+        }
+    }
+    __syncthreads();
+    if (jq == 0) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          accP[t][r] += red[((((sw * 2 + 0) * 2 + t) * 4 + r) << 6) + lane];
+          accQ[t][r] += red[((((sw * 2 + 1) * 2 + t) * 4 + r) << 6) + lane];
+        }
+    }
+    __syncthreads();
+  }
+  if (jq != 0 || !live) return;  // (whole waves)
+  const bool odd = (cl & 1) != 0;  // an even lane holds the real part's column 2j, its neighbour the imaginary part's 2j + 1
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double z[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const double qn = __shfl_xor(accQ[t][r], 1);  // (every lane of the wave takes part: in front of the row test)
+      z[t] = odd ? accP[t][r] + qn : accP[t][r] - qn;
+    }
+    const int row = 16 * strip + kq + 4 * r;
+    if (row >= nrows) continue;
+    double *dst = ((gridDim.y > 1) ? part + (((int64_t)ksp * nrows_pad + row) << 7) : Out + ((int64_t)(rowmap ? rowmap[row] : row) << 7)) + col0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dst[16 * t + cl] = z[t];
+  }
+}
+
+// NCT = 1 carries BOTH bodies: the two-tile one for the full groups in front (blockIdx.z + 1 < gridDim.z) and the one-tile
+// one for the last group, chosen by a branch that is uniform over the workgroup.  That is why k_top_gemm_z<1> is the
+// larger code object of the two (98 VGPRs against 96 of <2>, whose single body the compiler sees alone); a batch of
+// <= 8 columns has one group and runs the one-tile body only.
+template <int NCT>
+__global__ void __launch_bounds__(1024) k_top_gemm_z(int nrows, int kvalid, int kper /* K range per split, multiple of 64 */,
+                                                     const double *__restrict__ A, int lda, const double *__restrict__ X,
+                                                     const int32_t *__restrict__ rowmap, double *__restrict__ Out,
+                                                     double *__restrict__ part, int nrows_pad) {
+  extern __shared__ double tgz_lds[];  // two chunks of 64 panel rows at stride 80; reused for the reduction
+  if (NCT == 2 || blockIdx.z + 1 < gridDim.z)  // (uniform over the workgroup)
+    top_gemm_z_body<2>(nrows, kvalid, kper, A, lda, X, rowmap, Out, part, nrows_pad, tgz_lds);
+  else
+    top_gemm_z_body<1>(nrows, kvalid, kper, A, lda, X, rowmap, Out, part, nrows_pad, tgz_lds);
+}
+
+// the K splits of k_top_gemm_z, added in split order: a row of the real view has 128 columns, ncols of them in use
+__global__ void __launch_bounds__(256) k_top_reduce_z(int nrows, int nks, const double *__restrict__ part, int nrows_pad,
+                                                      const int32_t *__restrict__ rowmap, double *__restrict__ Out, int ncols) {
+  const int col = threadIdx.x & 127;
+  const int row = blockIdx.x * 2 + (threadIdx.x >> 7);
+  if (row >= nrows || col >= ncols) return;
+  double sacc = part[((int64_t)row << 7) + col];
+  for (int q = 1; q < nks; ++q) sacc += part[(((int64_t)q * nrows_pad + row) << 7) + col];
+  Out[((int64_t)(rowmap ? rowmap[row] : row) << 7) + col] = sacc;
 }
 
 // ---------------------------------------------------------------------------------------------

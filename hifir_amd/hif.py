@@ -25,6 +25,7 @@ STATUS = {0: "HIFAMD_SUCCESS", 1: "HIFAMD_NULL_OBJ", 2: "HIFAMD_MISMATCHED_SIZES
 
 
 OP_S, OP_SH, OP_M, OP_MH = 0, 1, 2, 3  # HifAmdOp == LhfOperationType (libhifir.h:159-164)
+ZOP_TAIL, ZOP_TOP = 1, 2  # HIFAMD_ZOP_*: explicit operators a complex handle forms on request (hifamd_set_complex_operators)
 
 
 class HifAmdError(RuntimeError):
@@ -57,17 +58,25 @@ def _np_dtype_of(t):
 class HIF:
     """A multilevel preconditioner resident on one MI355X."""
 
-    def __init__(self, dtype=np.float64, device=-1):
+    def __init__(self, dtype=np.float64, device=-1, complex_operators=0):
+        """complex_operators: ZOP_TAIL | ZOP_TOP -- a complex handle forms the tail operator / the combined top operators
+        that real handles always have (hifamd_set_complex_operators; 0: the default plan of complex handles)."""
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float64), np.dtype(np.complex128)):
             raise HifAmdError(3, "only float64 and complex128 hierarchies are supported")
         self._h = C.c_void_p()
         _check(lib().hifamd_create(0 if self.dtype == np.float64 else 1, device, C.byref(self._h)))
         self._A = None
+        if complex_operators:
+            self.set_complex_operators(complex_operators)
+
+    def set_complex_operators(self, flags):
+        """Before the first add_level, complex handles only (hifamd_set_complex_operators)."""
+        _check(lib().hifamd_set_complex_operators(self._h, int(flags)))
 
     # ---- construction --------------------------------------------------------------------------
     @classmethod
-    def from_levels(cls, levels, max_nrhs=64, rrqr_cond=0.0, device=-1, dtype=None):
+    def from_levels(cls, levels, max_nrhs=64, rrqr_cond=0.0, device=-1, dtype=None, complex_operators=0):
         """levels: list of dicts with the fields of hif::Prec (alg/Prec.hpp:309-323), CCS matrices:
         m, n, {L,U,E,F}_{colptr,rowind,vals}, d, s, t, p, q_inv (+ p_inv, q), and on the last one
         optionally dense_n, dense (unfactored column-major Schur complement); dense_symm (+ spd) marks the block of
@@ -76,7 +85,7 @@ class HIF:
             cplx = any(np.iscomplexobj(lv["L_vals"]) or np.iscomplexobj(lv["d"]) or np.iscomplexobj(lv["E_vals"])
                        for lv in levels)
             dtype = np.complex128 if cplx else np.float64
-        self = cls(dtype, device)
+        self = cls(dtype, device, complex_operators)
         for lv in levels:
             self.add_level(lv)
         last = levels[-1]
@@ -97,12 +106,13 @@ class HIF:
         _check(lib().hifamd_save_ex(self._h, os.fsencode(path), 1 if analysis else 0))
 
     @classmethod
-    def load(cls, path, max_nrhs=64, device=-1):
-        """Read a hierarchy written by save() and ship it to the device (hifamd_load + finalize)."""
+    def load(cls, path, max_nrhs=64, device=-1, complex_operators=0):
+        """Read a hierarchy written by save() and ship it to the device (hifamd_load_ex + finalize).  The file does not
+        hold the complex_operators of the handle that wrote it: they are the reader's choice."""
         self = cls.__new__(cls)
         self._h = C.c_void_p()
         self._A = None
-        _check(lib().hifamd_load(os.fsencode(path), device, C.byref(self._h)))
+        _check(lib().hifamd_load_ex(os.fsencode(path), device, int(complex_operators), C.byref(self._h)))
         with open(path, "rb") as f:
             f.seek(8)
             self.dtype = np.dtype(np.complex128 if int.from_bytes(f.read(8), "little") == 1 else np.float64)
@@ -216,6 +226,13 @@ class HIF:
         # component bands (slots 26 / 27): their components, and the workgroups that own more than one of them
         out.update({key: float(s[26 + i]) for i, key in enumerate(("cd_components", "cd_shared_workgroups")) if 26 + i < k})
         return out
+
+    def complex_operators(self):
+        """The flags of hifamd_set_complex_operators in force (hifamd_stats_ext slot 29; real handles: 0).  A method of its
+        own, like ls_stats(): the keys of stats_ext() are counted by tests/test_nsp_basis_host.py."""
+        s = np.zeros(32)
+        k = lib().hifamd_stats_ext(self._h, _p(s), 32)
+        return int(s[29]) if k > 29 else 0
 
     def ls_stats(self):
         """Sparse-own L bands that run with streamed sources (hifamd_stats_ext slots 23-25 and 28): rows streamed as sources,

@@ -104,6 +104,19 @@ HifAmdStatus hifamd_set_dense_lup(HifAmdHdl h, int64_t nd, const void *mat_colma
  * HBM and sizes the work arena for batches of up to max_nrhs (the reference sizes its work buffer
  * on first use only, builder.hpp:414-416 -- not replicated). */
 HifAmdStatus hifamd_finalize(HifAmdHdl h, int64_t max_nrhs);
+/* Complex handles only, and only before the first hifamd_add_level (the flags are planner options: they shape the
+ * analysis of every level).  Real handles form two explicit operators at hifamd_finalize that complex handles do not
+ * have by default: the closed top of every L / U triangle pair as one dense product, and the tail of the hierarchy (from
+ * the first level of at most 4,096 rows through the dense block) as one dense product, guarded by the finalize-time
+ * probe of hifamd_stats_ext slots 7-11.  The flags ask for them on this handle; their products run on the f64 matrix
+ * cores as two real products per complex one.  Opt-in because the kernel families a default complex handle launches
+ * are pinned by the test suite; a handle created without this call plans, launches and answers as before.
+ * Refusals, in this order: NULL handle HIFAMD_NULL_OBJ; flags outside 0 ... 3 HIFAMD_MISMATCHED_SIZES; a real handle
+ * with flags != 0 HIFAMD_BAD_PREC (it has both operators already); a handle that has a level or is finalized
+ * HIFAMD_BAD_PREC.  Flags 0 is a no-op.  hifamd_save(_ex) does not store the flags: pass them to hifamd_load_ex. */
+#define HIFAMD_ZOP_TAIL 1 /* tail of the hierarchy as one operator */
+#define HIFAMD_ZOP_TOP 2  /* closed top of every triangle pair as one operator */
+HifAmdStatus hifamd_set_complex_operators(HifAmdHdl h, int flags);
 
 /* ---- on-disk form of an imported hierarchy ---------------------------------- */
 /* hifamd_save writes exactly what hifamd_add_level / hifamd_set_dense received (before or after
@@ -115,6 +128,10 @@ HifAmdStatus hifamd_finalize(HifAmdHdl h, int64_t max_nrhs);
  * counted arrays; the dense block as int64 nd, double rrqr_cond and a counted column-major array. */
 HifAmdStatus hifamd_save(HifAmdHdl h, const char *path);
 HifAmdStatus hifamd_load(const char *path, int device, HifAmdHdl *out);
+/* hifamd_load with hifamd_set_complex_operators(h, complex_operators) applied between the creation of the handle and
+ * the replayed hifamd_add_level calls; hifamd_load is this call with 0.  An analysis trailer written under other flags
+ * does not fit the planner options in force and is ignored: the levels are analyzed afresh. */
+HifAmdStatus hifamd_load_ex(const char *path, int device, int complex_operators, HifAmdHdl *out);
 /* hifamd_save with options.  HIFAMD_SAVE_ANALYSIS appends the ANALYSIS of every level (wavefront schedules, band plans,
  * slot-ordered triangles: what hifamd_add_level derives on the host, e.g. 24 s of the 45 s between load and first apply
  * on a 256^3 grid) as a checksummed trailer behind the records above.  hifamd_load adopts it when it was made with the
@@ -157,7 +174,8 @@ HifAmdStatus hifamd_stats(HifAmdHdl h, double *stats16);
  * of that kernel's source chunk (0: no band runs through it),
  * 26 components of all component bands (L and U, every level), 27 workgroups of those bands that own more than one
  * component (the planner chains components once a band has more than 8 * HIFIR_AMD_BAND_WGS of them, and bags small
- * ones), 28 the largest number of source chunks per component of any band that runs through k_band_ls.
+ * ones), 28 the largest number of source chunks per component of any band that runs through k_band_ls, 29 the flags of
+ * hifamd_set_complex_operators in force (real handles: 0).  Slots 3-11 are filled for complex handles as for real ones.
  * -1 for a NULL handle. */
 int hifamd_stats_ext(HifAmdHdl h, double *out, int cap);
 /* Per-level sizes (what the SURVEY 8(d) byte formula needs level by level): 0 m, 1 n, 2 nnz(L_B), 3 nnz(U_B), 4 nnz(E),

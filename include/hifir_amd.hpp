@@ -61,11 +61,16 @@ class HIF {
   typedef ValueType value_type;
   typedef std::size_t size_type;
 
-  explicit HIF(int device = -1) : _h(nullptr), _device(device), _has_A(false) {}
+  explicit HIF(int device = -1) : _h(nullptr), _device(device), _has_A(false), _zop(0) {}
   ~HIF() { clear(); }
   HIF(const HIF &) = delete;
   HIF &operator=(const HIF &) = delete;
-  HIF(HIF &&o) noexcept : _h(o._h), _device(o._device), _has_A(o._has_A) { o._h = nullptr; }
+  HIF(HIF &&o) noexcept : _h(o._h), _device(o._device), _has_A(o._has_A), _zop(o._zop) { o._h = nullptr; }
+
+  /// Complex hierarchies: the explicit operators the next attach() asks for (HIFAMD_ZOP_TAIL | HIFAMD_ZOP_TOP,
+  /// hifamd_set_complex_operators; 0, the default, keeps the plan complex handles always had).  They are planner options,
+  /// fixed when the levels are imported: a hierarchy that is already attached keeps the ones it was attached with.
+  void set_complex_operators(const int flags) { _zop = flags; }
 
   /// Ship the hierarchy of a factorized hif::HIF (or anything with the same precs() interface,
   /// alg/Prec.hpp:309-357) to HBM.  max_nrhs sizes the device work arena (wider batches are tiled).
@@ -75,6 +80,7 @@ class HIF {
     clear();
     detail::check(hifamd_create(detail::value_tag<value_type>::value(), _device, &_h));
     try {
+      if (_zop) detail::check(hifamd_set_complex_operators(_h, _zop));
       for (auto itr = M.precs().cbegin(); itr != M.precs().cend(); ++itr) {
         const auto &p = *itr;
         // CCS accessors: ds/CompressedStorage.hpp:1910-1915; pointer type may be any integer
@@ -300,6 +306,7 @@ class HIF {
   HifAmdHdl _h;
   int _device;
   bool _has_A;
+  int _zop;  // set_complex_operators: applied by attach()
 };
 
 }  // namespace hifamd
