@@ -144,6 +144,14 @@ class Oracle:
         assert self._f("mmultiply_tran" if trans else "mmultiply")(self.h, _p(x), _p(y), rank) == 0
         return y
 
+    def mmultiply_batch(self, X, rank=0, trans=False):
+        """X: (n, nrhs) row-interleaved.  Column by column through mmultiply (the C side has no batch entry for it)."""
+        X = np.ascontiguousarray(X, dtype=self.dtype)
+        Y = np.empty_like(X)
+        for c in range(X.shape[1]):
+            Y[:, c] = self.mmultiply(np.ascontiguousarray(X[:, c]), rank=rank, trans=trans)
+        return Y
+
     def hifir(self, indptr, indices, vals, b, nirs, betas=None, rank=-1):
         indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         indices = np.ascontiguousarray(indices, dtype=np.int32)

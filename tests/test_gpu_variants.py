@@ -134,15 +134,23 @@ CPLX = ("kkt", "young", "synthz", "blocksz")
 _cache = {}
 
 
+def _levels(name):
+    """levels and their value type: once per hierarchy (test_gpu_product.py builds its own batch on the same levels)."""
+    key = ("levels", name)
+    if key not in _cache:
+        levels = HIERS[name]()
+        z = any(np.iscomplexobj(lv["L_vals"]) or np.iscomplexobj(lv["d"]) for lv in levels)
+        _cache[key] = (levels, np.complex128 if z else np.float64)
+    return _cache[key]
+
+
 def _hier(name):
     """levels, the 100-column batch and the oracle's two answers: once per hierarchy, never written to."""
     key = ("hier", name)
     if key not in _cache:
         from oracle import orc
 
-        levels = HIERS[name]()
-        z = any(np.iscomplexobj(lv["L_vals"]) or np.iscomplexobj(lv["d"]) for lv in levels)
-        dtype = np.complex128 if z else np.float64
+        levels, dtype = _levels(name)
         n = int(levels[0]["n"])
         B = rand_rhs(np.random.default_rng(41), (n, 100), dtype)
         O = orc.Oracle(levels, dtype=dtype)
