@@ -3378,6 +3378,150 @@ class Engine : public EngineBase {
     HIP_OK(hipStreamSynchronize(stream));
   }
 
+  // ---- symmetric QMR for a Hermitian indefinite pair, batched over columns ---------------------------
+  // PCG's coupled two-term recurrence without the positivity requirement, plus the quasi-minimal-residual smoothing of
+  // Freund and Nachtigal: x0 = 0, r = s = b, tau = ||b||, theta = 0, d = g = 0, z = M^{-1} r, rho = r^H z, p = z; per
+  // iteration q = A p, sigma = p^H q, alpha = rho / sigma, r -= alpha q, theta' = ||r|| / tau, c^2 = 1 / (1 + theta'^2),
+  // tau = tau theta' sqrt(c^2), eta = c^2 theta^2, zeta = c^2 alpha, theta = theta', d = eta d + zeta p,
+  // g = eta g + zeta q, x += d, s -= g (s = b - A x by recurrence), stop on ||s|| / ||b|| <= rtol, z = M^{-1} r,
+  // rho' = r^H z, p = z + (rho' / rho) p.  One apply and one SpMM per iteration (PCG's unit), seven work vectors
+  // r, z, p, q, d, g, s.  Up to 64 columns in lock step, per-column scalars in HBM (QmState), every reduction closed by
+  // k_qm_finish; the host reads the active count once per iteration, after the convergence test.  Only for a Hermitian
+  // M^{-1} (import.hpp check_hermitian); a breakdown is rho or sigma exactly zero or not finite.  With a basis filter on
+  // HIFAMD_S the iteration runs projected as PCG's does.  Flags 0 converged / 1 breakdown / 2 reached maxit.
+  DevBuf qm_r, qm_z, qm_p, qm_q, qm_d, qm_g, qm_s, qm_state;
+
+  QmState<D> qm_make_state(double rtol, int maxit) {
+    const size_t o_sc = 0, o_re = o_sc + 4 * 64 * sizeof(D), o_int = o_re + 4 * 64 * sizeof(double),
+                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
+    if (qm_state.bytes < bytes) qm_state.alloc(bytes);
+    HIP_OK(hipMemsetAsync(qm_state.p, 0, bytes, stream));
+    char *b = qm_state.as<char>();
+    QmState<D> S;
+    S.rho = (D *)(b + o_sc);
+    S.alpha = S.rho + 64;
+    S.beta = S.rho + 128;
+    S.zeta = S.rho + 192;
+    S.eta = (double *)(b + o_re);
+    S.tau = S.eta + 64;
+    S.theta = S.eta + 128;
+    S.bnorm = S.eta + 192;
+    int *ib = (int *)(b + o_int);
+    S.iter = ib;
+    S.flag = ib + 64;
+    S.active = ib + 128;
+    S.ctl = ib + 192;
+    S.maxit = maxit;
+    S.rtol = rtol;
+    return S;
+  }
+  int qm_active(const QmState<D> &S) {
+    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return cg_pin[0];
+  }
+
+  void sqmr_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank, int *flags,
+                 int *iters) {
+    const int64_t n = lv[0]->n;
+    const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
+    for (DevBuf *b : {&qm_r, &qm_z, &qm_p, &qm_q, &qm_d, &qm_g, &qm_s})
+      if (b->bytes < vec) b->alloc(vec);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
+    D *r = qm_r.as<D>(), *z = qm_z.as<D>(), *p = qm_p.as<D>(), *q = qm_q.as<D>(), *d = qm_d.as<D>(), *g = qm_g.as<D>(),
+      *s = qm_s.as<D>(), *pt = ir_part.as<D>();
+    StreamWait wait{stream};
+    const QmState<D> S = qm_make_state(rtol, maxit);
+    CgState<D> Sp{};  // what k_cg_p reads: beta and the active mask
+    Sp.beta = S.beta;
+    Sp.active = S.active;
+    const dim3 grid(kCgBlocks), blk(256);
+    auto dot = [&](const D *a, const D *b) { hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, a, b, pt); };
+    auto finish = [&](int mode, int k) {
+      hipLaunchKernelGGL((k_qm_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, mode, k, S);
+    };
+    vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);  // r = b
+    // projected: with a basis filter P = I - Q Q^H on the solve, r0 = s0 = P b, ||b|| := ||P b||, and every
+    // z = M^{-1} r below is already P M^{-1} r (solve_dev filters it)
+    if (nsp_k > 0) apply_nsp(r, nc, nc, stream);
+    dot(r, nullptr);
+    finish(0, 0);                                           // ||b||, tau
+    vec_op(1, n, nc, s, nc, (const D *)r, nc, nullptr, 0);  // s = r
+    vec_op(0, n, nc, d, nc, nullptr, 0, nullptr, 0);        // d = g = 0, x = 0
+    vec_op(0, n, nc, g, nc, nullptr, 0, nullptr, 0);
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);
+    solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);  // z = M^{-1} r
+    dot(r, z);
+    finish(1, 0);                                           // rho = r^H z
+    vec_op(1, n, nc, p, nc, (const D *)z, nc, nullptr, 0);  // p = z
+    HIP_OK(hipGetLastError());
+    // (one read-back per iteration, after the convergence test; a column that breaks down in mode 5 costs one frozen pass)
+    for (int k = 0, go = qm_active(S); k < maxit && go > 0; ++k) {
+      spmv_dev((const D *)p, nc, q, nc, nc, nullptr);       // q = A p
+      dot(p, q);
+      finish(2, k);                                         // alpha = rho / p^H q
+      hipLaunchKernelGGL((k_qm_r<D>), grid, blk, 0, stream, n, nc, r, (const D *)q, S, pt);
+      finish(3, k);                                         // theta, c^2, tau, eta, zeta
+      hipLaunchKernelGGL((k_qm_ds<D>), grid, blk, 0, stream, n, nc, dX, ldx, s, d, g, (const D *)p, (const D *)q, S, pt);
+      finish(4, k);                                         // ||s|| / ||b||, maxit
+      if ((go = qm_active(S)) == 0) break;
+      solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);
+      dot(r, z);
+      finish(5, k);                                         // beta = rho' / rho
+      hipLaunchKernelGGL((k_cg_p<D>), grid, blk, 0, stream, n, nc, p, (const D *)z, Sp);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+    for (int c = 0; c < nc; ++c) {
+      if (iters) iters[c] = cg_pin[1 + c];
+      if (flags) flags[c] = cg_pin[65 + c];
+    }
+  }
+
+  void sqmr_check(int maxit, double rtol) {
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "symmetric QMR needs the matrix (hifamd_set_matrix)");
+    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
+    const HermCheck &hc = hermitian();
+    if (!hc.ok)
+      throw Error(HIFAMD_BAD_PREC, "symmetric QMR needs a Hermitian preconditioner and this hierarchy is not one (level " +
+                                       std::to_string(hc.level) + ": " + hc.what +
+                                       "); factorize a Hermitian matrix with is_symm, or use GMRES or BiCGSTAB");
+    if (nsp_on)
+      throw Error(HIFAMD_BAD_PREC, "symmetric QMR does not support a constant null-space filter (hifamd_set_nsp_const)");
+  }
+
+  void sqmr_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+                int *flags, int *iters) {
+    check_batch(dB, ldb, dX, ldx, nrhs);
+    sqmr_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
+      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+      sqmr_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr, iters ? iters + c0 : nullptr);
+    }
+  }
+
+  void sqmr_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
+                 int *flags, int *iters) {
+    check_batch(B, ldb, X, ldx, nrhs);
+    sqmr_check(maxit, rtol);
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * nrhs * sizeof(T);
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
+    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyHostToDevice, stream));
+    sqmr_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
+                            hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
   // ---- on-disk form of the imported hierarchy (import.hpp save_hierarchy / load_hierarchy) -----------------
   void save(std::FILE *f, int flags = 0) const {
     if (adjoint || is_twin) throw Error(HIFAMD_HIFIR_ERROR, "internal engines are not saved");
@@ -4356,6 +4500,22 @@ HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb,
   API_BEGIN
   DISPATCH(ENG_D->bicgstab_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
            ENG_Z->bicgstab_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_sqmr_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, double rtol,
+                               int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->sqmr_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->sqmr_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_sqmr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                   double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->sqmr_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
+           ENG_Z->sqmr_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
   API_END
 }
 

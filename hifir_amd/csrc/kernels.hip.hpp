@@ -29,6 +29,8 @@
 //   k_gm_step / k_gm_finish / k_gm_backsolve / k_gm_combine / k_gm_colop   device-resident Arnoldi process of GMRES
 //   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
 //   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
+//   k_qm_r / k_qm_ds / k_qm_finish   device-resident symmetric QMR for Hermitian indefinite pairs (same reductions;
+//                    with k_cg_dot and k_cg_p)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -2260,6 +2262,162 @@ __global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, co
       S.alpha[c] = vzero(T());
       S.omega[c] = vzero(T());
       S.beta[c] = vzero(T());
+      act = 0;
+    }
+    S.active[c] = act;
+    if (act) atomicAdd(&cnt, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) S.ctl[0] = cnt;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident symmetric QMR (Freund / Nachtigal) for a Hermitian INDEFINITE pair (A, M) with x0 = 0, up to 64
+// columns in lock step (Engine::sqmr_tile): PCG's coupled two-term recurrence without the positivity requirement, plus
+// the quasi-minimal-residual smoothing of the iterates (d, g, x, s; s = b - A x by recurrence).  Same layout and row walk
+// as k_cg_*: vectors [n][nc], lane = column, wave w of block b owns the rows i = 4 b + w + k * 4 kCgBlocks, wave
+// partials added in wave order and the kCgBlocks block partials of a column in k_cg_finish's order by k_qm_finish; a
+// column's bits do not depend on the batch it travels in.  k_cg_dot and k_cg_p serve the inner products and p = z + beta p.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+struct QmState {
+  T *rho, *alpha, *beta, *zeta;            // [64]  r^H z, rho / sigma, rho' / rho, c^2 alpha (0 for a frozen column)
+  double *eta, *tau, *theta, *bnorm;       // [64]  c^2 theta_old^2, the quasi-residual norm, ||r|| / tau_old, ||b||
+  int *iter, *flag, *active;               // [64]
+  int *ctl;                                // [0] columns still active
+  int maxit;
+  double rtol;
+};
+
+// a where the column is active, b where it is frozen (component by component: no branch, no stack object)
+__device__ __forceinline__ double qm_sel(bool act, double a, double b) { return act ? a : b; }
+__device__ __forceinline__ cplx qm_sel(bool act, cplx a, cplx b) { return cplx{act ? a.x : b.x, act ? a.y : b.y}; }
+
+// r -= alpha q on the active columns, fused with the block's share of |r|^2: two vectors read, one written.  Every
+// access is unconditional (a frozen column stores back the bits it loaded), so the pass stays pipelined.
+template <class T>
+__global__ void __launch_bounds__(256) k_qm_r(int64_t n, int nc, T *__restrict__ r, const T *__restrict__ q, QmState<T> S,
+                                              T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc) {
+    const bool act = S.active[c] != 0;
+    const T al = S.alpha[c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      const T r0 = r[i * nc + c], qi = q[i * nc + c];
+      const T r1 = vsub(r0, vmul(al, qi));
+      const T ri = qm_sel(act, r1, r0);
+      r[i * nc + c] = ri;
+      acc = vadd(acc, vfromreal(vabs2(ri), T()));
+    }
+  }
+  cg_block_partial(acc, sm, partial);
+}
+
+// d = eta d + zeta p, g = eta g + zeta q, x += d, s -= g on the active columns, fused with the block's share of |s|^2
+// (x: row stride ldx): six vectors read, four written, each element once.  Unconditional accesses as in k_qm_r.
+template <class T>
+__global__ void __launch_bounds__(256) k_qm_ds(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ s,
+                                               T *__restrict__ d, T *__restrict__ g, const T *__restrict__ p,
+                                               const T *__restrict__ q, QmState<T> S,
+                                               T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc) {
+    const bool act = S.active[c] != 0;
+    const double et = S.eta[c];
+    const T ze = S.zeta[c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      const int64_t e = i * nc + c, ex = i * ldx + c;
+      const T d0 = d[e], g0 = g[e], pi = p[e], qi = q[e], x0 = x[ex], s0 = s[e];
+      const T d1 = vadd(vscale(et, d0), vmul(ze, pi));
+      const T g1 = vadd(vscale(et, g0), vmul(ze, qi));
+      const T si = qm_sel(act, vsub(s0, g1), s0);
+      d[e] = qm_sel(act, d1, d0);
+      g[e] = qm_sel(act, g1, g0);
+      x[ex] = qm_sel(act, vadd(x0, d1), x0);
+      s[e] = si;
+      acc = vadd(acc, vfromreal(vabs2(si), T()));
+    }
+  }
+  cg_block_partial(acc, sm, partial);
+}
+
+// Sums the kCgBlocks partials of every column in k_cg_finish's order and does the per-column scalar work of iteration k.
+// alpha and beta are formed as k_cg_finish modes 1, 2 and 4 form them; a breakdown value is exactly zero or not finite
+// (bs_bad), with no sign test:
+//   mode 0: ||b||: the state, tau = ||b||, theta = 0; a zero column is done (x = 0, flag 0, 0 iterations)
+//   mode 1: rho = r^H z of the start                                   (bad: flag 1, 0 iterations)
+//   mode 2: sigma = p^H A p: alpha = rho / sigma                       (bad: flag 1, k iterations)
+//   mode 3: |r|^2 after r -= alpha q: theta' = ||r|| / tau, c^2 = 1 / (1 + theta'^2), tau = tau theta' sqrt(c^2),
+//           eta = c^2 theta^2, zeta = c^2 alpha, theta = theta'
+//   mode 4: |s|^2 after the smoothed update: ||s|| / ||b|| <= rtol -> flag 0, k + 1 iterations; k + 1 == maxit -> flag 2
+//   mode 5: rho' = r^H z: beta = rho' / rho, rho = rho'                (bad: flag 1, k + 1 iterations)
+// A column that stops gets alpha = beta = zeta = eta = 0 and active = 0; ctl[0] = columns still active.
+template <class T>
+__global__ void __launch_bounds__(1024) k_qm_finish(const T *__restrict__ partial, int nc, int mode, int k, QmState<T> S) {
+  __shared__ T sm[16 * 64];
+  __shared__ int cnt;
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  T acc = vzero(T());
+  if (c < nc)
+    for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, partial[(int64_t)b * 64 + c]);
+  sm[threadIdx.x] = acc;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  if (threadIdx.x < nc) {
+    T tot = vzero(T());
+    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
+    int act = S.active[c];
+    int stop = -1, it = 0;  // flag and iterations of a column that stops here
+    if (mode == 0) {
+      const double bn = sqrt(vreal(tot));
+      S.bnorm[c] = bn;
+      S.tau[c] = bn;
+      S.theta[c] = 0.0;
+      S.eta[c] = 0.0;
+      S.iter[c] = 0;
+      S.flag[c] = 0;
+      S.alpha[c] = vzero(T());
+      S.beta[c] = vzero(T());
+      S.zeta[c] = vzero(T());
+      act = !(bn == 0.0);
+    } else if (act && mode == 1) {
+      if (bs_bad(tot)) stop = 1, it = 0;
+      else S.rho[c] = tot;
+    } else if (act && mode == 2) {
+      if (bs_bad(tot)) stop = 1, it = k;
+      else S.alpha[c] = vdiv(S.rho[c], tot);
+    } else if (act && mode == 3) {
+      const double th0 = S.theta[c], ta = S.tau[c];
+      const double th = sqrt(vreal(tot)) / ta;
+      const double c2 = 1.0 / (1.0 + th * th);
+      S.tau[c] = ta * th * sqrt(c2);
+      S.eta[c] = c2 * th0 * th0;
+      S.zeta[c] = vscale(c2, S.alpha[c]);
+      S.theta[c] = th;
+    } else if (act && mode == 4) {
+      if (sqrt(vreal(tot)) / S.bnorm[c] <= S.rtol) stop = 0, it = k + 1;
+      else if (k + 1 >= S.maxit) stop = 2, it = S.maxit;
+    } else if (act && mode == 5) {
+      if (bs_bad(tot)) {
+        stop = 1, it = k + 1;
+      } else {
+        S.beta[c] = vdiv(tot, S.rho[c]);
+        S.rho[c] = tot;
+      }
+    }
+    if (stop >= 0) {
+      S.flag[c] = stop;
+      S.iter[c] = it;
+      S.alpha[c] = vzero(T());
+      S.beta[c] = vzero(T());
+      S.zeta[c] = vzero(T());
+      S.eta[c] = 0.0;
       act = 0;
     }
     S.active[c] = act;

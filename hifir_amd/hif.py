@@ -409,8 +409,8 @@ class HIF:
     def set_nsp_basis(self, V, trans=False):
         """Basis mode of the null-space filter (hifamd_set_nsp_basis): V, (n,) or (n, k) with 1 <= k <= 16, spans the
         null space; after every solve (trans: every M^{-H} solve), also inside hifir / gmres / bicgstab, each column x
-        becomes x - Q (Q^H x) with Q an orthonormal basis of span(V).  None removes it.  With a basis set, pcg() runs
-        projected on the complement of span(Q)."""
+        becomes x - Q (Q^H x) with Q an orthonormal basis of span(V).  None removes it.  With a basis set, pcg() and
+        sqmr() run projected on the complement of span(Q)."""
         op = OP_SH if trans else OP_S
         if V is None:
             _check(lib().hifamd_set_nsp_basis(self._h, op, 0, None, 0))
@@ -611,6 +611,33 @@ class HIF:
             it = np.zeros(B.shape[1], dtype=np.int32)
             _check(lib().hifamd_pcg_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
                                          int(maxit), rank, _p(fl), _p(it)))
+        if vec:
+            return X.reshape(-1), int(fl[0]), int(it[0])
+        return X, fl, it
+
+    def sqmr(self, b, rtol=1e-6, maxit=500, full_rank=False):
+        """Symmetric QMR (Freund / Nachtigal, x0 = 0) for a Hermitian pair (A, M) that may be indefinite, all columns of b
+        ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix and is_hermitian().
+        One apply plus one SpMM per iteration.  Returns (x, flags, iters); ints for a vector.  flags: 0 converged,
+        1 breakdown, 2 reached maxit."""
+        vec = (b.ndim == 1)
+        rank = -1 if full_rank else 0
+        if _is_torch(b):
+            import torch
+
+            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
+            X = torch.empty_like(B)
+            fl = np.zeros(B.shape[1], dtype=np.int32)
+            it = np.zeros(B.shape[1], dtype=np.int32)
+            _check(lib().hifamd_sqmr_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0), B.shape[1],
+                                              float(rtol), int(maxit), rank, _p(fl), _p(it)))
+        else:
+            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
+            X = np.empty_like(B)
+            fl = np.zeros(B.shape[1], dtype=np.int32)
+            it = np.zeros(B.shape[1], dtype=np.int32)
+            _check(lib().hifamd_sqmr_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
+                                          int(maxit), rank, _p(fl), _p(it)))
         if vec:
             return X.reshape(-1), int(fl[0]), int(it[0])
         return X, fl, it

@@ -257,8 +257,8 @@ HifAmdStatus hifamd_set_nsp_const(HifAmdHdl h, HifAmdOp op, int64_t start, int64
  * norm before, the rank criterion of the dense level, QRCP.hpp:110-117) HIFAMD_BAD_PREC, the message naming the
  * vector's index.  A column's filtered bits do not depend on the batch it travels in.
  * Krylov drivers: GMRES / FGMRES and BiCGSTAB keep their semantics, the filter acts on their applies only -- a caller
- * who wants a consistent right-hand side calls hifamd_nsp_filter_batch on it first.  PCG with a basis on HIFAMD_S runs
- * projected (see hifamd_pcg_batch). */
+ * who wants a consistent right-hand side calls hifamd_nsp_filter_batch on it first.  PCG and symmetric QMR with a basis
+ * on HIFAMD_S run projected (see hifamd_pcg_batch, hifamd_sqmr_batch). */
 #define HIFAMD_NSP_MAX 16
 HifAmdStatus hifamd_set_nsp_basis(HifAmdHdl h, HifAmdOp op, int64_t k, const void *V, int64_t ldv);
 /* vectors of the basis filter in force on op (0: none or constant mode; -1: NULL handle) */
@@ -400,6 +400,35 @@ HifAmdStatus hifamd_bicgstab_batch(HifAmdHdl h, const void *B, int64_t ldb, void
                                    double rtol, int maxit, int64_t rank, int *flags, int *iters);
 HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                        double rtol, int maxit, int64_t rank, int *flags, int *iters);
+
+/* ---- symmetric QMR for a Hermitian INDEFINITE pair (A, M), batched ---------------------------- */
+/* The symmetric QMR of Freund and Nachtigal with x0 = 0 for nrhs columns in lock step: PCG's coupled two-term
+ * recurrence without the positivity requirement (A M^{-1} is self-adjoint in the indefinite form induced by M^{-1}),
+ * plus a quasi-minimal-residual smoothing of the iterates:
+ *   r = b; s = b; tau = ||b||; theta = 0; d = g = 0; z = M^{-1} r; rho = (r, z); p = z
+ *   per iteration: q = A p; sigma = (p, q); alpha = rho / sigma; r -= alpha q;
+ *     theta' = ||r|| / tau; c2 = 1 / (1 + theta'^2); tau = tau theta' sqrt(c2); eta = c2 theta^2; zeta = c2 alpha;
+ *     theta = theta'; d = eta d + zeta p; g = eta g + zeta q; x += d; s -= g;
+ *     stop on ||s|| / ||b|| <= rtol; z = M^{-1} r; rho' = (r, z); p = z + (rho' / rho) p; rho = rho'
+ * s is the residual b - A x of the smoothed iterate, by recurrence; the raw residual r underneath may be erratic.  An
+ * ITERATION is one M^{-1} apply plus one SpMM, the unit of the PCG iteration count and of a BiCGSTAB step.  All vectors
+ * and the per-column scalars stay in HBM (seven work vectors r, z, p, q, d, g, s per 64-column tile, no restarts); the
+ * host reads back one integer per iteration.  Inner products are Hermitian (sum conj(a_i) b_i) and their summation
+ * order depends on n only, so a column's result does not depend on the batch it is solved in.  Needs
+ * hifamd_set_matrix and a Hermitian M^{-1} (hifamd_hermitian; the HIFAMD_BAD_PREC message names the level and the array
+ * of the first violation and points to is_symm, GMRES and BiCGSTAB); M^{-1} and A may be indefinite (a positive-definite
+ * pair is a valid input too).  A constant-mode null-space filter on HIFAMD_S (hifamd_set_nsp_const) is refused with
+ * HIFAMD_BAD_PREC.  With a BASIS filter on HIFAMD_S (hifamd_set_nsp_basis, P = I - Q Q^H) the iteration runs projected
+ * exactly as hifamd_pcg_batch does: r0 = s0 = P b, ||b|| in the stopping test is ||P b||, every z is P M^{-1} r, and
+ * P b = 0 is the zero column.  maxit < 1 or rtol <= 0: HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  Per
+ * column: flags[c] = 0 converged / 1 breakdown (rho = (r, z) or sigma = (p, A p) exactly zero or not finite, no sign
+ * test; x keeps its last update) / 2 reached maxit, iters[c] = iterations (a zero column: x = 0, flag 0, 0 iterations;
+ * a non-finite column: flag 1, 0 iterations); either may be NULL.  Host pointers; the _dev variant takes device
+ * pointers for B, X (flags, iters stay host arrays) and returns when the solve is done. */
+HifAmdStatus hifamd_sqmr_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
+                               double rtol, int maxit, int64_t rank, int *flags, int *iters);
+HifAmdStatus hifamd_sqmr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                   double rtol, int maxit, int64_t rank, int *flags, int *iters);
 
 /* ---- instrumentation ---------------------------------------------------------------------- */
 /* Average device time (ms) of the last `hifamd_solve_batch_dev`-shaped graph over `reps` replays,

@@ -280,6 +280,19 @@ class HIF {
   }
   bool is_hermitian() const { return _h && hifamd_hermitian(_h) == 1; }
 
+  // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
+  // Needs an is_symm hierarchy: is_hermitian(); neither A nor M has to be definite.  iters counts iterations (one apply
+  // plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, int, int> sqmr(const Matrix &A, const ArrayType &b, const double rtol, const int maxit,
+                                       const bool full_rank = false) {
+    ensure_matrix(A);
+    ArrayType x(b.size());
+    int flag = 0, iters = 0;
+    detail::check(hifamd_sqmr_batch(_h, b.data(), 1, x.data(), 1, 1, rtol, maxit, full_rank ? -1 : 0, &flag, &iters));
+    return std::make_tuple(std::move(x), flag, iters);
+  }
+
   // ---- right-preconditioned BiCGSTAB for a general pair (A, M) on the device (hifamd_bicgstab_batch) ----
   // iters counts steps (one apply plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
   template <class Matrix, class ArrayType>
