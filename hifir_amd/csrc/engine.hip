@@ -533,6 +533,9 @@ class Engine : public EngineBase {
   }
   int64_t zop_top_max = 0;  // what top_max is for a real handle in the environment this handle was created under
   int cd_dbg = 0;        // development aid (HIFIR_AMD_CD_DBG): phases of k_band_cd switched off for timing experiments
+  // ... and bit 2048 (kDbgCtPlain), which switches nothing off: k_band_ct's phase 1 gathers a tile batch in front of its own
+  // products, as it did before its requests ran ahead -- the same sums in the same order, the same bits; the tests' second opinion
+  static constexpr int kDbgCtPlain = 2048;
   // Column-sliced component bands (kernels.hip.hpp k_band_cs): a component band of at most cs_max_wgs workgroups is cut
   // into 16-column slices (the heaviest component of a narrow band then runs on four compute units); a batch of fewer
   // than 49 columns runs EVERY component band sliced and launches only the slices it has.  HIFIR_AMD_CS=0: off.
@@ -689,8 +692,10 @@ class Engine : public EngineBase {
     HIP_OK(hipSetDevice(device));
     if (!stream) HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     if (sizeof(T) == sizeof(double) && band_opt.cd_rows > 0) {  // k_band_cd keeps a component in up to 128 KB of LDS
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
+      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
+      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
+      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<true, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
+      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<false, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
       HIP_OK(hipFuncSetAttribute((const void *)k_band_us, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1937,7 +1942,9 @@ class Engine : public EngineBase {
         const int nct = (ncols == 4 && g1 - g0 > ct_wide4_wgs) ? 4 : ((ncols >= 2 && g1 - g0 > ct_wide_wgs) ? 2 : 1);
         const int nslc = (ncols + nct - 1) / nct;
         const unsigned grid = (unsigned)(((g1 - g0 + 7) / 8) * 8 * nslc) + 4 * extra;
-        auto kct = nct == 4 ? k_band_ct<LOWER, 4> : (nct == 2 ? k_band_ct<LOWER, 2> : k_band_ct<LOWER, 1>);
+        const bool ct_ahead = !(cd_dbg & kDbgCtPlain);
+        auto kct = ct_ahead ? (nct == 4 ? k_band_ct<LOWER, 4, true> : (nct == 2 ? k_band_ct<LOWER, 2, true> : k_band_ct<LOWER, 1, true>))
+                            : (nct == 4 ? k_band_ct<LOWER, 4, false> : (nct == 2 ? k_band_ct<LOWER, 2, false> : k_band_ct<LOWER, 1, false>));
         tally(nct == 4 ? KF_BAND_CT4 : (nct == 2 ? KF_BAND_CT2 : KF_BAND_CT1));
         hipLaunchKernelGGL(kct, dim3(grid), dim3(256), ct_lds_bytes(nct), st, g0,
                            M.wg_grp_ptr.as<int32_t>(), M.ct_desc.as<int32_t>(), M.ptr.as<int32_t>(), M.split.as<int32_t>(),
@@ -1963,7 +1970,7 @@ class Engine : public EngineBase {
         }
       }
       if (LOWER && ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
-          (!with_f || M.ls_fused) && !cd_dbg && !no_walk && !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {
+          (!with_f || M.ls_fused) && !(cd_dbg & ~kDbgCtPlain) && !no_walk && !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {
         // dependent rows in LDS, sources through a chunk: two workgroups per unit
         const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]), f = with_f ? 1 : 0;
         const int32_t own_cap2 = std::max(64, (M.ls_band_own[band] + 63) & ~63), rptr_cap = (M.ls_band_rptr[band] + 3) & ~3;

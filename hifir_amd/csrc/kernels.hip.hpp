@@ -291,6 +291,7 @@ __device__ __forceinline__ int32_t rfl(int32_t v) { return __builtin_amdgcn_read
 // compiler barrier that "touches" a value: nothing that depends on it is scheduled above this point
 __device__ __forceinline__ void pin_here(double &v) { asm volatile("" : "+v"(v)::"memory"); }
 __device__ __forceinline__ void pin_here(cplx &v) { asm volatile("" : "+v"(v.x), "+v"(v.y)::"memory"); }
+__device__ __forceinline__ void pin_here(uint32_t &v) { asm volatile("" : "+v"(v)::"memory"); }
 
 // Development probe (make PROBE=1): wall_clock64 stamps of every wave of k_trsv_band -- kernel entry, start
 // of work, exit, and per row (the wave's first two) start / first gather / last accumulation / flag, number
@@ -4319,8 +4320,14 @@ __global__ void __launch_bounds__(256) k_band_cs(int32_t wg0, const int32_t *__r
 // a wave).  Column-separable like every kernel here: a column's bits do not depend on the batch width,
 // so this kernel serves narrow batches (nsl < 4) and full ones alike.  Summation order: tile by tile (tolerance-level).
 // ---------------------------------------------------------------------------------------------
-template <bool LOWER, int NCT>
-__global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
+// AHEAD (on unless bit 2048 of the development switch is set, engine.hip kDbgCtPlain): phase 1 keeps a strip's source ids two batches, its gathers and coefficient
+// tiles one batch ahead of the products (below); off: ids and coefficients one batch ahead, the gathers of a batch
+// requested in front of its own products.  The same sums in the same order: the same bits.
+// amdgpu_waves_per_eu: the occupancy the register budget is made for (three waves per SIMD; all four column tiles: two).
+// Without it the allocator takes what 256 threads allow and keeps the accumulators in AGPRs, with copies around every trip.
+template <bool LOWER, int NCT, bool AHEAD>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NCT == 4 ? 2 : 3)))
+k_band_ct(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
                                                  const int32_t *__restrict__ ct_desc, const int32_t *__restrict__ ptr,
                                                  const int32_t *__restrict__ split, const int32_t *__restrict__ col,
                                                  const double *__restrict__ val, const int32_t *__restrict__ rowid,
@@ -4370,6 +4377,9 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
   // generic access may return out of order) -- phase 2's counted waits would be lost.  Both blocks are device memory:
   typedef __attribute__((address_space(1))) double gdouble;
   const gdouble *rhs_g = (const gdouble *)rhs;
+  typedef __attribute__((address_space(1))) int32_t gint32;
+  const gdouble *x_g = (const gdouble *)x, *coef_g = (const gdouble *)ct_coef;
+  const gint32 *src_g = (const gint32 *)ct_src;
   int32_t c_first, c_last;
   if (single_c0 >= 0) {
     c_first = single_c0 + bw;
@@ -4442,11 +4452,69 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
           tr[ct][j] = rhs_g[(int64_t)i * rstride + (first_l ? min(cx, fl.nrhs - 1) : cx)];
         }
       }
-      const int32_t t0 = s_sptr[s], t1 = (dbg & 1) ? t0 : s_sptr[s + 1];
+      const int32_t t0v = s_sptr[s], t1v = (dbg & 1) ? t0v : s_sptr[s + 1];
       v4f64 acc[NCT];
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) acc[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
-      if (t0 < t1) {
+      if (AHEAD && t0v < t1v) {
+        // Batches of BU tiles; three request streams run ahead of the products, every load unconditional (a tile index
+        // past the strip's last tile reads that tile again; its coefficient is replaced by zero where it is multiplied,
+        // and a batch wholly past the end is never multiplied).  At the top of the step that multiplies batch b the ids
+        // of batch b + 1 and the gathers and coefficients of batch b are in flight, in that order; the step requests the
+        // ids of batch b + 2, then -- the ids of b + 1 have arrived, the wait leaves batch b's operands in flight -- the
+        // gathers and coefficients of batch b + 1, and only then multiplies batch b: its wait leaves everything the step
+        // requested in flight.  Two register sets of each kind rotate by name over a loop of two steps.
+        // (the strip's tile range is wave-uniform: said so, tile indices and clamps are scalar work)
+        const int32_t t0 = __builtin_amdgcn_readfirstlane(t0v), t1 = __builtin_amdgcn_readfirstlane(t1v);
+        uint32_t ia[BU], ib[BU];  // (row ids are not negative: widened by zero, nothing waits for the load that early)
+        double ca[BU], cb[BU], ga[NCT][BU], gb[NCT][BU];
+#define HIFAMD_CT_IDS(ii, tb_)                                                                   \
+  _Pragma("unroll") for (int u = 0; u < BU; ++u) ii[u] = (uint32_t)src_g[4 * (int64_t)min((tb_) + u, t1 - 1) + kq];
+#define HIFAMD_CT_OPS(gg, cf, ii, tb_)                                                           \
+  {                                                                                              \
+    _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                             \
+      _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) gg[ct][u] = x_g[((uint64_t)ii[u] << 6) + (uint32_t)(cc + 16 * ct)]; \
+    }                                                                                            \
+    _Pragma("unroll") for (int u = 0; u < BU; ++u) cf[u] = coef_g[64 * (int64_t)min((tb_) + u, t1 - 1) + lane]; \
+  }
+#define HIFAMD_CT_MUL(gg, cf, tb_)                                                               \
+  _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                               \
+    const double c_ = ((tb_) + u < t1) ? cf[u] : 0.0;                                            \
+    _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct)                                           \
+      acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(c_, gg[ct][u], acc[ct], 0, 0, 0);           \
+  }
+        // ifree: the id set whose gathers are out; inext: the ids of the batch behind the one being multiplied
+#define HIFAMD_CT_AHEAD_STEP(ifree, inext, gcur, ccur, gnew, cnew, tb_)                          \
+  {                                                                                              \
+    HIFAMD_CT_IDS(ifree, (tb_) + 2 * BU)                                                         \
+    __builtin_amdgcn_sched_barrier(0); /* (the ids lead: the next step's wait for them is counted) */ \
+    HIFAMD_CT_OPS(gnew, cnew, inext, (tb_) + BU)                                                 \
+    __builtin_amdgcn_sched_barrier(0); /* (the requests stay in front of the products) */        \
+    HIFAMD_CT_MUL(gcur, ccur, tb_)                                                               \
+    _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) asm volatile("" : "+v"(acc[ct]));         \
+  }
+        HIFAMD_CT_IDS(ia, t0)
+        HIFAMD_CT_IDS(ib, t0 + BU)
+        // (the second id set is touched here, or its request sinks into the loop's entry, behind batch 0's operands: the
+        // loop's first wait for ids would then be a wait for those operands, on every trip)
+#pragma unroll
+        for (int u = 0; u < BU; ++u) pin_here(ib[u]);
+        HIFAMD_CT_OPS(ga, ca, ia, t0)
+        int32_t t = t0;
+        for (; t + BU < t1; t += 2 * BU) {  // (one exit, at the top; two batches per trip)
+          HIFAMD_CT_AHEAD_STEP(ia, ib, ga, ca, gb, cb, t)
+          HIFAMD_CT_AHEAD_STEP(ib, ia, gb, cb, ga, ca, t + BU)
+        }
+        if (t < t1) {  // the strip's last batch: in registers or on its way
+          HIFAMD_CT_MUL(ga, ca, t)
+        }
+#undef HIFAMD_CT_AHEAD_STEP
+#undef HIFAMD_CT_MUL
+#undef HIFAMD_CT_OPS
+#undef HIFAMD_CT_IDS
+      }
+      if (!AHEAD && t0v < t1v) {
+        const int32_t t0 = t0v, t1 = t1v;
         int32_t sv[BU];
         double cv[BU];
 #pragma unroll
@@ -4493,8 +4561,10 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
       }
     }
     // (a wide band: requested behind phase 1, before the barrier -- there the registers buy more than the latency)
-    if ((NCT != 1 || (dbg & 256)) && wave < S) {
-      const double *ap_ = Ac + ((int64_t)(S - 1 - wave) * lda) * 16 + l16 + (int64_t)kq * 16;
+    // (unconditional where the instance decides it: a wave without a strip reads strip 0's first set, never multiplied --
+    // a set that is requested under a branch holds its registers through all of phase 1)
+    if (NCT != 1 || ((dbg & 256) && wave < S)) {
+      const double *ap_ = Ac + ((int64_t)max(S - 1 - wave, 0) * lda) * 16 + l16 + (int64_t)kq * 16;
 #pragma unroll
       for (int u = 0; u < KU; ++u) a0[u] = ap_[u * 64];
     }
@@ -4533,12 +4603,12 @@ __global__ void __launch_bounds__(256) k_band_ct(int32_t wg0, const int32_t *__r
     _Pragma("unroll") for (int u = 0; u < KU; ++u) aa[u] = ap_[u * 64];                          \
     HIFAMD_CT_NEXT(l_i, l_rnd, l_t, l_ns, l_strip)                                               \
   }
-    int l_i = 0, l_rnd = 0, l_t = 0, l_strip = S - 1 - wave, l_ns = (min(nb, 16 * (S - wave)) + 31) >> 5;
+    int l_i = 0, l_rnd = 0, l_t = 0, l_strip = max(S - 1 - wave, 0), l_ns = (min(nb, 16 * (S - wave)) + 31) >> 5;
     double a2[KU];
-    if (nitems > 0) {  // (item 0 is on its way; item 1 follows it before the barrier)
-      HIFAMD_CT_NEXT(l_i, l_rnd, l_t, l_ns, l_strip)
-      HIFAMD_CT_LOAD(a1)
-    }
+    // (item 0 is on its way; item 1 follows it before the barrier -- unconditionally: a wave without items reads strip
+    // 0's first set)
+    HIFAMD_CT_NEXT(l_i, l_rnd, l_t, l_ns, l_strip)
+    HIFAMD_CT_LOAD(a1)
     // (rows nb .. lda - 1 are zero for the inverse product; lds_rows is a multiple of 32)
     for (int t = nb * W + (int)threadIdx.x; t < lda * W; t += 256) tb[t] = 0.0;
     HIFAMD_CSP(4)

@@ -193,7 +193,9 @@ int hifamd_launch_map(HifAmdHdl h, int32_t *out, int cap);
  * out[f] = launches of family f on every level, out[N + f] = those of them on a level >= 1 (the tail operator counts for
  * the first level it replaces), f < N; hifamd_kernel_family_name(f) names the families in order ("band_ct1", "band_ct2",
  * ..., NULL from f = N on).  A family is what the dispatch distinguishes: a kernel, and where the planner or a
- * HIFIR_AMD_* switch chooses between instantiations, the instantiation.  Returns 2 N (writes min(cap, that)); 0 before
+ * HIFIR_AMD_* switch chooses between instantiations, the instantiation (one exception: bit 2048 of HIFIR_AMD_CD_DBG picks the
+ * other form of k_band_ct's tile loop, which makes the same sums in the same order -- both count as band_ct1 / 2 / 4).
+ * Returns 2 N (writes min(cap, that)); 0 before
  * hifamd_finalize, -1 for a NULL handle. */
 int hifamd_kernel_census(HifAmdHdl h, int32_t *out, int cap);
 const char *hifamd_kernel_family_name(int family);
