@@ -607,7 +607,7 @@ class Engine : public EngineBase {
   // nsp_on and nsp_k > 0 exclude each other.  (Twin engines never filter: solve_dev filters after their join.)
   int nsp_k = 0, nsp_kp = 0;
   DevBuf nsp_Q, nsp_cpart, nsp_C;
-  DevBuf gm_v, gm_w, gm_Q, gm_Z, gm_alpha;  // GMRES: work vectors, Krylov basis, per-column coefficients
+  DevBuf gm_Q, gm_Z, gm_alpha;  // GMRES: Krylov basis, per-column coefficients (its work vectors: kr_vec)
   int64_t ir_cols = 0;
 
   explicit Engine(int dev) : device(dev) {
@@ -729,7 +729,7 @@ class Engine : public EngineBase {
     // completes asynchronous work on threads of its own; see DESIGN 8 on the host copy that changed twice in four rounds)
     if (stream && !is_twin) (void)hipDeviceSynchronize();
     if (gm_ctl_host) (void)hipHostFree(gm_ctl_host);
-    if (cg_pin) (void)hipHostFree(cg_pin);
+    if (kr_pin) (void)hipHostFree(kr_pin);
 #ifdef HIFAMD_CSPROBE
     csprobe_dump();
 #endif
@@ -2763,20 +2763,35 @@ class Engine : public EngineBase {
     HIP_OK(hipGraphLaunch(it->second.exec, st));
   }
 
-  void solve_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int64_t rank) {
+  struct StreamWait {  // waits for the stream on every way out of a scope that enqueued work
+    hipStream_t s;
+    ~StreamWait() { (void)hipStreamSynchronize(s); }
+  };
+  // The host-pointer form of a batched entry: B [n][nrhs] (row stride ldb) is staged on the device, run(dB, dX) works
+  // on the staged blocks (row stride nrhs), and X (row stride ldx) comes back.  pre() holds what must refuse the call
+  // before anything is enqueued.  The stream is drained on every way out: when run() throws, no copy is left reading
+  // the caller's B.  sticky: also report the band kernels' error word (the solvers' tiles have done so themselves).
+  template <class Pre, class Run>
+  void staged(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, bool sticky, Pre pre, Run run) {
     check_batch(B, ldb, X, ldx, nrhs);
+    pre();
     HIP_OK(hipSetDevice(device));
     const int64_t n = lv[0]->n;
     const size_t need = (size_t)n * nrhs * sizeof(T);
     if (stage_b.bytes < need) stage_b.alloc(need);
     if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
     HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
                             hipMemcpyHostToDevice, stream));
-    solve_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rank, nullptr);
+    run((const D *)stage_b.as<D>(), stage_x.as<D>());
     HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
                             hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
+    if (sticky) check_device_error();
+  }
+
+  void solve_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int64_t rank) {
+    staged(B, ldb, X, ldx, nrhs, true, [] {}, [&](const D *b, D *x) { solve_dev(b, nrhs, x, nrhs, nrhs, rank, nullptr); });
   }
 
   // ---- SpMV + iterative refinement -----------------------------------------------------------
@@ -2925,19 +2940,87 @@ class Engine : public EngineBase {
 
   void hifir_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int nirs, const double *betas,
                   int64_t rank, int *ir_status) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    hifir_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, nirs, betas, rank, ir_status);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
+    staged(B, ldb, X, ldx, nrhs, true, [] {},
+           [&](const D *b, D *x) { hifir_dev(b, nrhs, x, nrhs, nrhs, nirs, betas, rank, ir_status); });
+  }
+
+  // ---- what the lock-step Krylov solvers share -------------------------------------------------------
+  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG 4, BiCGSTAB 5, symmetric QMR 7),
+  // each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
+  // That holds because no solver runs inside another one's tile: the null-space search calls gmres_dev between its own
+  // local blocks, flexible GMRES calls the refinement (ir_r, ir_xk) and the projected PCG / QMR call apply_nsp
+  // (nsp_cpart, nsp_C); none of these takes a pool vector.  Keep it so when adding a solver.
+  DevBuf kr_vec[7];
+  void krylov_vectors(int k, size_t bytes) {
+    for (int i = 0; i < k; ++i)
+      if (kr_vec[i].bytes < bytes) kr_vec[i].alloc(bytes);
+  }
+
+  // The per-column scalars of PCG, BiCGSTAB and symmetric QMR in one zeroed block: the [64] slots of D, those of double,
+  // then iter | flag | active | ctl.  One pinned buffer takes the read-backs: [0] active columns, [1, 65) iterations,
+  // [65, 129) flags.
+  DevBuf kr_state;
+  int *kr_pin = nullptr;
+  void krylov_state(KrylovState &S, std::initializer_list<D **> ds, std::initializer_list<double **> rs, double rtol, int maxit) {
+    const size_t o_re = ds.size() * 64 * sizeof(D), o_int = o_re + rs.size() * 64 * sizeof(double),
+                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
+    if (!kr_pin) HIP_OK(hipHostMalloc((void **)&kr_pin, 129 * sizeof(int), hipHostMallocDefault));
+    if (kr_state.bytes < bytes) kr_state.alloc(bytes);
+    HIP_OK(hipMemsetAsync(kr_state.p, 0, bytes, stream));
+    char *b = kr_state.as<char>();
+    D *d = (D *)b;
+    for (D **slot : ds) *slot = d, d += 64;
+    double *r = (double *)(b + o_re);
+    for (double **slot : rs) *slot = r, r += 64;
+    int *ib = (int *)(b + o_int);
+    S.iter = ib;
+    S.flag = ib + 64;
+    S.active = ib + 128;
+    S.ctl = ib + 192;
+    S.maxit = maxit;
+    S.rtol = rtol;
+  }
+  int krylov_active(const KrylovState &S) {
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return kr_pin[0];
+  }
+  void krylov_result(const KrylovState &S, int nc, int *flags, int *iters) {
+    HIP_OK(hipMemcpyAsync(kr_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
     HIP_OK(hipStreamSynchronize(stream));
     check_device_error();
+    for (int c = 0; c < nc; ++c) {
+      if (iters) iters[c] = kr_pin[1 + c];
+      if (flags) flags[c] = kr_pin[65 + c];
+    }
+  }
+
+  // A device-pointer entry: the batch checks, the solver's own (check), then tile(b, x, nc, flags, iters, sweeps) on
+  // every 64 columns
+  template <class Check, class Tile>
+  void krylov_batch(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int *flags, int *iters, int *sweeps,
+                    Check check, Tile tile) {
+    check_batch(dB, ldb, dX, ldx, nrhs);
+    check();
+    HIP_OK(hipSetDevice(device));
+    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
+      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+      auto at = [c0](int *p) { return p ? p + c0 : nullptr; };
+      tile(dB + c0, dX + c0, nc, at(flags), at(iters), at(sweeps));
+    }
+  }
+  void krylov_check(const std::string &who, int maxit, double rtol) {
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, who + " needs the matrix (hifamd_set_matrix)");
+    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
+  }
+  // for the solvers that need M^{-1} Hermitian; they run projected under a basis filter but not under the constant one
+  void hermitian_check(const std::string &who, const char *instead, const char *filter) {
+    const HermCheck &hc = hermitian();
+    if (!hc.ok)
+      throw Error(HIFAMD_BAD_PREC, who + " needs a Hermitian preconditioner and this hierarchy is not one (level " +
+                                       std::to_string(hc.level) + ": " + hc.what +
+                                       "); factorize a Hermitian matrix with is_symm, or use " + instead);
+    if (nsp_on) throw Error(HIFAMD_BAD_PREC, who + " does not support " + filter + " (hifamd_set_nsp_const)");
   }
 
   // ---- right-preconditioned restarted GMRES, batched over columns ----------------------------------
@@ -3022,12 +3105,11 @@ class Engine : public EngineBase {
                   int64_t rank, int *flags, int *iters, bool flexible, int *sweeps) {
     const int64_t n = lv[0]->n;
     const size_t vec = (size_t)n * nc * sizeof(D);
-    if (gm_v.bytes < vec) gm_v.alloc(vec);
-    if (gm_w.bytes < vec) gm_w.alloc(vec);
+    krylov_vectors(2, vec);
     if (gm_Q.bytes < vec * (size_t)restart) gm_Q.alloc(vec * (size_t)restart);
     // flexible variant (fgmres_hifir, gmres.hpp:127-231): the preconditioned vectors are kept as well
     if (flexible && gm_Z.bytes < vec * (size_t)restart) gm_Z.alloc(vec * (size_t)restart);
-    D *v = gm_v.as<D>(), *w = gm_w.as<D>(), *Q = gm_Q.as<D>(), *Z = gm_Z.as<D>();
+    D *v = kr_vec[0].as<D>(), *w = kr_vec[1].as<D>(), *Q = gm_Q.as<D>(), *Z = gm_Z.as<D>();
     auto Qk = [&](int k) { return Q + (size_t)k * (size_t)n * nc; };
     auto Zk = [&](int k) { return Z + (size_t)k * (size_t)n * nc; };
     const GmState<D> S = gm_state(nc, restart, maxit, rtol);
@@ -3097,34 +3179,23 @@ class Engine : public EngineBase {
     }
   }
 
-  void gmres_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int restart, double rtol,
-                 int maxit, int64_t rank, int *flags, int *iters, bool flexible = false, int *sweeps = nullptr) {
-    check_batch(dB, ldb, dX, ldx, nrhs);
+  void gmres_check(int restart, int maxit, double rtol) {
     if (!has_A) throw Error(HIFAMD_BAD_PREC, "GMRES needs the matrix (hifamd_set_matrix)");
     if (restart < 1 || maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need restart >= 1, maxit >= 1, rtol > 0");
-    HIP_OK(hipSetDevice(device));
-    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
-      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
-      gmres_tile(dB + c0, ldb, dX + c0, ldx, nc, restart, rtol, maxit, rank, flags ? flags + c0 : nullptr,
-                 iters ? iters + c0 : nullptr, flexible, sweeps ? sweeps + c0 : nullptr);
-    }
   }
-
+  void gmres_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int restart, double rtol,
+                 int maxit, int64_t rank, int *flags, int *iters, bool flexible = false, int *sweeps = nullptr) {
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, sweeps, [&] { gmres_check(restart, maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *sw) {
+                   gmres_tile(b, ldb, x, ldx, nc, restart, rtol, maxit, rank, fl, it, flexible, sw);
+                 });
+  }
+  // (GMRES's own checks run in gmres_dev, behind the staging copy)
   void gmres_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int restart, double rtol,
                   int maxit, int64_t rank, int *flags, int *iters, bool flexible = false, int *sweeps = nullptr) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    gmres_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, restart, rtol, maxit, rank, flags, iters, flexible,
-              sweeps);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    staged(B, ldb, X, ldx, nrhs, false, [] {}, [&](const D *b, D *x) {
+      gmres_dev(b, nrhs, x, nrhs, nrhs, restart, rtol, maxit, rank, flags, iters, flexible, sweeps);
+    });
   }
 
   // ---- preconditioned CG, batched over columns ------------------------------------------------------
@@ -3134,52 +3205,18 @@ class Engine : public EngineBase {
   // pass followed by a one-workgroup finishing kernel; the per-column scalars live in HBM (CgState) and the host reads
   // one integer per step (how many columns are still active) through a pinned buffer of the engine.  Only for a
   // Hermitian M^{-1} (import.hpp check_hermitian); flags 0 converged / 1 breakdown / 2 reached maxit.
-  DevBuf cg_r, cg_z, cg_p, cg_q, cg_state;
-  int *cg_pin = nullptr;  // pinned: [0] active columns, [1, 65) iterations, [65, 129) flags
-  struct StreamWait {     // waits for the stream on every way out of a scope that enqueued work
-    hipStream_t s;
-    ~StreamWait() { (void)hipStreamSynchronize(s); }
-  };
-
-  CgState<D> cg_make_state(double rtol, int maxit) {
-    const size_t o_rho = 0, o_al = o_rho + 64 * sizeof(D), o_be = o_al + 64 * sizeof(D), o_bn = o_be + 64 * sizeof(D),
-                 o_int = o_bn + 64 * sizeof(double), bytes = o_int + (3 * 64 + 4) * sizeof(int);
-    if (cg_state.bytes < bytes) cg_state.alloc(bytes);
-    HIP_OK(hipMemsetAsync(cg_state.p, 0, bytes, stream));
-    char *b = cg_state.as<char>();
-    CgState<D> S;
-    S.rho = (D *)(b + o_rho);
-    S.alpha = (D *)(b + o_al);
-    S.beta = (D *)(b + o_be);
-    S.bnorm = (double *)(b + o_bn);
-    int *ib = (int *)(b + o_int);
-    S.iter = ib;
-    S.flag = ib + 64;
-    S.active = ib + 128;
-    S.ctl = ib + 192;
-    S.maxit = maxit;
-    S.rtol = rtol;
-    return S;
-  }
-  int cg_active(const CgState<D> &S) {
-    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return cg_pin[0];
-  }
-
   void pcg_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank, int *flags,
                 int *iters) {
     const int64_t n = lv[0]->n;
     const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
-    for (DevBuf *b : {&cg_r, &cg_z, &cg_p, &cg_q})
-      if (b->bytes < vec) b->alloc(vec);
+    krylov_vectors(4, vec);
     if (ir_part.bytes < part) ir_part.alloc(part);
-    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
-    D *r = cg_r.as<D>(), *z = cg_z.as<D>(), *p = cg_p.as<D>(), *q = cg_q.as<D>(), *pt = ir_part.as<D>();
+    D *r = kr_vec[0].as<D>(), *z = kr_vec[1].as<D>(), *p = kr_vec[2].as<D>(), *q = kr_vec[3].as<D>(), *pt = ir_part.as<D>();
     StreamWait wait{stream};
-    const CgState<D> S = cg_make_state(rtol, maxit);
+    CgState<D> S;
+    krylov_state(S, {&S.rho, &S.alpha, &S.beta}, {&S.bnorm}, rtol, maxit);
     auto dot = [&](const D *a, const D *b) {
-      hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
+      hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, a, (int64_t)nc, b, pt);
     };
     auto finish = [&](int mode, int k) {
       hipLaunchKernelGGL((k_cg_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, mode, k, S);
@@ -3197,67 +3234,37 @@ class Engine : public EngineBase {
     vec_op(1, n, nc, p, nc, (const D *)z, nc, nullptr, 0);  // p = z
     HIP_OK(hipGetLastError());
     // (one read-back per step, after the convergence test; a column that breaks down in mode 4 costs one frozen step)
-    for (int k = 0, go = cg_active(S); k < maxit && go > 0; ++k) {
+    for (int k = 0, go = krylov_active(S); k < maxit && go > 0; ++k) {
       spmv_dev((const D *)p, nc, q, nc, nc, nullptr);    // q = A p
       dot(p, q);
       finish(2, k);                                      // alpha = rho / p^H q
       hipLaunchKernelGGL((k_cg_xr<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, dX, ldx, r, (const D *)p, (const D *)q,
-                         S, pt);
+                         (const D *)S.alpha, (const int *)S.active, pt);
       finish(3, k);                                      // ||r|| / ||b||, maxit
-      if ((go = cg_active(S)) == 0) break;
+      if ((go = krylov_active(S)) == 0) break;
       solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);
       dot(r, z);
       finish(4, k);                                      // beta = rho' / rho
-      hipLaunchKernelGGL((k_cg_p<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, p, (const D *)z, S);
+      hipLaunchKernelGGL((k_cg_p<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, p, (const D *)z, (const D *)S.beta,
+                         (const int *)S.active);
       HIP_OK(hipGetLastError());
     }
-    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
-    HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
-    for (int c = 0; c < nc; ++c) {
-      if (iters) iters[c] = cg_pin[1 + c];
-      if (flags) flags[c] = cg_pin[65 + c];
-    }
+    krylov_result(S, nc, flags, iters);
   }
 
   void pcg_check(int maxit, double rtol) {
-    if (!has_A) throw Error(HIFAMD_BAD_PREC, "PCG needs the matrix (hifamd_set_matrix)");
-    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
-    const HermCheck &hc = hermitian();
-    if (!hc.ok)
-      throw Error(HIFAMD_BAD_PREC, "PCG needs a Hermitian preconditioner and this hierarchy is not one (level " +
-                                       std::to_string(hc.level) + ": " + hc.what +
-                                       "); factorize a Hermitian matrix with is_symm, or use GMRES");
-    if (nsp_on) throw Error(HIFAMD_BAD_PREC, "PCG does not support a null-space filter (hifamd_set_nsp_const)");
+    krylov_check("PCG", maxit, rtol);
+    hermitian_check("PCG", "GMRES", "a null-space filter");
   }
-
   void pcg_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                int *flags, int *iters) {
-    check_batch(dB, ldb, dX, ldx, nrhs);
-    pcg_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
-      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
-      pcg_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr, iters ? iters + c0 : nullptr);
-    }
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { pcg_check(maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) { pcg_tile(b, ldb, x, ldx, nc, rtol, maxit, rank, fl, it); });
   }
-
   void pcg_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                 int *flags, int *iters) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    pcg_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    StreamWait wait{stream};
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    pcg_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    staged(B, ldb, X, ldx, nrhs, false, [&] { pcg_check(maxit, rtol); },
+           [&](const D *b, D *x) { pcg_dev(b, nrhs, x, nrhs, nrhs, rtol, maxit, rank, flags, iters); });
   }
 
   // ---- right-preconditioned BiCGSTAB, batched over columns ----------------------------------------
@@ -3269,67 +3276,40 @@ class Engine : public EngineBase {
   // host reads the active count after each of the two tests.  r^ is b itself, read in place, so the work vectors are
   // r, p, v, y, t.  Every apply goes through solve_dev, so a null-space filter on HIFAMD_S filters it.
   // Flags 0 converged / 1 breakdown / 2 reached maxit.
-  DevBuf bs_r, bs_p, bs_v, bs_y, bs_t, bs_part2, bs_state;
-
-  BsState<D> bs_make_state(double rtol, int maxit) {
-    const size_t o_sc = 0, o_bn = o_sc + 4 * 64 * sizeof(D), o_int = o_bn + 64 * sizeof(double),
-                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
-    if (bs_state.bytes < bytes) bs_state.alloc(bytes);
-    HIP_OK(hipMemsetAsync(bs_state.p, 0, bytes, stream));
-    char *b = bs_state.as<char>();
-    BsState<D> S;
-    S.rho = (D *)(b + o_sc);
-    S.alpha = S.rho + 64;
-    S.omega = S.rho + 128;
-    S.beta = S.rho + 192;
-    S.bnorm = (double *)(b + o_bn);
-    int *ib = (int *)(b + o_int);
-    S.iter = ib;
-    S.flag = ib + 64;
-    S.active = ib + 128;
-    S.ctl = ib + 192;
-    S.maxit = maxit;
-    S.rtol = rtol;
-    return S;
-  }
-  int bs_active(const BsState<D> &S) {
-    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return cg_pin[0];
-  }
+  DevBuf bs_part2;  // the block partials of a pass's second sum
 
   void bicgstab_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank,
                      int *flags, int *iters) {
     const int64_t n = lv[0]->n;
     const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
-    for (DevBuf *b : {&bs_r, &bs_p, &bs_v, &bs_y, &bs_t})
-      if (b->bytes < vec) b->alloc(vec);
+    krylov_vectors(5, vec);
     if (ir_part.bytes < part) ir_part.alloc(part);
     if (bs_part2.bytes < part) bs_part2.alloc(part);
-    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
-    D *r = bs_r.as<D>(), *p = bs_p.as<D>(), *v = bs_v.as<D>(), *y = bs_y.as<D>(), *t = bs_t.as<D>();
+    D *r = kr_vec[0].as<D>(), *p = kr_vec[1].as<D>(), *v = kr_vec[2].as<D>(), *y = kr_vec[3].as<D>(), *t = kr_vec[4].as<D>();
     D *pt = ir_part.as<D>(), *pt2 = bs_part2.as<D>();
     const D *rh = dB;  // r^ = b
     StreamWait wait{stream};
-    const BsState<D> S = bs_make_state(rtol, maxit);
+    BsState<D> S;
+    krylov_state(S, {&S.rho, &S.alpha, &S.omega, &S.beta}, {&S.bnorm}, rtol, maxit);
     const dim3 grid(kCgBlocks), blk(256);
     auto finish = [&](int mode, int k, const D *p1) {
       hipLaunchKernelGGL((k_bs_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, p1, nc, mode, k, S);
     };
     vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);            // r = b
-    hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, (const D *)r, (const D *)nullptr, pt);
+    hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, (const D *)r, (int64_t)nc, (const D *)nullptr, pt);
     finish(0, 0, nullptr);                                    // ||b||, rho = ||b||^2
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);        // x = 0
     vec_op(1, n, nc, p, nc, (const D *)r, nc, nullptr, 0);    // p = r
     HIP_OK(hipGetLastError());
-    for (int k = 0, go = bs_active(S); go > 0 && 2 * k < maxit; ++k) {
+    for (int k = 0, go = krylov_active(S); go > 0 && 2 * k < maxit; ++k) {
       solve_dev((const D *)p, nc, y, nc, nc, rank, nullptr);  // y = M^{-1} p           step 2k + 1
       spmv_dev((const D *)y, nc, v, nc, nc, nullptr);         // v = A y
-      hipLaunchKernelGGL((k_bs_hdot<D>), grid, blk, 0, stream, n, nc, rh, ldb, (const D *)v, pt);
+      hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, rh, ldb, (const D *)v, pt);  // (r^, v)
       finish(1, k, nullptr);                                  // alpha = rho / (r^, v)
-      hipLaunchKernelGGL((k_bs_xr_half<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)y, (const D *)v, S, pt);
+      hipLaunchKernelGGL((k_cg_xr<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)y, (const D *)v,
+                         (const D *)S.alpha, (const int *)S.active, pt);  // x += alpha y, r -= alpha v: r holds s
       finish(2, k, nullptr);                                  // ||s|| / ||b||, maxit
-      if ((go = bs_active(S)) == 0) break;
+      if ((go = krylov_active(S)) == 0) break;
       solve_dev((const D *)r, nc, y, nc, nc, rank, nullptr);  // y = M^{-1} s           step 2k + 2
       spmv_dev((const D *)y, nc, t, nc, nc, nullptr);         // t = A y
       hipLaunchKernelGGL((k_bs_tr<D>), grid, blk, 0, stream, n, nc, (const D *)t, (const D *)r, pt, pt2);
@@ -3337,52 +3317,22 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_bs_xr_full<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)y, (const D *)t, rh, ldb,
                          S, pt, pt2);
       finish(4, k, pt2);                                      // ||r|| / ||b||, maxit, beta
-      if ((go = bs_active(S)) == 0) break;
+      if ((go = krylov_active(S)) == 0) break;
       hipLaunchKernelGGL((k_bs_p<D>), grid, blk, 0, stream, n, nc, p, (const D *)r, (const D *)v, S);
       HIP_OK(hipGetLastError());
     }
-    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
-    HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
-    for (int c = 0; c < nc; ++c) {
-      if (iters) iters[c] = cg_pin[1 + c];
-      if (flags) flags[c] = cg_pin[65 + c];
-    }
-  }
-
-  void bicgstab_check(int maxit, double rtol) {
-    if (!has_A) throw Error(HIFAMD_BAD_PREC, "BiCGSTAB needs the matrix (hifamd_set_matrix)");
-    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
+    krylov_result(S, nc, flags, iters);
   }
 
   void bicgstab_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                     int *flags, int *iters) {
-    check_batch(dB, ldb, dX, ldx, nrhs);
-    bicgstab_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
-      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
-      bicgstab_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr,
-                    iters ? iters + c0 : nullptr);
-    }
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { krylov_check("BiCGSTAB", maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) { bicgstab_tile(b, ldb, x, ldx, nc, rtol, maxit, rank, fl, it); });
   }
-
   void bicgstab_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                      int *flags, int *iters) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    bicgstab_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    StreamWait wait{stream};
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    bicgstab_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    staged(B, ldb, X, ldx, nrhs, false, [&] { krylov_check("BiCGSTAB", maxit, rtol); },
+           [&](const D *b, D *x) { bicgstab_dev(b, nrhs, x, nrhs, nrhs, rtol, maxit, rank, flags, iters); });
   }
 
   // ---- symmetric QMR for a Hermitian indefinite pair, batched over columns ---------------------------
@@ -3396,55 +3346,22 @@ class Engine : public EngineBase {
   // k_qm_finish; the host reads the active count once per iteration, after the convergence test.  Only for a Hermitian
   // M^{-1} (import.hpp check_hermitian); a breakdown is rho or sigma exactly zero or not finite.  With a basis filter on
   // HIFAMD_S the iteration runs projected as PCG's does.  Flags 0 converged / 1 breakdown / 2 reached maxit.
-  DevBuf qm_r, qm_z, qm_p, qm_q, qm_d, qm_g, qm_s, qm_state;
-
-  QmState<D> qm_make_state(double rtol, int maxit) {
-    const size_t o_sc = 0, o_re = o_sc + 4 * 64 * sizeof(D), o_int = o_re + 4 * 64 * sizeof(double),
-                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
-    if (qm_state.bytes < bytes) qm_state.alloc(bytes);
-    HIP_OK(hipMemsetAsync(qm_state.p, 0, bytes, stream));
-    char *b = qm_state.as<char>();
-    QmState<D> S;
-    S.rho = (D *)(b + o_sc);
-    S.alpha = S.rho + 64;
-    S.beta = S.rho + 128;
-    S.zeta = S.rho + 192;
-    S.eta = (double *)(b + o_re);
-    S.tau = S.eta + 64;
-    S.theta = S.eta + 128;
-    S.bnorm = S.eta + 192;
-    int *ib = (int *)(b + o_int);
-    S.iter = ib;
-    S.flag = ib + 64;
-    S.active = ib + 128;
-    S.ctl = ib + 192;
-    S.maxit = maxit;
-    S.rtol = rtol;
-    return S;
-  }
-  int qm_active(const QmState<D> &S) {
-    HIP_OK(hipMemcpyAsync(cg_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return cg_pin[0];
-  }
 
   void sqmr_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank, int *flags,
                  int *iters) {
     const int64_t n = lv[0]->n;
     const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
-    for (DevBuf *b : {&qm_r, &qm_z, &qm_p, &qm_q, &qm_d, &qm_g, &qm_s})
-      if (b->bytes < vec) b->alloc(vec);
+    krylov_vectors(7, vec);
     if (ir_part.bytes < part) ir_part.alloc(part);
-    if (!cg_pin) HIP_OK(hipHostMalloc((void **)&cg_pin, 129 * sizeof(int), hipHostMallocDefault));
-    D *r = qm_r.as<D>(), *z = qm_z.as<D>(), *p = qm_p.as<D>(), *q = qm_q.as<D>(), *d = qm_d.as<D>(), *g = qm_g.as<D>(),
-      *s = qm_s.as<D>(), *pt = ir_part.as<D>();
+    D *r = kr_vec[0].as<D>(), *z = kr_vec[1].as<D>(), *p = kr_vec[2].as<D>(), *q = kr_vec[3].as<D>(), *d = kr_vec[4].as<D>(),
+      *g = kr_vec[5].as<D>(), *s = kr_vec[6].as<D>(), *pt = ir_part.as<D>();
     StreamWait wait{stream};
-    const QmState<D> S = qm_make_state(rtol, maxit);
-    CgState<D> Sp{};  // what k_cg_p reads: beta and the active mask
-    Sp.beta = S.beta;
-    Sp.active = S.active;
+    QmState<D> S;
+    krylov_state(S, {&S.rho, &S.alpha, &S.beta, &S.zeta}, {&S.eta, &S.tau, &S.theta, &S.bnorm}, rtol, maxit);
     const dim3 grid(kCgBlocks), blk(256);
-    auto dot = [&](const D *a, const D *b) { hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, a, b, pt); };
+    auto dot = [&](const D *a, const D *b) {
+      hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, a, (int64_t)nc, b, pt);
+    };
     auto finish = [&](int mode, int k) {
       hipLaunchKernelGGL((k_qm_finish<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, mode, k, S);
     };
@@ -3464,69 +3381,37 @@ class Engine : public EngineBase {
     vec_op(1, n, nc, p, nc, (const D *)z, nc, nullptr, 0);  // p = z
     HIP_OK(hipGetLastError());
     // (one read-back per iteration, after the convergence test; a column that breaks down in mode 5 costs one frozen pass)
-    for (int k = 0, go = qm_active(S); k < maxit && go > 0; ++k) {
+    for (int k = 0, go = krylov_active(S); k < maxit && go > 0; ++k) {
       spmv_dev((const D *)p, nc, q, nc, nc, nullptr);       // q = A p
       dot(p, q);
       finish(2, k);                                         // alpha = rho / p^H q
-      hipLaunchKernelGGL((k_qm_r<D>), grid, blk, 0, stream, n, nc, r, (const D *)q, S, pt);
+      hipLaunchKernelGGL((k_qm_r<D>), grid, blk, 0, stream, n, nc, r, (const D *)q, (const D *)S.alpha, (const int *)S.active, pt);
       finish(3, k);                                         // theta, c^2, tau, eta, zeta
       hipLaunchKernelGGL((k_qm_ds<D>), grid, blk, 0, stream, n, nc, dX, ldx, s, d, g, (const D *)p, (const D *)q, S, pt);
       finish(4, k);                                         // ||s|| / ||b||, maxit
-      if ((go = qm_active(S)) == 0) break;
+      if ((go = krylov_active(S)) == 0) break;
       solve_dev((const D *)r, nc, z, nc, nc, rank, nullptr);
       dot(r, z);
       finish(5, k);                                         // beta = rho' / rho
-      hipLaunchKernelGGL((k_cg_p<D>), grid, blk, 0, stream, n, nc, p, (const D *)z, Sp);
+      hipLaunchKernelGGL((k_cg_p<D>), grid, blk, 0, stream, n, nc, p, (const D *)z, (const D *)S.beta, (const int *)S.active);
       HIP_OK(hipGetLastError());
     }
-    HIP_OK(hipMemcpyAsync(cg_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
-    HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
-    for (int c = 0; c < nc; ++c) {
-      if (iters) iters[c] = cg_pin[1 + c];
-      if (flags) flags[c] = cg_pin[65 + c];
-    }
+    krylov_result(S, nc, flags, iters);
   }
 
   void sqmr_check(int maxit, double rtol) {
-    if (!has_A) throw Error(HIFAMD_BAD_PREC, "symmetric QMR needs the matrix (hifamd_set_matrix)");
-    if (maxit < 1 || !(rtol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need maxit >= 1, rtol > 0");
-    const HermCheck &hc = hermitian();
-    if (!hc.ok)
-      throw Error(HIFAMD_BAD_PREC, "symmetric QMR needs a Hermitian preconditioner and this hierarchy is not one (level " +
-                                       std::to_string(hc.level) + ": " + hc.what +
-                                       "); factorize a Hermitian matrix with is_symm, or use GMRES or BiCGSTAB");
-    if (nsp_on)
-      throw Error(HIFAMD_BAD_PREC, "symmetric QMR does not support a constant null-space filter (hifamd_set_nsp_const)");
+    krylov_check("symmetric QMR", maxit, rtol);
+    hermitian_check("symmetric QMR", "GMRES or BiCGSTAB", "a constant null-space filter");
   }
-
   void sqmr_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                 int *flags, int *iters) {
-    check_batch(dB, ldb, dX, ldx, nrhs);
-    sqmr_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
-      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
-      sqmr_tile(dB + c0, ldb, dX + c0, ldx, nc, rtol, maxit, rank, flags ? flags + c0 : nullptr, iters ? iters + c0 : nullptr);
-    }
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { sqmr_check(maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) { sqmr_tile(b, ldb, x, ldx, nc, rtol, maxit, rank, fl, it); });
   }
-
   void sqmr_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, double rtol, int maxit, int64_t rank,
                  int *flags, int *iters) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    sqmr_check(maxit, rtol);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    StreamWait wait{stream};
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    sqmr_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rtol, maxit, rank, flags, iters);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    staged(B, ldb, X, ldx, nrhs, false, [&] { sqmr_check(maxit, rtol); },
+           [&](const D *b, D *x) { sqmr_dev(b, nrhs, x, nrhs, nrhs, rtol, maxit, rank, flags, iters); });
   }
 
   // ---- on-disk form of the imported hierarchy (import.hpp save_hierarchy / load_hierarchy) -----------------
@@ -3582,19 +3467,7 @@ class Engine : public EngineBase {
 
   // host-pointer product (lhf?Apply with LHF_M / LHF_MH: direct, no refinement, libhifir.cpp:457-460)
   void prod_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int64_t rank) {
-    check_batch(B, ldb, X, ldx, nrhs);
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * nrhs * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    HIP_OK(hipMemcpy2DAsync(stage_b.p, nrhs * sizeof(T), B, ldb * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyHostToDevice, stream));
-    solve_dev(stage_b.as<D>(), nrhs, stage_x.as<D>(), nrhs, nrhs, rank, nullptr, 1);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nrhs * sizeof(T), nrhs * sizeof(T), n,
-                            hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
+    staged(B, ldb, X, ldx, nrhs, true, [] {}, [&](const D *b, D *x) { solve_dev(b, nrhs, x, nrhs, nrhs, rank, nullptr, 1); });
   }
 
   // ---- stats ----------------------------------------------------------------------------------

@@ -28,7 +28,7 @@
 //                    products in one kernel, combined across neighbouring lanes
 //   k_gm_step / k_gm_finish / k_gm_backsolve / k_gm_combine / k_gm_colop   device-resident Arnoldi process of GMRES
 //   k_cg_dot / k_cg_xr / k_cg_p / k_cg_finish   device-resident preconditioned CG (batch-width-independent reductions)
-//   k_bs_hdot / k_bs_xr_half / k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions)
+//   k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions; with k_cg_dot and k_cg_xr)
 //   k_qm_r / k_qm_ds / k_qm_finish   device-resident symmetric QMR for Hermitian indefinite pairs (same reductions;
 //                    with k_cg_dot and k_cg_p)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
@@ -1927,14 +1927,18 @@ __global__ void __launch_bounds__(256) k_gm_colop(int op, int64_t n, int nc, T *
 // ---------------------------------------------------------------------------------------------
 constexpr int kCgBlocks = 1024;  // blocks of 4 waves of every fused pass (and partials per column)
 
-template <class T>
-struct CgState {
-  T *rho, *alpha, *beta;  // [64]  r^H z of the last step, rho / sigma, rho' / rho (0 for a frozen column)
-  double *bnorm;          // [64]  ||b||
+// what the states of the lock-step solvers (PCG, BiCGSTAB, symmetric QMR) share
+struct KrylovState {
+  double *bnorm;              // [64]  ||b||
   int *iter, *flag, *active;  // [64]
-  int *ctl;               // [0] columns still active
+  int *ctl;                   // [0] columns still active
   int maxit;
   double rtol;
+};
+
+template <class T>
+struct CgState : KrylovState {
+  T *rho, *alpha, *beta;  // [64]  r^H z of the last step, rho / sigma, rho' / rho (0 for a frozen column)
 };
 
 // adds the four wave partials of a block in wave order: partial[blockIdx.x][c], stride 64
@@ -1947,34 +1951,40 @@ __device__ __forceinline__ void cg_block_partial(T acc, T *sm /* [4][64] */, T *
     partial[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[c], sm[64 + c]), sm[128 + c]), sm[192 + c]);
 }
 
-// the block's share of sum conj(a_i) b_i per column (b == nullptr: sum |a_i|^2)
+// the block's share of sum conj(a_i) b_i per column (b == nullptr: sum |a_i|^2); a has the row stride lda
 template <class T>
-__global__ void __launch_bounds__(256) k_cg_dot(int64_t n, int nc, const T *__restrict__ a, const T *__restrict__ b,
-                                                T *__restrict__ partial /* [kCgBlocks][64] */) {
+__global__ void __launch_bounds__(256) k_cg_dot(int64_t n, int nc, const T *__restrict__ a, int64_t lda,
+                                                const T *__restrict__ b, T *__restrict__ partial /* [kCgBlocks][64] */) {
   __shared__ T sm[256];
   const int c = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 4;
   T acc = vzero(T());
-  if (c < nc)
-    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
-      const T x = a[i * nc + c];
-      acc = vadd(acc, b ? vmul(vconj(x), b[i * nc + c]) : vfromreal(vabs2(x), T()));
-    }
+  if (c < nc) {
+    // (one loop per form: with the choice inside the loop the load of b stays conditional and the pass does not pipeline)
+    if (b)
+      for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
+        acc = vadd(acc, vmul(vconj(a[i * lda + c]), b[i * nc + c]));
+    else
+      for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
+        acc = vadd(acc, vfromreal(vabs2(a[i * lda + c]), T()));
+  }
   cg_block_partial(acc, sm, partial);
 }
 
-// x += alpha p, r -= alpha q on the active columns, fused with the block's share of |r|^2 (x: row stride ldx)
+// x += alpha p, r -= alpha q on the active columns, fused with the block's share of |r|^2 (x: row stride ldx).  Also
+// BiCGSTAB's half step x += alpha y, r -= alpha v (r then holds s).
 template <class T>
 __global__ void __launch_bounds__(256) k_cg_xr(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
-                                               const T *__restrict__ p, const T *__restrict__ q, CgState<T> S,
+                                               const T *__restrict__ p, const T *__restrict__ q,
+                                               const T *__restrict__ alpha, const int *__restrict__ active,
                                                T *__restrict__ partial /* [kCgBlocks][64] */) {
   __shared__ T sm[256];
   const int c = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 4;
   T acc = vzero(T());
   if (c < nc) {
-    const bool act = S.active[c] != 0;
-    const T al = S.alpha[c];
+    const bool act = active[c] != 0;
+    const T al = alpha[c];
     for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
       T ri = r[i * nc + c];
       if (act) {
@@ -1990,10 +2000,11 @@ __global__ void __launch_bounds__(256) k_cg_xr(int64_t n, int nc, T *__restrict_
 
 // p = z + beta p on the active columns
 template <class T>
-__global__ void __launch_bounds__(256) k_cg_p(int64_t n, int nc, T *__restrict__ p, const T *__restrict__ z, CgState<T> S) {
+__global__ void __launch_bounds__(256) k_cg_p(int64_t n, int nc, T *__restrict__ p, const T *__restrict__ z,
+                                              const T *__restrict__ beta, const int *__restrict__ active) {
   const int c = threadIdx.x & 63;
-  if (c >= nc || !S.active[c]) return;
-  const T be = S.beta[c];
+  if (c >= nc || !active[c]) return;
+  const T be = beta[c];
   const int64_t stride = (int64_t)gridDim.x * 4;
   for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
     p[i * nc + c] = vadd(z[i * nc + c], vmul(be, p[i * nc + c]));
@@ -2003,8 +2014,40 @@ __global__ void __launch_bounds__(256) k_cg_p(int64_t n, int nc, T *__restrict__
 __device__ __forceinline__ bool cg_bad(double v) { return !(v > 0.0) || !isfinite(v); }
 __device__ __forceinline__ bool cg_bad(cplx v) { return !(v.x > 0.0) || !isfinite(v.x) || !isfinite(v.y); }
 
-// Sums the kCgBlocks partials of every column in a fixed order (wave w takes blocks w, w + 16, ..., then the 16 wave
-// sums in wave order) and does the per-column scalar work of step k:
+// The two shared parts of the finishing kernels (one workgroup of 16 waves; every thread calls both).
+// The kCgBlocks partials of column c = threadIdx.x & 63 in a fixed order: wave w takes blocks w, w + 16, ..., then
+// the 16 wave sums are added in wave order.  Thread c < nc gets the total.  partial == nullptr sums to zero.  Its
+// barrier also publishes what the caller wrote to shared memory before (the zeroed active count).
+template <class T>
+__device__ __forceinline__ T cg_sum_partials(const T *__restrict__ partial, int nc, T *sm /* [16][64] */) {
+  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
+  T acc = vzero(T());
+  if (c < nc && partial)
+    for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, partial[(int64_t)b * 64 + c]);
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  T tot = vzero(T());
+  if (threadIdx.x < nc)
+    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
+  return tot;
+}
+// Closes a mode for column c = threadIdx.x < nc: a column that stops here (stop >= 0: its flag, it: its count) leaves
+// the iteration, zero(c) clears the coefficients of a column that is out (so that the vector passes leave it alone; a
+// column that left earlier has them zero already), active[c], and the active count (*cnt, zeroed by the caller) to ctl[0].
+template <class Zero>
+__device__ __forceinline__ void cg_close_mode(const KrylovState &S, int nc, int act, int stop, int it, int *cnt, Zero zero) {
+  if (threadIdx.x < nc) {
+    const int c = threadIdx.x;
+    if (stop >= 0) S.flag[c] = stop, S.iter[c] = it, act = 0;
+    if (!act) zero(c);
+    S.active[c] = act;
+    if (act) atomicAdd(cnt, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) S.ctl[0] = *cnt;
+}
+
+// Sums the kCgBlocks partials of every column (cg_sum_partials) and does the per-column scalar work of step k:
 //   mode 0: ||b||: the state; a zero column is done (x = 0, flag 0, 0 iterations)
 //   mode 1: rho = r^H z of the start                                   (not positive: flag 1, 0 iterations)
 //   mode 2: sigma = p^H A p: alpha = rho / sigma                       (not positive: flag 1, k iterations)
@@ -2015,18 +2058,12 @@ template <class T>
 __global__ void __launch_bounds__(1024) k_cg_finish(const T *__restrict__ partial, int nc, int mode, int k, CgState<T> S) {
   __shared__ T sm[16 * 64];
   __shared__ int cnt;
-  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
-  T acc = vzero(T());
-  if (c < nc)
-    for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, partial[(int64_t)b * 64 + c]);
-  sm[threadIdx.x] = acc;
+  const int c = threadIdx.x & 63;
   if (threadIdx.x == 0) cnt = 0;
-  __syncthreads();
+  const T tot = cg_sum_partials(partial, nc, sm);
+  int act = 0, stop = -1, it = 0;  // stop, it: flag and iterations of a column that stops here
   if (threadIdx.x < nc) {
-    T tot = vzero(T());
-    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
-    int act = S.active[c];
-    int stop = -1, it = 0;  // flag and iterations of a column that stops here
+    act = S.active[c];
     if (mode == 0) {
       const double bn = sqrt(vreal(tot));
       S.bnorm[c] = bn;
@@ -2052,18 +2089,8 @@ __global__ void __launch_bounds__(1024) k_cg_finish(const T *__restrict__ partia
         S.rho[c] = tot;
       }
     }
-    if (stop >= 0) {
-      S.flag[c] = stop;
-      S.iter[c] = it;
-      S.alpha[c] = vzero(T());
-      S.beta[c] = vzero(T());
-      act = 0;
-    }
-    S.active[c] = act;
-    if (act) atomicAdd(&cnt, 1);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) S.ctl[0] = cnt;
+  cg_close_mode(S, nc, act, stop, it, &cnt, [&](int c) { S.alpha[c] = S.beta[c] = vzero(T()); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2074,67 +2101,9 @@ __global__ void __launch_bounds__(1024) k_cg_finish(const T *__restrict__ partia
 // the batch it travels in.  A step is one M^{-1} apply plus one SpMM; one iteration is two steps.
 // ---------------------------------------------------------------------------------------------
 template <class T>
-struct BsState {
+struct BsState : KrylovState {  // (iter counts steps)
   T *rho, *alpha, *omega, *beta;  // [64]  (r^, r), rho / (r^, v), (t, r) / (t, t), (rho' / rho)(alpha / omega); 0 when frozen
-  double *bnorm;                  // [64]  ||b||
-  int *iter, *flag, *active;      // [64]  iter counts steps
-  int *ctl;                       // [0] columns still active
-  int maxit;
-  double rtol;
 };
-
-// the four wave partials of two sums, each added in wave order: p0 / p1[blockIdx.x][c], stride 64
-template <class T>
-__device__ __forceinline__ void bs_block_partial2(T a0, T a1, T *sm /* [2][4][64] */, T *__restrict__ p0,
-                                                  T *__restrict__ p1) {
-  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
-  sm[w * 64 + c] = a0;
-  sm[256 + w * 64 + c] = a1;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    p0[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[c], sm[64 + c]), sm[128 + c]), sm[192 + c]);
-    p1[(int64_t)blockIdx.x * 64 + c] = vadd(vadd(vadd(sm[256 + c], sm[320 + c]), sm[384 + c]), sm[448 + c]);
-  }
-}
-
-// the block's share of (r^, v) = sum conj(r^_i) v_i per column (r^: row stride ldh)
-template <class T>
-__global__ void __launch_bounds__(256) k_bs_hdot(int64_t n, int nc, const T *__restrict__ rh, int64_t ldh,
-                                                 const T *__restrict__ v, T *__restrict__ partial /* [kCgBlocks][64] */) {
-  __shared__ T sm[256];
-  const int c = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * 4;
-  T acc = vzero(T());
-  if (c < nc)
-    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride)
-      acc = vadd(acc, vmul(vconj(rh[i * ldh + c]), v[i * nc + c]));
-  cg_block_partial(acc, sm, partial);
-}
-
-// half step on the active columns: x += alpha y, r -= alpha v (r then holds s), fused with the block's share of |r|^2
-template <class T>
-__global__ void __launch_bounds__(256) k_bs_xr_half(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
-                                                    const T *__restrict__ y, const T *__restrict__ v, BsState<T> S,
-                                                    T *__restrict__ partial /* [kCgBlocks][64] */) {
-  __shared__ T sm[256];
-  const int c = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * 4;
-  T acc = vzero(T());
-  if (c < nc) {
-    const bool act = S.active[c] != 0;
-    const T al = S.alpha[c];
-    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
-      T ri = r[i * nc + c];
-      if (act) {
-        x[i * ldx + c] = vadd(x[i * ldx + c], vmul(al, y[i * nc + c]));
-        ri = vsub(ri, vmul(al, v[i * nc + c]));
-        r[i * nc + c] = ri;
-      }
-      acc = vadd(acc, vfromreal(vabs2(ri), T()));
-    }
-  }
-  cg_block_partial(acc, sm, partial);
-}
 
 // the block's shares of (t, r) = sum conj(t_i) r_i and (t, t) = sum |t_i|^2, one read of t and r
 template <class T>
@@ -2150,7 +2119,8 @@ __global__ void __launch_bounds__(256) k_bs_tr(int64_t n, int nc, const T *__res
       tr = vadd(tr, vmul(vconj(ti), r[i * nc + c]));
       tt = vadd(tt, vfromreal(vabs2(ti), T()));
     }
-  bs_block_partial2(tr, tt, sm, part_tr, part_tt);
+  cg_block_partial(tr, sm, part_tr);
+  cg_block_partial(tt, sm + 256, part_tt);
 }
 
 // full step on the active columns: x += omega y, r -= omega t, fused with the block's shares of |r|^2 and (r^, r)
@@ -2177,7 +2147,8 @@ __global__ void __launch_bounds__(256) k_bs_xr_full(int64_t n, int nc, T *__rest
       hr = vadd(hr, vmul(vconj(rh[i * ldh + c]), ri));
     }
   }
-  bs_block_partial2(rr, hr, sm, part_rr, part_hr);
+  cg_block_partial(rr, sm, part_rr);
+  cg_block_partial(hr, sm + 256, part_hr);
 }
 
 // p = r + beta (p - omega v) on the active columns
@@ -2196,7 +2167,7 @@ __global__ void __launch_bounds__(256) k_bs_p(int64_t n, int nc, T *__restrict__
 __device__ __forceinline__ bool bs_bad(double v) { return v == 0.0 || !isfinite(v); }
 __device__ __forceinline__ bool bs_bad(cplx v) { return (v.x == 0.0 && v.y == 0.0) || !isfinite(v.x) || !isfinite(v.y); }
 
-// Sums the kCgBlocks partials of every column of p0 (and of p1 when given) in k_cg_finish's order and does the
+// Sums the kCgBlocks partials of every column of p0 (and of p1 when given; cg_sum_partials) and does the
 // per-column scalar work of iteration k (steps 2k + 1 and 2k + 2):
 //   mode 0: p0 = ||b||^2: ||b||, rho = ||b||^2; b = 0 is done (x = 0, flag 0, 0 steps); rho bad: flag 1, 0 steps
 //   mode 1: p0 = (r^, v): alpha = rho / (r^, v)                                   (bad: flag 1, 2k + 1 steps)
@@ -2210,23 +2181,12 @@ __global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, co
                                                     int k, BsState<T> S) {
   __shared__ T sm0[16 * 64], sm1[16 * 64];
   __shared__ int cnt;
-  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
-  T a0 = vzero(T()), a1 = vzero(T());
-  if (c < nc) {
-    for (int b = w; b < kCgBlocks; b += 16) a0 = vadd(a0, p0[(int64_t)b * 64 + c]);
-    if (p1)
-      for (int b = w; b < kCgBlocks; b += 16) a1 = vadd(a1, p1[(int64_t)b * 64 + c]);
-  }
-  sm0[threadIdx.x] = a0;
-  sm1[threadIdx.x] = a1;
+  const int c = threadIdx.x & 63;
   if (threadIdx.x == 0) cnt = 0;
-  __syncthreads();
+  const T t0 = cg_sum_partials(p0, nc, sm0), t1 = cg_sum_partials(p1, nc, sm1);
+  int act = 0, stop = -1, it = 0;  // stop, it: flag and steps of a column that stops here
   if (threadIdx.x < nc) {
-    T t0 = vzero(T()), t1 = vzero(T());
-    for (int v = 0; v < 16; ++v) t0 = vadd(t0, sm0[v * 64 + c]);
-    for (int v = 0; v < 16; ++v) t1 = vadd(t1, sm1[v * 64 + c]);
-    int act = S.active[c];
-    int stop = -1, it = 0;  // flag and steps of a column that stops here
+    act = S.active[c];
     if (mode == 0) {
       const double bn = sqrt(vreal(t0));
       S.bnorm[c] = bn;
@@ -2257,19 +2217,9 @@ __global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, co
         S.rho[c] = t1;
       }
     }
-    if (stop >= 0 || !act) {
-      if (stop >= 0) S.flag[c] = stop, S.iter[c] = it;
-      S.rho[c] = vzero(T());
-      S.alpha[c] = vzero(T());
-      S.omega[c] = vzero(T());
-      S.beta[c] = vzero(T());
-      act = 0;
-    }
-    S.active[c] = act;
-    if (act) atomicAdd(&cnt, 1);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) S.ctl[0] = cnt;
+  cg_close_mode(S, nc, act, stop, it, &cnt,
+                [&](int c) { S.rho[c] = S.alpha[c] = S.omega[c] = S.beta[c] = vzero(T()); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2281,13 +2231,9 @@ __global__ void __launch_bounds__(1024) k_bs_finish(const T *__restrict__ p0, co
 // column's bits do not depend on the batch it travels in.  k_cg_dot and k_cg_p serve the inner products and p = z + beta p.
 // ---------------------------------------------------------------------------------------------
 template <class T>
-struct QmState {
-  T *rho, *alpha, *beta, *zeta;            // [64]  r^H z, rho / sigma, rho' / rho, c^2 alpha (0 for a frozen column)
-  double *eta, *tau, *theta, *bnorm;       // [64]  c^2 theta_old^2, the quasi-residual norm, ||r|| / tau_old, ||b||
-  int *iter, *flag, *active;               // [64]
-  int *ctl;                                // [0] columns still active
-  int maxit;
-  double rtol;
+struct QmState : KrylovState {
+  T *rho, *alpha, *beta, *zeta;  // [64]  r^H z, rho / sigma, rho' / rho, c^2 alpha (0 for a frozen column)
+  double *eta, *tau, *theta;     // [64]  c^2 theta_old^2, the quasi-residual norm, ||r|| / tau_old
 };
 
 // a where the column is active, b where it is frozen (component by component: no branch, no stack object)
@@ -2297,15 +2243,16 @@ __device__ __forceinline__ cplx qm_sel(bool act, cplx a, cplx b) { return cplx{a
 // r -= alpha q on the active columns, fused with the block's share of |r|^2: two vectors read, one written.  Every
 // access is unconditional (a frozen column stores back the bits it loaded), so the pass stays pipelined.
 template <class T>
-__global__ void __launch_bounds__(256) k_qm_r(int64_t n, int nc, T *__restrict__ r, const T *__restrict__ q, QmState<T> S,
+__global__ void __launch_bounds__(256) k_qm_r(int64_t n, int nc, T *__restrict__ r, const T *__restrict__ q,
+                                              const T *__restrict__ alpha, const int *__restrict__ active,
                                               T *__restrict__ partial /* [kCgBlocks][64] */) {
   __shared__ T sm[256];
   const int c = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 4;
   T acc = vzero(T());
   if (c < nc) {
-    const bool act = S.active[c] != 0;
-    const T al = S.alpha[c];
+    const bool act = active[c] != 0;
+    const T al = alpha[c];
     for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
       const T r0 = r[i * nc + c], qi = q[i * nc + c];
       const T r1 = vsub(r0, vmul(al, qi));
@@ -2348,7 +2295,7 @@ __global__ void __launch_bounds__(256) k_qm_ds(int64_t n, int nc, T *__restrict_
   cg_block_partial(acc, sm, partial);
 }
 
-// Sums the kCgBlocks partials of every column in k_cg_finish's order and does the per-column scalar work of iteration k.
+// Sums the kCgBlocks partials of every column (cg_sum_partials) and does the per-column scalar work of iteration k.
 // alpha and beta are formed as k_cg_finish modes 1, 2 and 4 form them; a breakdown value is exactly zero or not finite
 // (bs_bad), with no sign test:
 //   mode 0: ||b||: the state, tau = ||b||, theta = 0; a zero column is done (x = 0, flag 0, 0 iterations)
@@ -2363,18 +2310,12 @@ template <class T>
 __global__ void __launch_bounds__(1024) k_qm_finish(const T *__restrict__ partial, int nc, int mode, int k, QmState<T> S) {
   __shared__ T sm[16 * 64];
   __shared__ int cnt;
-  const int w = threadIdx.x >> 6, c = threadIdx.x & 63;
-  T acc = vzero(T());
-  if (c < nc)
-    for (int b = w; b < kCgBlocks; b += 16) acc = vadd(acc, partial[(int64_t)b * 64 + c]);
-  sm[threadIdx.x] = acc;
+  const int c = threadIdx.x & 63;
   if (threadIdx.x == 0) cnt = 0;
-  __syncthreads();
+  const T tot = cg_sum_partials(partial, nc, sm);
+  int act = 0, stop = -1, it = 0;  // stop, it: flag and iterations of a column that stops here
   if (threadIdx.x < nc) {
-    T tot = vzero(T());
-    for (int v = 0; v < 16; ++v) tot = vadd(tot, sm[v * 64 + c]);
-    int act = S.active[c];
-    int stop = -1, it = 0;  // flag and iterations of a column that stops here
+    act = S.active[c];
     if (mode == 0) {
       const double bn = sqrt(vreal(tot));
       S.bnorm[c] = bn;
@@ -2412,20 +2353,11 @@ __global__ void __launch_bounds__(1024) k_qm_finish(const T *__restrict__ partia
         S.rho[c] = tot;
       }
     }
-    if (stop >= 0) {
-      S.flag[c] = stop;
-      S.iter[c] = it;
-      S.alpha[c] = vzero(T());
-      S.beta[c] = vzero(T());
-      S.zeta[c] = vzero(T());
-      S.eta[c] = 0.0;
-      act = 0;
-    }
-    S.active[c] = act;
-    if (act) atomicAdd(&cnt, 1);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) S.ctl[0] = cnt;
+  cg_close_mode(S, nc, act, stop, it, &cnt, [&](int c) {
+    S.alpha[c] = S.beta[c] = S.zeta[c] = vzero(T());
+    S.eta[c] = 0.0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -555,31 +555,32 @@ class HIF:
         it, fl = st[0::2].copy(), st[1::2].copy()
         return (x, int(it[0]), int(fl[0])) if vec else (x, it, fl)
 
-    def gmres(self, b, restart=30, rtol=1e-6, maxit=500, full_rank=False):
-        """Right-preconditioned restarted GMRES (the reference's examples/advanced/gmres.hpp:19-123),
-        all columns of b ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.
-        Returns (x, flags, iters); ints for a vector."""
+    def _krylov(self, name, b, *lead, rtol, maxit, full_rank):
+        """The batched solver hifamd_<name>_batch (host array) or hifamd_<name>_batch_dev (CUDA tensor) on all columns of
+        b; lead are the solver's arguments ahead of rtol.  Returns (x, flags, iters); ints for a vector."""
         vec = (b.ndim == 1)
-        rank = -1 if full_rank else 0
         if _is_torch(b):
             import torch
 
             B = self._dev_block(b.reshape(b.shape[0], -1), "b")
             X = torch.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_gmres_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0), B.shape[1],
-                                               int(restart), float(rtol), int(maxit), rank, _p(fl), _p(it)))
+            fn, io = getattr(lib(), "hifamd_%s_batch_dev" % name), (B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0))
         else:
             B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
             X = np.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_gmres_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], int(restart),
-                                           float(rtol), int(maxit), rank, _p(fl), _p(it)))
+            fn, io = getattr(lib(), "hifamd_%s_batch" % name), (_p(B), B.shape[1], _p(X), X.shape[1])
+        fl = np.zeros(B.shape[1], dtype=np.int32)
+        it = np.zeros(B.shape[1], dtype=np.int32)
+        _check(fn(self._h, *io, B.shape[1], *lead, float(rtol), int(maxit), -1 if full_rank else 0, _p(fl), _p(it)))
         if vec:
             return X.reshape(-1), int(fl[0]), int(it[0])
         return X, fl, it
+
+    def gmres(self, b, restart=30, rtol=1e-6, maxit=500, full_rank=False):
+        """Right-preconditioned restarted GMRES (the reference's examples/advanced/gmres.hpp:19-123),
+        all columns of b ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.
+        Returns (x, flags, iters); ints for a vector."""
+        return self._krylov("gmres", b, int(restart), rtol=rtol, maxit=maxit, full_rank=full_rank)
 
     def is_hermitian(self):
         """True when M^{-1} of the imported hierarchy is Hermitian (hifamd_hermitian: exact test on the host copy, every
@@ -593,81 +594,21 @@ class HIF:
         """Preconditioned CG (x0 = 0) for a Hermitian positive-definite pair (A, M), all columns of b ([n] or
         [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix and is_hermitian().
         Returns (x, flags, iters); ints for a vector.  flags: 0 converged, 1 breakdown, 2 reached maxit."""
-        vec = (b.ndim == 1)
-        rank = -1 if full_rank else 0
-        if _is_torch(b):
-            import torch
-
-            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
-            X = torch.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_pcg_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0), B.shape[1],
-                                             float(rtol), int(maxit), rank, _p(fl), _p(it)))
-        else:
-            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
-            X = np.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_pcg_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
-                                         int(maxit), rank, _p(fl), _p(it)))
-        if vec:
-            return X.reshape(-1), int(fl[0]), int(it[0])
-        return X, fl, it
+        return self._krylov("pcg", b, rtol=rtol, maxit=maxit, full_rank=full_rank)
 
     def sqmr(self, b, rtol=1e-6, maxit=500, full_rank=False):
         """Symmetric QMR (Freund / Nachtigal, x0 = 0) for a Hermitian pair (A, M) that may be indefinite, all columns of b
         ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix and is_hermitian().
         One apply plus one SpMM per iteration.  Returns (x, flags, iters); ints for a vector.  flags: 0 converged,
         1 breakdown, 2 reached maxit."""
-        vec = (b.ndim == 1)
-        rank = -1 if full_rank else 0
-        if _is_torch(b):
-            import torch
-
-            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
-            X = torch.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_sqmr_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0), B.shape[1],
-                                              float(rtol), int(maxit), rank, _p(fl), _p(it)))
-        else:
-            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
-            X = np.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_sqmr_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
-                                          int(maxit), rank, _p(fl), _p(it)))
-        if vec:
-            return X.reshape(-1), int(fl[0]), int(it[0])
-        return X, fl, it
+        return self._krylov("sqmr", b, rtol=rtol, maxit=maxit, full_rank=full_rank)
 
     def bicgstab(self, b, rtol=1e-6, maxit=500, full_rank=False):
         """Right-preconditioned BiCGSTAB (x0 = 0, shadow residual b) for a general pair (A, M), all columns of b ([n] or
         [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix.  maxit and iters count
         steps (one apply plus one SpMM each; two per iteration).  Returns (x, flags, iters); ints for a vector.
         flags: 0 converged, 1 breakdown, 2 reached maxit."""
-        vec = (b.ndim == 1)
-        rank = -1 if full_rank else 0
-        if _is_torch(b):
-            import torch
-
-            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
-            X = torch.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_bicgstab_batch_dev(self._h, B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0),
-                                                  B.shape[1], float(rtol), int(maxit), rank, _p(fl), _p(it)))
-        else:
-            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
-            X = np.empty_like(B)
-            fl = np.zeros(B.shape[1], dtype=np.int32)
-            it = np.zeros(B.shape[1], dtype=np.int32)
-            _check(lib().hifamd_bicgstab_batch(self._h, _p(B), B.shape[1], _p(X), X.shape[1], B.shape[1], float(rtol),
-                                              int(maxit), rank, _p(fl), _p(it)))
-        if vec:
-            return X.reshape(-1), int(fl[0]), int(it[0])
-        return X, fl, it
+        return self._krylov("bicgstab", b, rtol=rtol, maxit=maxit, full_rank=full_rank)
 
     def fgmres(self, b, restart=30, rtol=1e-6, maxit=500, full_rank=False):
         """Flexible GMRES with 2^k refinement sweeps as the preconditioner of outer cycle k (the reference's

@@ -4,7 +4,7 @@ factorized with default parameters by the compiled reference, 64 columns, device
   python tests/dev_krylov.py [--out DIR]          memory, ms per step, steps and time to 1e-8 -> DIR/krylov.json (DIR: .)
   python tests/dev_krylov.py --trace-steps K      one K-step BiCGSTAB call after a warm-up, for a
                                                   rocprofv3 --kernel-trace --stats run of its own
-  python tests/dev_krylov.py --kernel-stats CSV   each k_bs_* kernel's time and bytes/s from the stats CSV of that run
+  python tests/dev_krylov.py --kernel-stats CSV   each BiCGSTAB kernel's time and bytes/s from the stats CSV of that run
                                                   (bytes from the shapes: n = 10^6 rows, 64 columns, 8 B)
 """
 import argparse
@@ -22,8 +22,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 N, NC = 1000 * 1000, 64
 VEC = N * NC * 8
-# vectors of [n][64] float64 each kernel reads plus writes
-KERNEL_VECS = {"k_bs_hdot": 2, "k_bs_xr_half": 6, "k_bs_tr": 2, "k_bs_xr_full": 7, "k_bs_p": 4, "k_bs_finish": 0}
+# vectors of [n][64] float64 each kernel reads plus writes (k_cg_dot: the (r^, v) pass; the ||b||^2 pass at the head of
+# every call is the same kernel reading one vector, and the stats row averages over both)
+KERNEL_VECS = {"k_cg_dot": 2, "k_cg_xr": 6, "k_bs_tr": 2, "k_bs_xr_full": 7, "k_bs_p": 4, "k_bs_finish": 0}
 
 
 def setup():

@@ -128,7 +128,7 @@ def kernel_stats(path):
     groups = {}
     for r in csv.DictReader(open(path)):
         name = (r.get("Kernel_Name") or r.get("Name") or "").replace(" ", "")
-        m = re.search(r"(k_nsp_coef|k_nsp_sub|k_nsp_finish|k_colsum_partial|k_sub_colmean|k_bs_xr_half|k_bs_hdot|k_bs_finish)<([^>]*)>", name)
+        m = re.search(r"(k_nsp_coef|k_nsp_sub|k_nsp_finish|k_colsum_partial|k_sub_colmean|k_cg_xr|k_cg_dot|k_bs_finish)<([^>]*)>", name)
         if not m or not m.group(2).startswith("double"):
             continue
         key = m.group(1) + "<" + m.group(2) + ">"
@@ -142,7 +142,7 @@ def kernel_stats(path):
         if m:
             nbytes = (1 if m.group(1) == "coef" else 2) * VEC + N * int(m.group(2)) * 8
         else:
-            nbytes = {"k_colsum_partial": 1, "k_sub_colmean": 2, "k_bs_xr_half": 6, "k_bs_hdot": 2}.get(key.split("<")[0], 0) * VEC
+            nbytes = {"k_colsum_partial": 1, "k_sub_colmean": 2, "k_cg_xr": 6, "k_cg_dot": 2}.get(key.split("<")[0], 0) * VEC
         us = float(np.mean(d)) / 1e3
         out[key] = {"calls": len(d), "avg_us": us, "min_us": min(d) / 1e3, "bytes": nbytes,
                     "GB_per_s": (nbytes / us / 1e3) if nbytes else None}

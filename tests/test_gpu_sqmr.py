@@ -1,7 +1,8 @@
 """GPU (-m gpu): the batched symmetric QMR driver (hifamd_sqmr_batch / HIF.sqmr) on Hermitian indefinite hierarchies against
 the numpy restatement of the same recurrence around the oracle's apply (test_sqmr_host.sqmr_restated), where PCG breaks
 down; its batch-width independence; a complex Hermitian indefinite hierarchy made from a real one by a diagonal unitary
-similarity; its flags and refusals; and the projected iteration under a basis null-space filter."""
+similarity; its flags and refusals; the projected iteration under a basis null-space filter; and, since this file runs several
+solvers on one handle, that the buffers they share carry nothing from one call into the next."""
 import numpy as np
 import pytest
 
@@ -108,6 +109,54 @@ def test_complex_hermitian_indefinite_hierarchy():
     Xo, fo, io = sqmr_restated(orc.Oracle(lz).solve, Az, Bz, 1e-10, MAXIT)
     _check_vs_restated(Xz, flz, itz, Xo, fo, io, Az, Bz, 1e-10)
     assert flz.tolist() == [0, 0, 0]
+
+
+def _mixed_batch(n, ncol, seed, cplx=False):
+    """seeded uniform columns; the 70-wide ones hold a zero column and one scaled by 1e-8, so columns freeze at different steps"""
+    rng = np.random.default_rng(seed)
+    B = rng.uniform(-1, 1, size=(n, ncol))
+    if cplx:
+        B = B + 1j * rng.uniform(-1, 1, size=(n, ncol))
+    if ncol == 70:
+        B[:, 9] = 0.0
+        B[:, 66] *= 1e-8
+    return B
+
+
+def _solvers_share_nothing(make, n, calls, cplx=False):
+    """every call of the sequence on ONE handle gives the bits of the same call on a fresh handle that ran nothing else"""
+    M = make()
+    for k, (solver, ncol, kw) in enumerate(calls):
+        B = _mixed_batch(n, ncol, 100 + k, cplx)
+        b = B[:, 0].copy() if ncol == 1 else B
+        X, fl, it = getattr(M, solver)(b, **kw)
+        Xf, ff, itf = getattr(make(), solver)(b, **kw)
+        print(k, solver, ncol, "flags", np.unique(fl), "iters", np.min(it), np.max(it))
+        assert np.array_equal(X, Xf) and np.array_equal(fl, ff) and np.array_equal(it, itf), (k, solver, ncol)
+
+
+def test_solvers_on_one_handle_leave_nothing_behind():
+    """PCG, BiCGSTAB, symmetric QMR and GMRES share the work vectors, the state block and the pinned read-back buffer of a
+    handle: no scalar, active mask or vector of one call (another solver, another width, another sizeof) reaches the next"""
+    levels, d, O, A = fixture("p2d_32_symm")
+
+    def make():
+        M = hifir_amd.HIF.from_levels(levels, max_nrhs=64)
+        M.set_matrix(d["A_indptr"], d["A_indices"], d["A_vals"])
+        return M
+
+    kw = dict(rtol=1e-8, maxit=MAXIT)
+    _solvers_share_nothing(make, A.shape[0], [("sqmr", 70, kw), ("pcg", 5, kw), ("bicgstab", 64, kw),
+                                              ("gmres", 3, dict(restart=5, rtol=1e-8, maxit=MAXIT)), ("pcg", 70, kw),
+                                              ("sqmr", 1, kw)])
+    lz, Az = complex_case()[:2]
+
+    def make_z():
+        Mz = hifir_amd.HIF.from_levels(lz, max_nrhs=64)
+        Mz.set_matrix(Az.indptr, Az.indices, Az.data)
+        return Mz
+
+    _solvers_share_nothing(make_z, Az.shape[0], [("sqmr", 70, kw), ("bicgstab", 5, kw), ("sqmr", 64, kw)], cplx=True)
 
 
 def test_flags_and_refusals():
