@@ -7,6 +7,7 @@ import pytest
 import scipy.sparse as sp
 
 import hifir_amd
+from krylov_edges_util import perturbed as _perturbed
 from oracle import orc, ref
 from util import load_hier, relerr
 
@@ -112,18 +113,6 @@ def test_flexible_gmres(cache, name, restart, rtol, maxit):
         xr, fr, ir, mr = R.fgmres(d["b"], restart=restart, rtol=rtol, maxit=maxit)
         assert (int(fl[0]), int(it[0]), int(mv[0])) == (fr, ir, mr)
         assert relerr(X[:, 0], xr) <= 1e-7
-
-
-def _perturbed(d, amp, seed=7):
-    """the fixture's matrix with a random complex diagonal added: the hierarchy becomes a mediocre preconditioner,
-    so that the solve needs tens of iterations and crosses restarts"""
-    n = len(d["b"])
-    A = sp.csr_matrix((d["A_vals"], d["A_indices"], d["A_indptr"]), shape=(n, n))
-    if amp:
-        rng = np.random.default_rng(seed)
-        A = (A + sp.diags(amp * abs(A).max() * (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)))).tocsr()
-    A.sort_indices()
-    return A
 
 
 @pytest.mark.parametrize("name,amp,restart,rtol,maxit", [("young1c", 0.0, 30, 1e-10, 200), ("young1c", 0.05, 12, 1e-9, 300),
