@@ -10,85 +10,13 @@ import scipy.sparse as sp
 
 import hifir_amd
 from hifir_amd._lib import lib
+from lockstep_edges_util import bicgstab_restated
 from oracle import orc, ref
 from util import load_hier, poisson2d, relerr
 
 pytestmark = pytest.mark.gpu
 
 NULL_OBJ, MISMATCHED_SIZES, BAD_PREC = 1, 2, 3
-
-
-def _bad(v):
-    return v == 0 or not np.isfinite(v)
-
-
-def bicgstab_restated(O, A, B, rtol, maxit, nsp=False):
-    """Column by column, verbatim: r = b, r^ = b, rho = (r^, r), p = r; loop: y = M^{-1} p, v = A y (a step),
-    alpha = rho / (r^, v), x += alpha y, r -= alpha v, test; y = M^{-1} r, t = A y (a step), omega = (t, r) / (t, t),
-    x += omega y, r -= omega t, test; rho' = (r^, r), beta = (rho' / rho)(alpha / omega), rho = rho',
-    p = r + beta (p - omega v).  Test: ||r|| / ||b|| <= rtol -> flag 0, else steps == maxit -> flag 2.  (r^, v), (t, t),
-    omega, rho' or the initial rho exactly zero or not finite: flag 1.  nsp: every M^{-1} apply loses its mean."""
-    B = B.reshape(B.shape[0], -1)
-    X = np.zeros_like(B)
-    flags = np.zeros(B.shape[1], dtype=np.int32)
-    iters = np.zeros(B.shape[1], dtype=np.int32)
-
-    def prec(u):
-        y = O.solve(u.copy())
-        return y - y.mean() if nsp else y
-
-    for c in range(B.shape[1]):
-        b = B[:, c]
-        bn = np.linalg.norm(b)
-        if bn == 0.0:
-            continue
-        x = np.zeros_like(b)
-        r = b.copy()
-        rh = b.copy()
-        rho = np.vdot(rh, r)
-        p = r.copy()
-        flag, steps = 1, 0
-        while not _bad(rho):
-            y = prec(p)
-            v = A @ y
-            steps += 1
-            rv = np.vdot(rh, v)
-            if _bad(rv):
-                break
-            alpha = rho / rv
-            x = x + alpha * y
-            r = r - alpha * v
-            if np.linalg.norm(r) / bn <= rtol:
-                flag = 0
-                break
-            if steps >= maxit:
-                flag = 2
-                break
-            y = prec(r)
-            t = A @ y
-            steps += 1
-            tt = np.vdot(t, t)
-            if _bad(tt):
-                break
-            omega = np.vdot(t, r) / tt
-            if _bad(omega):
-                break
-            x = x + omega * y
-            r = r - omega * t
-            if np.linalg.norm(r) / bn <= rtol:
-                flag = 0
-                break
-            if steps >= maxit:
-                flag = 2
-                break
-            rho1 = np.vdot(rh, r)
-            if _bad(rho1):
-                break
-            beta = (rho1 / rho) * (alpha / omega)
-            rho = rho1
-            p = r + beta * (p - omega * v)
-        X[:, c], flags[c], iters[c] = x, flag, steps
-    return X, flags, iters
 
 
 def _matrix(d):

@@ -9,60 +9,11 @@ import pytest
 import scipy.sparse as sp
 
 import hifir_amd
+from lockstep_edges_util import pcg_restated
 from oracle import orc, ref
 from util import load_hier, poisson2d, relerr
 
 pytestmark = pytest.mark.gpu
-
-
-def _bad(v):
-    return not (np.isfinite(v) and np.real(v) > 0.0)
-
-
-def pcg_restated(O, A, B, rtol, maxit):
-    """Column by column: x0 = 0, r = b, z = M^{-1} r, p = z, rho = r^H z; per step q = A p, alpha = rho / p^H q,
-    x += alpha p, r -= alpha q, stop on |r| / |b| <= rtol (flag 0) or after maxit steps (flag 2), z = M^{-1} r,
-    rho' = r^H z, p = z + (rho' / rho) p.  A non-positive or non-finite p^H A p or r^H z is a breakdown (flag 1)."""
-    B = B.reshape(B.shape[0], -1)
-    X = np.zeros_like(B)
-    flags = np.zeros(B.shape[1], dtype=np.int32)
-    iters = np.zeros(B.shape[1], dtype=np.int32)
-    for c in range(B.shape[1]):
-        b = B[:, c]
-        bn = np.linalg.norm(b)
-        if bn == 0.0:
-            continue
-        x = np.zeros_like(b)
-        r = b.copy()
-        z = O.solve(r.copy())
-        p = z.copy()
-        rho = np.vdot(r, z)
-        flag, it = 1, 0
-        if not _bad(rho):
-            for k in range(maxit):
-                q = A @ p
-                sigma = np.vdot(p, q)
-                if _bad(sigma):
-                    flag, it = 1, k
-                    break
-                alpha = rho / sigma
-                x = x + alpha * p
-                r = r - alpha * q
-                if np.linalg.norm(r) / bn <= rtol:
-                    flag, it = 0, k + 1
-                    break
-                if k + 1 >= maxit:
-                    flag, it = 2, maxit
-                    break
-                z = O.solve(r.copy())
-                rho1 = np.vdot(r, z)
-                if _bad(rho1):
-                    flag, it = 1, k + 1
-                    break
-                p = z + (rho1 / rho) * p
-                rho = rho1
-        X[:, c], flags[c], iters[c] = x, flag, it
-    return X, flags, iters
 
 
 def _matrix(d):

@@ -1,5 +1,5 @@
 """CPU: the symmetric QMR driver (hifamd_sqmr_batch / HIF.sqmr) without a GPU -- its two Hermitian indefinite fixtures load,
-import and pass the Hermitian test; a numpy restatement of the recurrence around the oracle's apply (sqmr_restated,
+import and pass the Hermitian test; a numpy restatement of the recurrence around the oracle's apply (lockstep_edges_util.sqmr_restated,
 shared with test_gpu_sqmr.py) converges on them where the PCG restatement breaks down; every stopping decision the GPU
 test compares iteration counts on keeps a margin; and the entry points refuse a NULL handle and an unfinalized
 hierarchy (no CPU fallback)."""
@@ -9,6 +9,8 @@ import scipy.sparse as sp
 
 import hifir_amd
 from hifir_amd._lib import lib
+import lockstep_edges_util
+from lockstep_edges_util import sqmr_restated  # noqa: F401  (test_gpu_sqmr.py takes it from here)
 from oracle import orc
 from util import load_hier
 
@@ -21,102 +23,11 @@ PROJ_RTOLS = (1e-8, 1e-10)
 MARGIN = 1.02  # the last two ||s|| / ||b|| of every compared column lie outside [rtol / MARGIN, MARGIN * rtol]
 
 
-def _bad(v):
-    """a breakdown value: exactly zero or not finite (no sign test)"""
-    return v == 0 or not np.isfinite(v)
-
-
-def sqmr_restated(solve, A, B, rtol, maxit, hist=None):
-    """Column by column, x0 = 0 (solve(r) is M^{-1} r, filtered where the handle filters it; B is P b then):
-    r = s = b, tau = |b|, theta = 0, d = g = 0, z = M^{-1} r, rho = r^H z, p = z; per iteration q = A p, sigma = p^H q,
-    alpha = rho / sigma, r -= alpha q, theta' = |r| / tau, c2 = 1 / (1 + theta'^2), tau = tau theta' sqrt(c2),
-    eta = c2 theta^2, zeta = c2 alpha, theta = theta', d = eta d + zeta p, g = eta g + zeta q, x += d, s -= g, stop on
-    |s| / |b| <= rtol (flag 0) or after maxit iterations (flag 2), z = M^{-1} r, rho' = r^H z, p = z + (rho' / rho) p.
-    rho or sigma exactly zero or not finite is a breakdown (flag 1).  hist (a list) gets one list per column: |s| / |b|
-    after every iteration."""
-    B = B.reshape(B.shape[0], -1)
-    X = np.zeros_like(B)
-    flags = np.zeros(B.shape[1], dtype=np.int32)
-    iters = np.zeros(B.shape[1], dtype=np.int32)
-    for c in range(B.shape[1]):
-        b = B[:, c]
-        h = []
-        if hist is not None:
-            hist.append(h)
-        bn = np.linalg.norm(b)
-        if bn == 0.0:
-            continue
-        x = np.zeros_like(b)
-        r, s = b.copy(), b.copy()
-        d, g = np.zeros_like(b), np.zeros_like(b)
-        tau, theta = bn, 0.0
-        z = solve(r.copy())
-        p = z.copy()
-        rho = np.vdot(r, z)
-        flag, it = 1, 0
-        if not _bad(rho):
-            for k in range(maxit):
-                q = A @ p
-                sigma = np.vdot(p, q)
-                if _bad(sigma):
-                    flag, it = 1, k
-                    break
-                alpha = rho / sigma
-                r = r - alpha * q
-                th = np.linalg.norm(r) / tau
-                c2 = 1.0 / (1.0 + th * th)
-                tau = tau * th * np.sqrt(c2)
-                eta, zeta = c2 * theta * theta, c2 * alpha
-                theta = th
-                d = eta * d + zeta * p
-                g = eta * g + zeta * q
-                x = x + d
-                s = s - g
-                h.append(float(np.linalg.norm(s) / bn))
-                if h[-1] <= rtol:
-                    flag, it = 0, k + 1
-                    break
-                if k + 1 >= maxit:
-                    flag, it = 2, maxit
-                    break
-                z = solve(r.copy())
-                rho1 = np.vdot(r, z)
-                if _bad(rho1):
-                    flag, it = 1, k + 1
-                    break
-                p = z + (rho1 / rho) * p
-                rho = rho1
-        X[:, c], flags[c], iters[c] = x, flag, it
-    return X, flags, iters
-
-
 def pcg_restated(solve, A, b, rtol, maxit):
-    """PCG's flag and iterations for one column (test_gpu_pcg.pcg_restated: a non-positive or non-finite p^H A p or
+    """PCG's flag and iterations for one column (lockstep_edges_util.pcg_restated: a non-positive or non-finite p^H A p or
     r^H M^{-1} r is a breakdown, flag 1)."""
-    def bad(v):
-        return not (np.isfinite(v) and np.real(v) > 0.0)
-
-    bn = np.linalg.norm(b)
-    r = b.copy()
-    z = solve(r.copy())
-    p, rho = z.copy(), np.vdot(r, z)
-    if bad(rho):
-        return 1, 0
-    for k in range(maxit):
-        q = A @ p
-        sigma = np.vdot(p, q)
-        if bad(sigma):
-            return 1, k
-        alpha = rho / sigma
-        r = r - alpha * q
-        if np.linalg.norm(r) / bn <= rtol:
-            return 0, k + 1
-        z = solve(r.copy())
-        rho1 = np.vdot(r, z)
-        if bad(rho1):
-            return 1, k + 1
-        p, rho = z + (rho1 / rho) * p, rho1
-    return 2, maxit
+    X, fl, it = lockstep_edges_util.pcg_restated(solve, A, b, rtol, maxit)
+    return int(fl[0]), int(it[0])
 
 
 def matrix(d):
