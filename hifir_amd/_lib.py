@@ -62,6 +62,14 @@ SIGNATURES = {
     "hifamd_gmres_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_gmres_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_fgmres_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _dbl, _int, _i64, _vp, _vp, _vp]),
+    "hifamd_set_residual_precision": (_int, [_vp, _int]),
+    "hifamd_residual_precision": (_int, [_vp]),
+    "hifamd_residual_batch": (_int, [_vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _int]),
+    "hifamd_residual_batch_dev": (_int, [_vp, _int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _int, _vp]),
+    "hifamd_gmres_ir_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _dbl, _dbl, _int, _int, _i64, _vp, _vp, _vp,
+                                     _vp]),
+    "hifamd_gmres_ir_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _dbl, _dbl, _int, _int, _i64, _vp, _vp,
+                                         _vp, _vp]),
     "hifamd_hermitian": (_int, [_vp]),
     "hifamd_pcg_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_pcg_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),

@@ -609,6 +609,9 @@ class Engine : public EngineBase {
   DevBuf nsp_Q, nsp_cpart, nsp_C;
   DevBuf gm_Q, gm_Z, gm_alpha;  // GMRES: Krylov basis, per-column coefficients (its work vectors: kr_vec)
   int64_t ir_cols = 0;
+  // how resid_dev forms r = b - A x: 0 working precision (k_crs_spmm), 1 compensated (k_crs_resid_dd); from the
+  // environment at creation (import.hpp resid_mode_from_env), hifamd_set_residual_precision later
+  int resid_mode = 0;
 
   explicit Engine(int dev) : device(dev) {
     // Import and host-side analysis (CCS -> CSR, level schedules, dense QRCP) need no GPU; the
@@ -651,6 +654,7 @@ class Engine : public EngineBase {
     fuse_gather = env_int("HIFIR_AMD_FUSE_S1", 1) != 0;
     spmm_tiles = env_int("HIFIR_AMD_SPMM_TILES", 1) != 0;
     use_twin = env_int("HIFIR_AMD_TWIN", 1);
+    resid_mode = resid_mode_from_env();
     xcd_remap = env_int("HIFIR_AMD_XCD", 1);
     band_opt.thin_rows = env_int("HIFIR_AMD_THIN_ROWS", 96);
     band_opt.band_depth = env_int("HIFIR_AMD_BAND_DEPTH", 32);
@@ -827,6 +831,14 @@ class Engine : public EngineBase {
     device_inverses = P.device_inverses, xcd_remap = P.xcd_remap;
     tail_probe_tol = P.tail_probe_tol, tail_max_growth = P.tail_max_growth;
     zop_flags = P.zop_flags, zop_top_max = P.zop_top_max;  // (band_opt, copied above, carries the top_max they chose)
+    resid_mode = P.resid_mode;
+  }
+
+  // the residual mode of this engine and of every engine built from it so far (those built later inherit it)
+  void set_resid_mode(int mode) {
+    resid_mode = mode;
+    for (auto &tw : twins) tw->set_resid_mode(mode);
+    if (adj) adj->set_resid_mode(mode);
   }
 
   Engine<T> &adjoint_engine() {
@@ -2640,7 +2652,7 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_probe_fill<D>), dim3(vec_grid(n * K)), dim3(256), 0, stream, n, seed, V);
     }
     vec_op(0, n, K, Dx, K, nullptr, 0, nullptr, 0);
-    resid_dev((const D *)Dx, K, (const D *)V, K, B, K, K);  // B = 0 - A X0
+    resid_dev((const D *)Dx, K, (const D *)V, K, B, K, K, 0);  // B = 0 - A X0, in working precision whatever the mode
     std::vector<int> flags((size_t)K, 0), iters((size_t)K, 0);
     gmres_dev((const D *)B, K, Dx, K, K, restart, rtol, maxit, rank, flags.data(), iters.data());
     vec_op(2, n, K, V, K, (const D *)Dx, K, nullptr, 0);  // V = X0 + D
@@ -2811,15 +2823,56 @@ class Engine : public EngineBase {
     HIP_OK(hipGetLastError());
   }
 
-  void resid_dev(const D *dB, int64_t ldb, const D *dX, int64_t ldx, D *dR, int64_t ldr, int64_t nrhs) {
+  // r = b - A x; mode 0: in working precision, mode 1: compensated (k_crs_resid_dd)
+  void resid_dev(const D *dB, int64_t ldb, const D *dX, int64_t ldx, D *dR, int64_t ldr, int64_t nrhs, int mode,
+                 hipStream_t user = nullptr) {
+    hipStream_t st = user ? user : stream;
     for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
       const int nc = (int)std::min<int64_t>(64, nrhs - c0);
       const int logR = pick_logR(nc);
-      hipLaunchKernelGGL((k_crs_spmm<D, true>), dim3(grid_for(A.nrows, logR)), dim3(256), 0, stream, A.nrows,
-                         A.ptr.as<int32_t>(), A.col.as<int32_t>(), A.val.as<D>(), dX + c0, ldx, dB + c0, ldb,
-                         dR + c0, ldr, nc, logR);
+      if (mode == 1)  // (requests two nonzeros ahead: four and eight measured slower)
+        hipLaunchKernelGGL((k_crs_resid_dd<D, 2>), dim3(grid_for(A.nrows, logR)), dim3(256), 0, st, A.nrows,
+                           A.ptr.as<int32_t>(), A.col.as<int32_t>(), A.val.as<D>(), dX + c0, ldx, dB + c0, ldb,
+                           dR + c0, ldr, nc, logR);
+      else
+        hipLaunchKernelGGL((k_crs_spmm<D, true>), dim3(grid_for(A.nrows, logR)), dim3(256), 0, st, A.nrows,
+                           A.ptr.as<int32_t>(), A.col.as<int32_t>(), A.val.as<D>(), dX + c0, ldx, dB + c0, ldb,
+                           dR + c0, ldr, nc, logR);
     }
     HIP_OK(hipGetLastError());
+  }
+
+  // hifamd_residual_batch(_dev) on this engine (the adjoint engine: r = b - A^H x); mode -1: the handle's
+  void residual_check(const void *B, int64_t ldb, const void *X, int64_t ldx, const void *R, int64_t ldr, int64_t nrhs) const {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "the residual needs the matrix (hifamd_set_matrix)");
+    if (!B || !X || !R) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    if (nrhs < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "nrhs must be >= 1");
+    if (ldb < nrhs || ldx < nrhs || ldr < nrhs) throw Error(HIFAMD_MISMATCHED_SIZES, "row stride smaller than nrhs");
+    if (R == B || R == X) throw Error(HIFAMD_BAD_PREC, "r must not alias b or x");
+  }
+  void residual_dev(const D *dB, int64_t ldb, const D *dX, int64_t ldx, D *dR, int64_t ldr, int64_t nrhs, int mode,
+                    hipStream_t user) {
+    residual_check(dB, ldb, dX, ldx, dR, ldr, nrhs);
+    HIP_OK(hipSetDevice(device));
+    resid_dev(dB, ldb, dX, ldx, dR, ldr, nrhs, mode < 0 ? resid_mode : mode, user);
+  }
+  DevBuf stage_r;
+  void residual_host(const T *B, int64_t ldb, const T *X, int64_t ldx, T *R, int64_t ldr, int64_t nrhs, int mode) {
+    residual_check(B, ldb, X, ldx, R, ldr, nrhs);
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t row = (size_t)nrhs * sizeof(T), need = (size_t)n * row;
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    if (stage_r.bytes < need) stage_r.alloc(need);
+    StreamWait wait{stream};
+    HIP_OK(hipMemcpy2DAsync(stage_b.p, row, B, ldb * sizeof(T), row, n, hipMemcpyHostToDevice, stream));
+    HIP_OK(hipMemcpy2DAsync(stage_x.p, row, X, ldx * sizeof(T), row, n, hipMemcpyHostToDevice, stream));
+    resid_dev((const D *)stage_b.as<D>(), nrhs, (const D *)stage_x.as<D>(), nrhs, stage_r.as<D>(), nrhs, nrhs,
+              mode < 0 ? resid_mode : mode);
+    HIP_OK(hipMemcpy2DAsync(R, ldr * sizeof(T), stage_r.p, row, row, n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
   }
 
   void vec_op(int op, int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const D *z, int64_t ldz) {
@@ -2874,7 +2927,7 @@ class Engine : public EngineBase {
       for (int i = 0; i < nirs; ++i) {
         vec_op(1, n, nrhs, xk, nrhs, dX, ldx, nullptr, 0);
         if (i)
-          resid_dev(dB, ldb, xk, nrhs, r, nrhs, nrhs);
+          resid_dev(dB, ldb, xk, nrhs, r, nrhs, nrhs, resid_mode);
         else
           vec_op(1, n, nrhs, r, nrhs, dB, ldb, nullptr, 0);
         // M.solve(x, _r): the reference solves into _r and then x = _r + _xk (:102-103)
@@ -2915,7 +2968,7 @@ class Engine : public EngineBase {
       nactive = 0;
       for (char a : active) nactive += a;
       if (!nactive) break;
-      resid_dev(dB, ldb, dX, ldx, r, nrhs, nrhs);  // r = b - A x
+      resid_dev(dB, ldb, dX, ldx, r, nrhs, nrhs, resid_mode);  // r = b - A x
       col_norms(r, nrhs, n, nrhs, rnorm);
       for (int64_t c = 0; c < nrhs; ++c) {
         if (!active[(size_t)c]) continue;
@@ -3123,7 +3176,7 @@ class Engine : public EngineBase {
     const int max_outer = (maxit + restart - 1) / restart;  // :43
     for (int outer = 0; outer < max_outer && gm_ctl_host[2] > 0; ++outer) {
       if (outer) {
-        resid_dev(dB, ldb, (const D *)dX, ldx, v, nc, nc);  // v = b - A x  (:48-50)
+        resid_dev(dB, ldb, (const D *)dX, ldx, v, nc, nc, resid_mode);  // v = b - A x  (:48-50)
         gm_step(n, nc, v, nullptr, nullptr, S);
       }  // (outer == 0: the partial sums of |b|^2 are still in place)
       gm_finish(nc, 2, 0, 0, S);                        // beta, y[0], active mask  (:53-54)
@@ -3196,6 +3249,124 @@ class Engine : public EngineBase {
     staged(B, ldb, X, ldx, nrhs, false, [] {}, [&](const D *b, D *x) {
       gmres_dev(b, nrhs, x, nrhs, nrhs, restart, rtol, maxit, rank, flags, iters, flexible, sweeps);
     });
+  }
+
+  // ---- GMRES-based iterative refinement (Carson and Higham's GMRES-IR), batched over columns -----------
+  // Refinement whose residual is formed as if in twice the working precision and whose correction equation A d = r is
+  // solved by right-preconditioned GMRES:
+  //   x = 0; bn = ||b||
+  //   outer k = 0, 1, ...: r = b - A x, compensated whatever the handle's mode (k = 0: r = b); res = ||r|| / bn
+  //     res <= rtol                       flag 0
+  //     k > 0 and res >= res of step k-1  flag 1 (stagnated): the column gets back the iterate of step k-1 (ir_xk)
+  //     k == max_outer                    flag 2
+  //     the frozen columns of r are zeroed; d = gmres_dev(r) (x0 = 0, inner_rtol relative to ||r||); x += d on the
+  //     active columns
+  // Per 64-column tile, the per-column bookkeeping on the host as in hifir_dev's bounded branch: one read-back (the
+  // column norms) per outer step.  A zero column: x = 0, flag 0, 0 steps; a column whose norm or residual is not finite:
+  // flag 1 at once.  The restart residuals of the inner GMRES follow the handle's mode.  No pool vector is held while
+  // gmres_dev runs (see kr_vec): r lives in ir_r, the previous iterate in ir_xk, the correction in gi_d.
+  DevBuf gi_d, gi_mask;
+  void launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask);
+  void gmres_ir_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, int restart, double rtol, double inner_rtol,
+                     int max_outer, int inner_maxit, int64_t rank, int *flags, int *outer, int *iters, double *relres) {
+    const int64_t n = lv[0]->n;
+    // The residual and the correction live in blocks of W columns whatever nc is, the columns behind nc zero: the
+    // reductions of GMRES and of the norms deal rows to threads by the block's width, so a fixed width is what makes a
+    // column's bits (x and relres) independent of the batch it came in.  W is the widest tile the handle takes.
+    const int W = (int)std::min<int64_t>(64, std::max<int64_t>(Rmax, max_nrhs));
+    const size_t vec = (size_t)n * W * sizeof(D);
+    if (ir_r.bytes < vec) ir_r.alloc(vec);
+    if (ir_xk.bytes < vec) ir_xk.alloc(vec);
+    if (gi_d.bytes < vec) gi_d.alloc(vec);
+    if (!gi_mask.p) gi_mask.alloc(64 * sizeof(int));
+    D *r = ir_r.as<D>(), *xk = ir_xk.as<D>(), *d = gi_d.as<D>();
+    StreamWait wait{stream};
+    const size_t w = (size_t)nc;
+    std::vector<double> bn, rn, res(w, 0.0), prev(w, 0.0);
+    std::vector<int> fl(w, 0), nout(w, 0), nit(w, 0), gfl((size_t)W), git((size_t)W), hmask(w);
+    std::vector<char> active(w, 1);
+    auto mask_of = [&](auto pred) {  // (a pageable source: the copy has read it when the call returns)
+      for (size_t c = 0; c < w; ++c) hmask[c] = pred(c) ? 1 : 0;
+      HIP_OK(hipMemcpyAsync(gi_mask.p, hmask.data(), w * sizeof(int), hipMemcpyHostToDevice, stream));
+    };
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
+    HIP_OK(hipMemsetAsync(r, 0, vec, stream));
+    vec_op(1, n, nc, r, W, dB, ldb, nullptr, 0);  // r = b
+    col_norms(r, W, n, W, bn);
+    for (size_t c = 0; c < w; ++c) {
+      if (bn[c] == 0.0) active[c] = 0;  // x = 0, flag 0, 0 steps
+      if (!std::isfinite(bn[c])) active[c] = 0, fl[c] = 1, res[c] = std::numeric_limits<double>::quiet_NaN();
+    }
+    rn = bn;
+    for (int k = 0;; ++k) {
+      int nactive = 0;
+      for (char a : active) nactive += a;
+      if (!nactive) break;
+      if (k > 0) {
+        resid_dev(dB, ldb, (const D *)dX, ldx, r, W, nc, 1);  // r = b - A x, compensated
+        col_norms(r, W, n, W, rn);
+      }
+      std::vector<char> back(w, 0);
+      int nback = 0;
+      for (size_t c = 0; c < w; ++c) {
+        if (!active[c]) continue;
+        const double rc = rn[c] / bn[c];
+        if (k > 0 && (!std::isfinite(rc) || rc >= prev[c])) {  // no better than the iterate before: that one is returned
+          fl[c] = 1, active[c] = 0, back[c] = 1, ++nback;
+          res[c] = prev[c], --nout[c];
+          continue;
+        }
+        res[c] = prev[c] = rc;
+        if (rc <= rtol)
+          active[c] = 0;
+        else if (k == max_outer)
+          fl[c] = 2, active[c] = 0;
+      }
+      if (nback) {
+        mask_of([&](size_t c) { return back[c] != 0; });
+        launch_masked_set(n, nc, dX, ldx, (const D *)xk, nc, gi_mask.as<int>());
+      }
+      nactive = 0;
+      for (char a : active) nactive += a;
+      if (!nactive) break;
+      mask_of([&](size_t c) { return !active[c]; });
+      launch_masked_set(n, nc, r, W, (const D *)nullptr, 0, gi_mask.as<int>());  // the frozen columns take no part
+      gmres_dev((const D *)r, W, d, W, W, restart, inner_rtol, inner_maxit, rank, gfl.data(), git.data());
+      vec_op(1, n, nc, xk, nc, (const D *)dX, ldx, nullptr, 0);  // the iterate of this step, should the next be no better
+      mask_of([&](size_t c) { return active[c] != 0; });
+      launch_masked_add(n, nc, dX, ldx, (const D *)d, W, gi_mask.as<int>());  // x += d on the active columns
+      HIP_OK(hipGetLastError());
+      for (size_t c = 0; c < w; ++c)
+        if (active[c]) ++nout[c], nit[c] += git[c];
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+    for (size_t c = 0; c < w; ++c) {
+      if (flags) flags[c] = fl[c];
+      if (outer) outer[c] = nout[c];
+      if (iters) iters[c] = nit[c];
+      if (relres) relres[c] = res[c];
+    }
+  }
+  void gmres_ir_check(int restart, double rtol, double inner_rtol, int max_outer, int inner_maxit) {
+    gmres_check(restart, inner_maxit, rtol);
+    if (!(inner_rtol > 0.0 && inner_rtol < 1.0) || max_outer < 1)
+      throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < inner_rtol < 1 and max_outer >= 1");
+  }
+  void gmres_ir_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int restart, double rtol, double inner_rtol,
+                    int max_outer, int inner_maxit, int64_t rank, int *flags, int *outer, int *iters, double *relres) {
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, outer, [&] { gmres_ir_check(restart, rtol, inner_rtol, max_outer, inner_maxit); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *ou) {
+                   gmres_ir_tile(b, ldb, x, ldx, nc, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, fl, ou, it,
+                                 relres ? relres + (b - dB) : nullptr);
+                 });
+  }
+  void gmres_ir_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int restart, double rtol, double inner_rtol,
+                     int max_outer, int inner_maxit, int64_t rank, int *flags, int *outer, int *iters, double *relres) {
+    staged(B, ldb, X, ldx, nrhs, false, [&] { gmres_ir_check(restart, rtol, inner_rtol, max_outer, inner_maxit); },
+           [&](const D *b, D *x) {
+             gmres_ir_dev(b, nrhs, x, nrhs, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres);
+           });
   }
 
   // ---- preconditioned CG, batched over columns ------------------------------------------------------
@@ -3587,6 +3758,26 @@ __global__ void __launch_bounds__(256) k_masked_add(int64_t n, int nrhs, D *y, i
   }
 }
 
+// where mask[c]: y[:, c] = x[:, c], or 0 when x is NULL
+template <class D>
+__global__ void __launch_bounds__(256) k_masked_set(int64_t n, int nrhs, D *y, int64_t ldy, const D *x, int64_t ldx,
+                                                    const int *mask) {
+  const int64_t total = n * nrhs;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e / nrhs;
+    const int c = (int)(e - i * nrhs);
+    if (mask[c]) y[i * ldy + c] = x ? x[i * ldx + c] : vzero(D());
+  }
+}
+
+template <class T>
+void Engine<T>::launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
+  int64_t g = (n * nrhs + 255) / 256;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL((k_masked_set<D>), dim3((unsigned)g), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
+}
+
 template <class T>
 void Engine<T>::launch_masked_add(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
   int64_t g = (n * nrhs + 255) / 256;
@@ -3920,6 +4111,15 @@ static E *nsp_engine(E *e, HifAmdOp op) {
   if (!e->finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
   if (op == HIFAMD_S) return e;
   return e->adj ? e->adj.get() : nullptr;
+}
+
+// what refuses a residual call before the adjoint engine would be built for it
+template <class E>
+static void residual_pre(E *e, HifAmdOp op, int mode) {
+  if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the residual belongs to HIFAMD_S (A) or HIFAMD_SH (A^H)");
+  if (mode < -1 || mode > HIFAMD_RESID_COMPENSATED) throw Error(HIFAMD_MISMATCHED_SIZES, "residual mode: -1, 0 or 1");
+  if (!e->finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+  if (!e->has_A) throw Error(HIFAMD_BAD_PREC, "the residual needs the matrix (hifamd_set_matrix)");
 }
 
 extern "C" {
@@ -4340,6 +4540,55 @@ HifAmdStatus hifamd_gmres_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, vo
   API_BEGIN
   DISPATCH(ENG_D->gmres_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, restart, rtol, maxit, rank, flags, iters),
            ENG_Z->gmres_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, restart, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_set_residual_precision(HifAmdHdl h, int mode) {
+  API_BEGIN
+  if (mode != HIFAMD_RESID_WORKING && mode != HIFAMD_RESID_COMPENSATED)
+    throw Error(HIFAMD_MISMATCHED_SIZES, "residual precision: HIFAMD_RESID_WORKING or HIFAMD_RESID_COMPENSATED");
+  DISPATCH(ENG_D->set_resid_mode(mode), ENG_Z->set_resid_mode(mode))
+  API_END
+}
+
+int hifamd_residual_precision(HifAmdHdl h) {
+  if (!h || !h->eng) return -1;
+  return h->vt == HIFAMD_D ? ENG_D->resid_mode : ENG_Z->resid_mode;
+}
+
+HifAmdStatus hifamd_residual_batch(HifAmdHdl h, HifAmdOp op, const void *B, int64_t ldb, const void *X, int64_t ldx, void *R,
+                                   int64_t ldr, int64_t nrhs, int mode) {
+  API_BEGIN
+  DISPATCH(residual_pre(ENG_D, op, mode), residual_pre(ENG_Z, op, mode))
+  DISPATCH(ENG_D->for_op(op).residual_host((const double *)B, ldb, (const double *)X, ldx, (double *)R, ldr, nrhs, mode),
+           ENG_Z->for_op(op).residual_host((const zdouble *)B, ldb, (const zdouble *)X, ldx, (zdouble *)R, ldr, nrhs, mode))
+  API_END
+}
+
+HifAmdStatus hifamd_residual_batch_dev(HifAmdHdl h, HifAmdOp op, const void *dB, int64_t ldb, const void *dX, int64_t ldx,
+                                       void *dR, int64_t ldr, int64_t nrhs, int mode, void *stream) {
+  API_BEGIN
+  DISPATCH(residual_pre(ENG_D, op, mode), residual_pre(ENG_Z, op, mode))
+  DISPATCH(ENG_D->for_op(op).residual_dev((const double *)dB, ldb, (const double *)dX, ldx, (double *)dR, ldr, nrhs, mode, (hipStream_t)stream),
+           ENG_Z->for_op(op).residual_dev((const cplx *)dB, ldb, (const cplx *)dX, ldx, (cplx *)dR, ldr, nrhs, mode, (hipStream_t)stream))
+  API_END
+}
+
+HifAmdStatus hifamd_gmres_ir_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int restart,
+                                   double rtol, double inner_rtol, int max_outer, int inner_maxit, int64_t rank, int *flags,
+                                   int *outer, int *iters, double *relres) {
+  API_BEGIN
+  DISPATCH(ENG_D->gmres_ir_host((const double *)B, ldb, (double *)X, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres),
+           ENG_Z->gmres_ir_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres))
+  API_END
+}
+
+HifAmdStatus hifamd_gmres_ir_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                       int restart, double rtol, double inner_rtol, int max_outer, int inner_maxit,
+                                       int64_t rank, int *flags, int *outer, int *iters, double *relres) {
+  API_BEGIN
+  DISPATCH(ENG_D->gmres_ir_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres),
+           ENG_Z->gmres_ir_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres))
   API_END
 }
 

@@ -89,6 +89,13 @@ HostLevel<T> import_level(int64_t parent_nm, int64_t m, int64_t n, const int64_t
   return H;
 }
 
+// The residual mode a handle starts with (hifamd_set_residual_precision changes it): HIFIR_AMD_RESIDUAL = 1 asks for the
+// compensated residual, anything else is working precision.  How callers of the drop-in shim reach the mode.
+inline int resid_mode_from_env() {
+  const char *e = std::getenv("HIFIR_AMD_RESIDUAL");
+  return e && std::atoi(e) == 1 ? 1 : 0;
+}
+
 // two independent pieces of host work side by side (an exception of either is rethrown after both have finished)
 template <class FA, class FB>
 void par2(FA &&fa, FB &&fb) {

@@ -1406,6 +1406,102 @@ __global__ void __launch_bounds__(256) k_crs_spmm(int64_t nrows, const int32_t *
 }
 
 // ---------------------------------------------------------------------------------------------
+// compensated residual r = b - A x: every row's sum carried as an unevaluated pair (s, c), as if in twice the
+// working precision (Dot2 of Ogita, Rump and Oishi with b_i as the first term).  Per row and column, in CRS order:
+//   s = b_i; c = 0
+//   per nonzero: p = (-a) x; e = fma(-a, x, -p)                          (TwoProd)
+//                t = s + p; z = t - s; q = (s - (t - z)) + (p - z)       (TwoSum)
+//                s = t; c = c + (q + e)
+//   r_i = s + c
+// A complex sum is two independent real sums of this form, started from Re b and Im b; per nonzero the real part takes
+// (-ar xr) then (+ai xi), the imaginary part (-ar xi) then (-ai xr).  The order is fixed: a host restatement matches
+// bit for bit.  One chain per sum -- a second accumulator would change the bits.  -ffp-contract=off keeps TwoSum as
+// written; the fused multiply-add is explicit.  Launch shape and lane map of k_crs_spmm.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dd_step(double &s, double &c, double a, double x) {
+  const double p = a * x;
+  const double e = __builtin_fma(a, x, -p);
+  const double t = s + p;
+  const double z = t - s;
+  const double q = (s - (t - z)) + (p - z);
+  s = t;
+  c = c + (q + e);
+}
+struct DdAcc {
+  double s, c;
+};
+struct DdAccZ {
+  double sr, cr, si, ci;
+};
+__device__ __forceinline__ DdAcc dd_init(double b) { return DdAcc{b, 0.0}; }
+__device__ __forceinline__ DdAccZ dd_init(cplx b) { return DdAccZ{b.x, 0.0, b.y, 0.0}; }
+__device__ __forceinline__ void dd_sub(DdAcc &r, double a, double x) { dd_step(r.s, r.c, -a, x); }
+__device__ __forceinline__ void dd_sub(DdAccZ &r, cplx a, cplx x) {
+  dd_step(r.sr, r.cr, -a.x, x.x);
+  dd_step(r.sr, r.cr, a.y, x.y);
+  dd_step(r.si, r.ci, -a.x, x.y);
+  dd_step(r.si, r.ci, -a.y, x.x);
+}
+__device__ __forceinline__ double dd_value(const DdAcc &r) { return r.s + r.c; }
+__device__ __forceinline__ cplx dd_value(const DdAccZ &r) { return cplx{r.sr + r.cr, r.si + r.ci}; }
+
+// AH >= 2 slots hold the nonzeros k .. k + AH - 1 (coefficient and x entry) and the column indices of the next AH; a
+// slot is requested again right behind its sum, so a request has the AH - 1 sums of the other slots to land in (asked
+// for IN FRONT of the sum, the old value is still live, the new one gets a register of its own and the copy at the
+// back edge waits for every load).  Full trips in a loop with one exit, the remainder behind it from the slots; every
+// load is unconditional (clamped to the row's last nonzero), and the values requested in front of the loop
+// are touched there (pin_here), or the compiler folds each request into a load in front of its use.
+// Timing only: every AH gives the same bits.
+template <class T, int AH>
+__global__ void __launch_bounds__(256) k_crs_resid_dd(int64_t nrows, const int32_t *__restrict__ ptr,
+                                                      const int32_t *__restrict__ col,
+                                                      const T *__restrict__ val, const T *__restrict__ x,
+                                                      int64_t ldx, const T *__restrict__ b, int64_t ldb,
+                                                      T *__restrict__ y, int64_t ldy, int nrhs, int logR) {
+  const LaneMap lm = lane_map(logR);
+  const int cc = min(lm.c, nrhs - 1);  // a lane beyond the batch reads its last column and stores nothing
+  const uint32_t *__restrict__ ucol = (const uint32_t *)col;  // (never negative: widened by zero)
+  const int64_t wave = ((int64_t)xcd_block() * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t i = wave * lm.G + lm.g; i < nrows; i += nwaves * lm.G) {
+    const int32_t k0 = ptr[i], k1 = ptr[i + 1];
+    auto acc = dd_init(b[i * ldb + cc]);
+    if (k0 < k1) {
+      const int32_t kl = k1 - 1;
+      T a[AH], xv[AH];
+      uint32_t j[AH];
+#pragma unroll
+      for (int q = 0; q < AH; ++q) {
+        j[q] = ucol[min(k0 + AH + q, kl)];
+        a[q] = val[min(k0 + q, kl)];
+        xv[q] = x[(int64_t)ucol[min(k0 + q, kl)] * ldx + cc];
+      }
+#pragma unroll
+      for (int q = 0; q < AH; ++q) {
+        pin_here(j[q]);
+        pin_here(a[q]);
+        pin_here(xv[q]);
+      }
+      int32_t k = k0;
+      for (; k + AH <= k1; k += AH) {  // full trips; a slot is requested again right behind its sum
+#pragma unroll
+        for (int q = 0; q < AH; ++q) {
+          dd_sub(acc, a[q], xv[q]);
+          const uint32_t jc = j[q];
+          j[q] = ucol[min(k + q + 2 * AH, kl)];
+          a[q] = val[min(k + q + AH, kl)];
+          xv[q] = x[(int64_t)jc * ldx + cc];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < AH - 1; ++q)  // the remainder sits in the slots already
+        if (k + q < k1) dd_sub(acc, a[q], xv[q]);
+    }
+    if (lm.c < nrhs) y[i * ldy + lm.c] = dd_value(acc);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // prec_prod (y = M b, alg/prec_prod.hpp:55-147): the inverse direction of the apply.  No dependent steps
 // except the one LDU solve of the Schur coupling term, so these are plain row-gather kernels.
 // ---------------------------------------------------------------------------------------------

@@ -25,7 +25,8 @@ STATUS = {0: "HIFAMD_SUCCESS", 1: "HIFAMD_NULL_OBJ", 2: "HIFAMD_MISMATCHED_SIZES
 
 
 OP_S, OP_SH, OP_M, OP_MH = 0, 1, 2, 3  # HifAmdOp == LhfOperationType (libhifir.h:159-164)
-ZOP_TAIL, ZOP_TOP = 1, 2  # HIFAMD_ZOP_*: explicit operators a complex handle forms on request (hifamd_set_complex_operators)
+RESID_WORKING, RESID_COMPENSATED = 0, 1  # HIFAMD_RESID_*: how b - A x is formed (hifamd_set_residual_precision)
+ZOP_TAIL, ZOP_TOP = 1, 2  #HIFAMD_ZOP_*: explicit operators a complex handle forms on request (hifamd_set_complex_operators)
 
 
 class HifAmdError(RuntimeError):
@@ -581,6 +582,72 @@ class HIF:
         all columns of b ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.
         Returns (x, flags, iters); ints for a vector."""
         return self._krylov("gmres", b, int(restart), rtol=rtol, maxit=maxit, full_rank=full_rank)
+
+    # ---- extra-precise residuals ---------------------------------------------------------------------
+    def set_residual_precision(self, mode):
+        """How hifir / gmres / fgmres form b - A x (hifamd_set_residual_precision): RESID_WORKING (0) in working
+        precision, RESID_COMPENSATED (1) as if in twice the working precision.  The default comes from
+        HIFIR_AMD_RESIDUAL when the handle is created."""
+        _check(lib().hifamd_set_residual_precision(self._h, int(mode)))
+
+    def residual_precision(self):
+        """The residual mode in force (hifamd_residual_precision)."""
+        m = lib().hifamd_residual_precision(self._h)
+        if m < 0:
+            _check(1)
+        return m
+
+    def residual(self, B, X, trans=False, precise=None):
+        """R = B - A X (trans: B - A^H X) on the device (hifamd_residual_batch / _dev).  B, X: [n] or [n][nrhs], both host
+        arrays or both CUDA tensors (not synchronized).  precise: True compensated, False working precision, None the
+        handle's mode."""
+        op = OP_SH if trans else OP_S
+        mode = -1 if precise is None else (1 if precise else 0)
+        vec = (B.ndim == 1)
+        if _is_torch(B) != _is_torch(X):
+            raise HifAmdError(2, "residual: B and X must both be host arrays or both CUDA tensors")
+        if _is_torch(B):
+            import torch
+
+            B2 = self._dev_block(B.reshape(B.shape[0], -1), "B")
+            X2 = self._dev_block(X.reshape(X.shape[0], -1), "X", B2.shape)
+            R = torch.empty((B2.shape[0], B2.shape[1]), dtype=B2.dtype, device=B2.device)
+            _check(lib().hifamd_residual_batch_dev(self._h, op, B2.data_ptr(), B2.stride(0), X2.data_ptr(), X2.stride(0),
+                                                  R.data_ptr(), R.stride(0), B2.shape[1], mode, None))
+        else:
+            B2 = np.ascontiguousarray(B, dtype=self.dtype).reshape(B.shape[0], -1)
+            X2 = np.ascontiguousarray(X, dtype=self.dtype).reshape(X.shape[0], -1)
+            if B2.shape[0] != self.nrows() or X2.shape != B2.shape:
+                raise HifAmdError(2, "unmatched sizes")
+            R = np.empty_like(B2)
+            _check(lib().hifamd_residual_batch(self._h, op, _p(B2), B2.shape[1], _p(X2), X2.shape[1], _p(R), R.shape[1],
+                                              B2.shape[1], mode))
+        return R.reshape(-1) if vec else R
+
+    def gmres_ir(self, b, restart=30, rtol=1e-14, inner_rtol=1e-6, max_outer=10, inner_maxit=500, full_rank=False):
+        """GMRES-based iterative refinement (hifamd_gmres_ir_batch / _dev): outer residuals always compensated, every
+        correction A d = r by right-preconditioned GMRES to inner_rtol.  b: [n] or [n][nrhs], host array or CUDA tensor.
+        Returns (x, flags, outer, iters, relres) per column (scalars for a vector): flags 0 converged / 1 stagnated (x is
+        the better of the last two iterates) / 2 reached max_outer; outer = corrections in x; iters = inner GMRES
+        iterations; relres = the compensated ||b - A x|| / ||b|| of the returned x."""
+        vec = (b.ndim == 1)
+        if _is_torch(b):
+            import torch
+
+            B = self._dev_block(b.reshape(b.shape[0], -1), "b")
+            X = torch.empty_like(B)
+            fn, io = lib().hifamd_gmres_ir_batch_dev, (B.data_ptr(), B.stride(0), X.data_ptr(), X.stride(0))
+        else:
+            B = np.ascontiguousarray(b, dtype=self.dtype).reshape(b.shape[0], -1)
+            X = np.empty_like(B)
+            fn, io = lib().hifamd_gmres_ir_batch, (_p(B), B.shape[1], _p(X), X.shape[1])
+        fl, ou, it = (np.zeros(B.shape[1], dtype=np.int32) for _ in range(3))
+        rr = np.zeros(B.shape[1])
+        _check(fn(self._h, *io, B.shape[1], int(restart), float(rtol), float(inner_rtol), int(max_outer), int(inner_maxit),
+                  -1 if full_rank else 0, _p(fl), _p(ou), _p(it), _p(rr)))
+        if vec:
+            return X.reshape(-1), int(fl[0]), int(ou[0]), int(it[0]), float(rr[0])
+        return X, fl, ou, it, rr
 
     def is_hermitian(self):
         """True when M^{-1} of the imported hierarchy is Hermitian (hifamd_hermitian: exact test on the host copy, every

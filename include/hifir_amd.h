@@ -349,6 +349,59 @@ HifAmdStatus hifamd_fgmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *
                                  int restart, double rtol, int maxit, int64_t rank, int *flags, int *iters,
                                  int *sweeps);
 
+/* ---- extra-precise residuals: compensated b - A x, refinement and GMRES-IR -------------------- */
+/* How the handle's drivers form r = b - A x.  HIFAMD_RESID_WORKING (the default): tmp = 0; tmp += a x; r = b - tmp in
+ * working precision, rounding error about eps sum |a||x| per row.  HIFAMD_RESID_COMPENSATED: every row's sum is carried
+ * as an unevaluated pair, as if in twice the working precision (TwoProd by fused multiply-add, TwoSum; Dot2 of Ogita,
+ * Rump and Oishi with b_i as the first term), error eps |r| + gamma^2 (|b| + sum |a||x|): what lets refinement reach a
+ * forward error of eps instead of cond(A) eps.  x, the applies and the Krylov kernels stay in working precision.  The
+ * operations per row and column, in CRS order:
+ *   s = b_i; c = 0; per nonzero: p = (-a) x; e = fma(-a, x, -p); t = s + p; z = t - s; q = (s - (t - z)) + (p - z);
+ *   s = t; c = c + (q + e); finally r_i = s + c.
+ * Complex: two independent real sums started from Re b and Im b; per nonzero the real part takes (-ar xr) then (+ai xi),
+ * the imaginary part (-ar xi) then (-ai xr).  A column's bits depend neither on the batch width nor on its neighbours.
+ * The mode is followed by both branches of hifamd_hifir_batch and hifamd_apply_batch (HIFAMD_S and HIFAMD_SH: the
+ * adjoint engine holds A^H as a CRS of its own), by the restart residuals of GMRES / FGMRES and by FGMRES's inner
+ * refinement; the null-space search always works in working precision.  The default is read from HIFIR_AMD_RESIDUAL
+ * (0 / 1) when the handle is created.  Finalized or not; a mode outside 0..1: HIFAMD_MISMATCHED_SIZES. */
+#define HIFAMD_RESID_WORKING 0
+#define HIFAMD_RESID_COMPENSATED 1
+HifAmdStatus hifamd_set_residual_precision(HifAmdHdl h, int mode);
+/* the mode in force; -1 for a NULL handle */
+int hifamd_residual_precision(HifAmdHdl h);
+/* R = B - A X (op = HIFAMD_S) or B - A^H X (op = HIFAMD_SH, the adjoint engine, built on first use as for
+ * hifamd_apply_batch) on [n][nrhs] blocks with row strides ldb, ldx, ldr; mode HIFAMD_RESID_WORKING /
+ * HIFAMD_RESID_COMPENSATED, or -1 for the handle's.  Needs hifamd_set_matrix; any width (64 columns per launch).
+ * Refusals, in this order: NULL handle HIFAMD_NULL_OBJ; another op, a mode outside -1..1 HIFAMD_MISMATCHED_SIZES; handle
+ * not finalized or no matrix HIFAMD_BAD_PREC; a NULL block HIFAMD_NULL_OBJ; nrhs < 1 or a row stride below nrhs
+ * HIFAMD_MISMATCHED_SIZES; R aliasing B or X HIFAMD_BAD_PREC.  Host pointers (returns when done) / device pointers,
+ * enqueued on `stream` (NULL = the handle's own) and not synchronized. */
+HifAmdStatus hifamd_residual_batch(HifAmdHdl h, HifAmdOp op, const void *B, int64_t ldb, const void *X, int64_t ldx,
+                                   void *R, int64_t ldr, int64_t nrhs, int mode);
+HifAmdStatus hifamd_residual_batch_dev(HifAmdHdl h, HifAmdOp op, const void *dB, int64_t ldb, const void *dX, int64_t ldx,
+                                       void *dR, int64_t ldr, int64_t nrhs, int mode, void *stream);
+/* GMRES-based iterative refinement (Carson and Higham's GMRES-IR) for nrhs columns, 64 in lock step: x = 0; per outer
+ * step k = 0, 1, ...: r = b - A x, ALWAYS compensated (k = 0: r = b); res = ||r|| / ||b||; res <= rtol: flag 0;
+ * k > 0 and res not below the step before: flag 1 (stagnated), the column gets back the iterate of the step before;
+ * k == max_outer: flag 2; otherwise d = hifamd_gmres_batch_dev on A d = r (x0 = 0, restart, inner_rtol relative to
+ * ||r||, inner_maxit, rank; its restart residuals follow the handle's mode) and x += d.  A column that has stopped is
+ * frozen: its later bits do not depend on its neighbours.  The residual and the correction are kept in blocks as wide as
+ * the widest tile the handle takes (64 columns, or the max_nrhs of hifamd_finalize where the arena is narrower), so a
+ * column's x and relres do not depend on the width of the batch either -- and a narrow batch costs the memory and the
+ * vector passes of a full tile.  A zero column: x = 0, flag 0, 0 steps; a column whose norm or
+ * residual is not finite: flag 1 at once.  Per column (each array may be NULL): flags[c]; outer[c] = corrections that
+ * the returned x contains; iters[c] = inner GMRES iterations spent; relres[c] = the compensated ||r|| / ||b|| of the
+ * returned x, a certificate that holds below 1e-13 where a working-precision residual is noise.  Refusals as for
+ * hifamd_gmres_batch (inner_maxit for maxit), plus inner_rtol outside (0, 1) or max_outer < 1
+ * HIFAMD_MISMATCHED_SIZES.  Host pointers; the _dev variant takes device pointers for B, X (the other arrays stay
+ * host arrays) and returns when the solve is done. */
+HifAmdStatus hifamd_gmres_ir_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
+                                   int restart, double rtol, double inner_rtol, int max_outer, int inner_maxit,
+                                   int64_t rank, int *flags, int *outer, int *iters, double *relres);
+HifAmdStatus hifamd_gmres_ir_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
+                                       int restart, double rtol, double inner_rtol, int max_outer, int inner_maxit,
+                                       int64_t rank, int *flags, int *outer, int *iters, double *relres);
+
 /* ---- preconditioned CG for a Hermitian positive-definite pair (A, M), batched --------------- */
 /* 1 when M^{-1} of the imported hierarchy is Hermitian, 0 when not, -1 for a NULL handle.  Exact test on the host
  * copy, every sparse level: U_B == L_B^H (same pattern, equal values), F == E^H (F absent only if E is empty),

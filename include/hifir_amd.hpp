@@ -267,6 +267,36 @@ class HIF {
     return std::make_tuple(std::move(x), flag, iters);
   }
 
+  // ---- extra-precise residuals (hifamd_set_residual_precision, hifamd_residual_batch, hifamd_gmres_ir_batch) ----
+  // HIFAMD_RESID_COMPENSATED: hifir and the restart residuals of gmres form b - A x as if in twice the working precision.
+  void set_residual_precision(const int mode) {
+    require();
+    detail::check(hifamd_set_residual_precision(_h, mode));
+  }
+  int residual_precision() const { return _h ? hifamd_residual_precision(_h) : -1; }
+  /// r = b - A x (trans: b - A^H x); mode HIFAMD_RESID_WORKING / HIFAMD_RESID_COMPENSATED, -1: the handle's
+  template <class Matrix, class RhsType, class SolType, class ResType>
+  void residual(const Matrix &A, const RhsType &b, const SolType &x, ResType &r, const bool trans = false, const int mode = -1) {
+    ensure_matrix(A);
+    if (b.size() != x.size() || b.size() != r.size()) throw std::runtime_error("hifir_amd: unmatched sizes");
+    detail::check(hifamd_residual_batch(_h, trans ? HIFAMD_SH : HIFAMD_S, b.data(), 1, x.data(), 1, r.data(), 1, 1, mode));
+  }
+  /// GMRES-based iterative refinement: (x, flag, corrections in x, inner GMRES iterations, compensated ||b - A x|| / ||b||);
+  /// flag 0 converged, 1 stagnated, 2 reached max_outer
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, int, int, int, double> gmres_ir(const Matrix &A, const ArrayType &b, const int restart = 30,
+                                                        const double rtol = 1e-14, const double inner_rtol = 1e-6,
+                                                        const int max_outer = 10, const int inner_maxit = 500,
+                                                        const bool full_rank = false) {
+    ensure_matrix(A);
+    ArrayType x(b.size());
+    int flag = 0, outer = 0, iters = 0;
+    double relres = 0.0;
+    detail::check(hifamd_gmres_ir_batch(_h, b.data(), 1, x.data(), 1, 1, restart, rtol, inner_rtol, max_outer, inner_maxit,
+                                        full_rank ? -1 : 0, &flag, &outer, &iters, &relres));
+    return std::make_tuple(std::move(x), flag, outer, iters, relres);
+  }
+
   // ---- preconditioned CG for a Hermitian positive-definite pair (A, M) on the device (hifamd_pcg_batch) ----
   // Needs an is_symm hierarchy: is_hermitian(); flag 0 converged, 1 breakdown, 2 reached maxit.
   template <class Matrix, class ArrayType>
