@@ -75,6 +75,8 @@ SIGNATURES = {
     "hifamd_pcg_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_bicgstab_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_bicgstab_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
+    "hifamd_idrs_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, C.c_uint64, _dbl, _int, _i64, _vp, _vp]),
+    "hifamd_idrs_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, C.c_uint64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_sqmr_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_sqmr_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_time_apply": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _int, _int, _vp]),

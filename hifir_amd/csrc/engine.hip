@@ -2998,12 +2998,12 @@ class Engine : public EngineBase {
   }
 
   // ---- what the lock-step Krylov solvers share -------------------------------------------------------
-  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG 4, BiCGSTAB 5, symmetric QMR 7),
-  // each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
+  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG 4, BiCGSTAB 5, symmetric QMR 7,
+  // IDR(s) 2 s + 4), each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
   // That holds because no solver runs inside another one's tile: the null-space search calls gmres_dev between its own
   // local blocks, flexible GMRES calls the refinement (ir_r, ir_xk) and the projected PCG / QMR call apply_nsp
   // (nsp_cpart, nsp_C); none of these takes a pool vector.  Keep it so when adding a solver.
-  DevBuf kr_vec[7];
+  DevBuf kr_vec[2 * kIdrMax + 4];
   void krylov_vectors(int k, size_t bytes) {
     for (int i = 0; i < k; ++i)
       if (kr_vec[i].bytes < bytes) kr_vec[i].alloc(bytes);
@@ -3015,14 +3015,23 @@ class Engine : public EngineBase {
   DevBuf kr_state;
   int *kr_pin = nullptr;
   void krylov_state(KrylovState &S, std::initializer_list<D **> ds, std::initializer_list<double **> rs, double rtol, int maxit) {
-    const size_t o_re = ds.size() * 64 * sizeof(D), o_int = o_re + rs.size() * 64 * sizeof(double),
+    std::vector<std::pair<D **, int>> rows;
+    for (D **slot : ds) rows.push_back({slot, 1});
+    krylov_state(S, rows, rs, rtol, maxit);
+  }
+  // (the same with slots of several [64] rows each: IDR(s) keeps an s x s matrix per column)
+  void krylov_state(KrylovState &S, const std::vector<std::pair<D **, int>> &ds, std::initializer_list<double **> rs, double rtol,
+                    int maxit) {
+    size_t nd = 0;
+    for (const auto &slot : ds) nd += (size_t)slot.second;
+    const size_t o_re = nd * 64 * sizeof(D), o_int = o_re + rs.size() * 64 * sizeof(double),
                  bytes = o_int + (3 * 64 + 4) * sizeof(int);
     if (!kr_pin) HIP_OK(hipHostMalloc((void **)&kr_pin, 129 * sizeof(int), hipHostMallocDefault));
     if (kr_state.bytes < bytes) kr_state.alloc(bytes);
     HIP_OK(hipMemsetAsync(kr_state.p, 0, bytes, stream));
     char *b = kr_state.as<char>();
     D *d = (D *)b;
-    for (D **slot : ds) *slot = d, d += 64;
+    for (const auto &slot : ds) *slot.first = d, d += 64 * (size_t)slot.second;
     double *r = (double *)(b + o_re);
     for (double **slot : rs) *slot = r, r += 64;
     int *ib = (int *)(b + o_int);
@@ -3504,6 +3513,181 @@ class Engine : public EngineBase {
                      int *flags, int *iters) {
     staged(B, ldb, X, ldx, nrhs, false, [&] { krylov_check("BiCGSTAB", maxit, rtol); },
            [&](const D *b, D *x) { bicgstab_dev(b, nrhs, x, nrhs, nrhs, rtol, maxit, rank, flags, iters); });
+  }
+
+  // ---- right-preconditioned IDR(s) with biorthogonalization, batched over columns --------------------
+  // van Gijzen / Sonneveld (ACM TOMS 38(1), 2011) with the "maintaining convergence" omega (kappa = 0.7), x0 = 0:
+  //   r = b; G = U = 0; M = I; omega = 1
+  //   cycle: f = P^H r; for k = 0 .. s-1: c = forward substitution on M[k:, k:] c = f[k:]; v = r - sum_{i>=k} c_i g_i;
+  //     v^ = M^{-1} v; u = omega v^ + sum_{i>=k} c_i u_i; g = A u (a step); raw = P^H g (one pass);
+  //     alpha, the new column of M and beta from raw and the stored M (k_idr_finish mode 2: no second pass over G);
+  //     g_k = g - sum_{l<k} alpha_l g_l; u_k likewise; r -= beta g_k; x += beta u_k; test;
+  //   v^ = M^{-1} r; t = A v^ (a step); omega from (t, r), (t, t); r -= omega t; x += omega v^; test.
+  // Up to 64 columns in lock step sharing k, per-column scalars in HBM (IdState), work vectors r, v, v^, t, G_0 .., U_0 ..
+  // (2 s + 4 of the pool; u is built in U_k and g = A u lands in G_k, so neither needs a vector of its own).  The shadow
+  // block P [n][K] (K = s padded to 1, 2, 4, 8) is shared by all columns and tiles of a call.  The host reads the
+  // active count once per step, after the stopping test.  Every apply goes through solve_dev, so a null-space filter on
+  // HIFAMD_S filters it.  Flags 0 converged / 1 breakdown / 2 reached maxit.
+  DevBuf id_P, id_cpart, id_C;  // P, the block partials of P^H x [K][kCgBlocks][64], P^H x [K][64]
+  int id_K = 0;
+
+  void idrs_check(int s, const T *P, int64_t ldp, int maxit, double rtol) {
+    krylov_check("IDR(s)", maxit, rtol);
+    if (s < 1 || s > HIFAMD_IDRS_MAX) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= s <= HIFAMD_IDRS_MAX");
+    if (P && ldp < s) throw Error(HIFAMD_MISMATCHED_SIZES, "row stride of the shadow block smaller than s");
+    if (P) {
+      const int64_t n = lv[0]->n;
+      for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < s; ++j)
+          if (!std::isfinite(abs1_(P[i * ldp + j]))) throw Error(HIFAMD_BAD_PREC, "the shadow block has a non-finite entry");
+    }
+  }
+  // P as [n][K] on the device: the caller's block as it is (host pointer), or the generated one
+  void idrs_shadow(int s, const T *P, int64_t ldp, uint64_t seed) {
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const int K = (int)nsp_padded(s);
+    if (P) {
+      std::vector<T> h((size_t)n * K, T(0));
+      for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < s; ++j) h[(size_t)(i * K + j)] = P[i * ldp + j];
+      id_P.upload(h);
+    } else {
+      if (id_P.bytes < (size_t)n * K * sizeof(T)) id_P.alloc((size_t)n * K * sizeof(T));
+      hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * K)), dim3(256), 0, stream, n, s, K, seed, id_P.as<D>());
+      HIP_OK(hipGetLastError());
+    }
+    if (id_cpart.bytes < (size_t)K * kCgBlocks * 64 * sizeof(T)) id_cpart.alloc((size_t)K * kCgBlocks * 64 * sizeof(T));
+    if (id_C.bytes < (size_t)K * 64 * sizeof(T)) id_C.alloc((size_t)K * 64 * sizeof(T));
+    id_K = K;
+  }
+  // id_C = P^H x, x [n][nc] contiguous
+  template <int K>
+  void idr_coef_k(const D *x, int nc) {
+    hipLaunchKernelGGL((k_nsp_coef<D, K>), dim3(kCgBlocks), dim3(256), 0, stream, lv[0]->n, nc, x, (int64_t)nc,
+                       (const D *)id_P.as<D>(), id_cpart.as<D>());
+    hipLaunchKernelGGL((k_nsp_finish<D>), dim3(K), dim3(1024), 0, stream, (const D *)id_cpart.as<D>(), id_C.as<D>());
+  }
+  void idr_coef(const D *x, int nc) {
+    switch (id_K) {
+      case 1: idr_coef_k<1>(x, nc); break;
+      case 2: idr_coef_k<2>(x, nc); break;
+      case 4: idr_coef_k<4>(x, nc); break;
+      default: idr_coef_k<8>(x, nc); break;
+    }
+  }
+  template <int S, bool U>
+  void idr_comb_s(int nc, D *y, const D *z, D *const *W, const D *coef, const D *omega) {
+    IdRun<D, S> run;
+    for (int j = 0; j < S; ++j) run.w[j] = W[j];
+    hipLaunchKernelGGL((k_idr_comb<D, S, U>), dim3(kCgBlocks), dim3(256), 0, stream, lv[0]->n, nc, y, z, run, coef, omega);
+  }
+  template <bool U>
+  void idr_comb(int m, int nc, D *y, const D *z, D *const *W, const D *coef, const D *omega) {
+    switch (m) {
+      case 1: idr_comb_s<1, U>(nc, y, z, W, coef, omega); break;
+      case 2: idr_comb_s<2, U>(nc, y, z, W, coef, omega); break;
+      case 3: idr_comb_s<3, U>(nc, y, z, W, coef, omega); break;
+      case 4: idr_comb_s<4, U>(nc, y, z, W, coef, omega); break;
+      case 5: idr_comb_s<5, U>(nc, y, z, W, coef, omega); break;
+      case 6: idr_comb_s<6, U>(nc, y, z, W, coef, omega); break;
+      case 7: idr_comb_s<7, U>(nc, y, z, W, coef, omega); break;
+      default: idr_comb_s<8, U>(nc, y, z, W, coef, omega); break;
+    }
+  }
+  template <int S>
+  void idr_gu_s(int nc, D *x, int64_t ldx, D *r, D *const *G, D *const *U, const IdState<D> &St, D *pt) {
+    IdRun<D, S> g, u;
+    for (int l = 0; l < S; ++l) g.w[l] = G[l], u.w[l] = U[l];
+    hipLaunchKernelGGL((k_idr_gu<D, S>), dim3(kCgBlocks), dim3(256), 0, stream, lv[0]->n, nc, x, ldx, r, G[S], U[S], g, u, St, pt);
+  }
+  void idr_gu(int k, int nc, D *x, int64_t ldx, D *r, D *const *G, D *const *U, const IdState<D> &St, D *pt) {
+    switch (k) {
+      case 0: idr_gu_s<0>(nc, x, ldx, r, G, U, St, pt); break;
+      case 1: idr_gu_s<1>(nc, x, ldx, r, G, U, St, pt); break;
+      case 2: idr_gu_s<2>(nc, x, ldx, r, G, U, St, pt); break;
+      case 3: idr_gu_s<3>(nc, x, ldx, r, G, U, St, pt); break;
+      case 4: idr_gu_s<4>(nc, x, ldx, r, G, U, St, pt); break;
+      case 5: idr_gu_s<5>(nc, x, ldx, r, G, U, St, pt); break;
+      case 6: idr_gu_s<6>(nc, x, ldx, r, G, U, St, pt); break;
+      default: idr_gu_s<7>(nc, x, ldx, r, G, U, St, pt); break;
+    }
+  }
+
+  void idrs_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, int s, double rtol, int maxit, int64_t rank,
+                 int *flags, int *iters) {
+    const int64_t n = lv[0]->n;
+    const size_t vec = (size_t)n * nc * sizeof(D), part = (size_t)kCgBlocks * 64 * sizeof(D);
+    krylov_vectors(2 * s + 4, vec);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    if (bs_part2.bytes < part) bs_part2.alloc(part);
+    D *r = kr_vec[0].as<D>(), *v = kr_vec[1].as<D>(), *vh = kr_vec[2].as<D>(), *t = kr_vec[3].as<D>();
+    D *G[kIdrMax], *U[kIdrMax];
+    for (int i = 0; i < s; ++i) G[i] = kr_vec[4 + i].as<D>(), U[i] = kr_vec[4 + s + i].as<D>();
+    D *pt = ir_part.as<D>(), *pt2 = bs_part2.as<D>();
+    const D *C = id_C.as<D>();
+    StreamWait wait{stream};
+    IdState<D> S;
+    S.s = s;
+    krylov_state(S, {{&S.M, s * s}, {&S.f, s}, {&S.c, s}, {&S.alpha, s}, {&S.omega, 1}, {&S.beta, 1}}, {&S.bnorm, &S.rr}, rtol,
+                 maxit);
+    const dim3 grid(kCgBlocks), blk(256);
+    auto finish = [&](int mode, int k, int step, const D *p0, const D *p1) {
+      hipLaunchKernelGGL((k_idr_finish<D>), dim3(1), dim3(1024), 0, stream, p0, p1, C, nc, mode, k, step, S);
+    };
+    vec_op(1, n, nc, r, nc, dB, ldb, nullptr, 0);            // r = b
+    hipLaunchKernelGGL((k_cg_dot<D>), grid, blk, 0, stream, n, nc, (const D *)r, (int64_t)nc, (const D *)nullptr, pt);
+    finish(0, 0, 0, pt, nullptr);                             // ||b||, omega = 1, M = I
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);        // x = 0
+    for (int i = 0; i < s; ++i) {                             // G = U = 0
+      HIP_OK(hipMemsetAsync(G[i], 0, vec, stream));
+      HIP_OK(hipMemsetAsync(U[i], 0, vec, stream));
+    }
+    HIP_OK(hipGetLastError());
+    int step = 0, go = krylov_active(S);
+    while (go > 0 && step < maxit) {
+      idr_coef(r, nc);
+      finish(1, 0, step, nullptr, nullptr);                   // f = P^H r, c
+      for (int k = 0; k < s && go > 0; ++k, ++step) {
+        idr_comb<false>(s - k, nc, v, r, G + k, S.c + k * 64, nullptr);       // v = r - sum c_i g_i
+        solve_dev((const D *)v, nc, vh, nc, nc, rank, nullptr);               // v^ = M^{-1} v
+        idr_comb<true>(s - k, nc, U[k], vh, U + k, S.c + k * 64, S.omega);    // u = omega v^ + sum c_i u_i, in U_k
+        spmv_dev((const D *)U[k], nc, G[k], nc, nc, nullptr);                 // g = A u, in G_k
+        idr_coef(G[k], nc);
+        finish(2, k, step, nullptr, nullptr);                 // alpha, M[:, k], beta, f, the next c
+        idr_gu(k, nc, dX, ldx, r, G, U, S, pt);
+        finish(3, k, step, pt, nullptr);                      // ||r|| / ||b||, maxit
+        HIP_OK(hipGetLastError());
+        go = krylov_active(S);
+      }
+      if (go == 0) break;
+      solve_dev((const D *)r, nc, vh, nc, nc, rank, nullptr);  // v^ = M^{-1} r
+      spmv_dev((const D *)vh, nc, t, nc, nc, nullptr);         // t = A v^
+      hipLaunchKernelGGL((k_bs_tr<D>), grid, blk, 0, stream, n, nc, (const D *)t, (const D *)r, pt, pt2);
+      finish(4, 0, step, pt, pt2);                             // omega
+      hipLaunchKernelGGL((k_cg_xr<D>), grid, blk, 0, stream, n, nc, dX, ldx, r, (const D *)vh, (const D *)t,
+                         (const D *)S.omega, (const int *)S.active, pt);  // x += omega v^, r -= omega t
+      finish(3, 0, step, pt, nullptr);
+      HIP_OK(hipGetLastError());
+      ++step;
+      go = krylov_active(S);
+    }
+    krylov_result(S, nc, flags, iters);
+  }
+
+  void idrs_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int s, const T *P, int64_t ldp, uint64_t seed,
+                double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr,
+                 [&] {
+                   idrs_check(s, P, ldp, maxit, rtol);
+                   idrs_shadow(s, P, ldp, seed);
+                 },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) { idrs_tile(b, ldb, x, ldx, nc, s, rtol, maxit, rank, fl, it); });
+  }
+  void idrs_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int s, const T *P, int64_t ldp, uint64_t seed,
+                 double rtol, int maxit, int64_t rank, int *flags, int *iters) {
+    staged(B, ldb, X, ldx, nrhs, false, [&] { idrs_check(s, P, ldp, maxit, rtol); },
+           [&](const D *b, D *x) { idrs_dev(b, nrhs, x, nrhs, nrhs, s, P, ldp, seed, rtol, maxit, rank, flags, iters); });
   }
 
   // ---- symmetric QMR for a Hermitian indefinite pair, batched over columns ---------------------------
@@ -4629,6 +4813,24 @@ HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb,
   API_BEGIN
   DISPATCH(ENG_D->bicgstab_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
            ENG_Z->bicgstab_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_idrs_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int s,
+                               const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank, int *flags,
+                               int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->idrs_host((const double *)B, ldb, (double *)X, ldx, nrhs, s, (const double *)P, ldp, seed, rtol, maxit, rank, flags, iters),
+           ENG_Z->idrs_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, s, (const zdouble *)P, ldp, seed, rtol, maxit, rank, flags, iters))
+  API_END
+}
+
+HifAmdStatus hifamd_idrs_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int s,
+                                   const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank,
+                                   int *flags, int *iters) {
+  API_BEGIN
+  DISPATCH(ENG_D->idrs_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, s, (const double *)P, ldp, seed, rtol, maxit, rank, flags, iters),
+           ENG_Z->idrs_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, s, (const zdouble *)P, ldp, seed, rtol, maxit, rank, flags, iters))
   API_END
 }
 

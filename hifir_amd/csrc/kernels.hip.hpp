@@ -31,6 +31,8 @@
 //   k_bs_tr / k_bs_xr_full / k_bs_p / k_bs_finish   device-resident BiCGSTAB (same reductions; with k_cg_dot and k_cg_xr)
 //   k_qm_r / k_qm_ds / k_qm_finish   device-resident symmetric QMR for Hermitian indefinite pairs (same reductions;
 //                    with k_cg_dot and k_cg_p)
+//   k_idr_comb / k_idr_gu / k_idr_finish / k_idr_pfill   device-resident IDR(s) (same reductions; with k_cg_dot, k_cg_xr,
+//                    k_bs_tr and, for P^H x, k_nsp_coef / k_nsp_finish)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -2585,6 +2587,208 @@ __global__ void __launch_bounds__(256) k_probe_fill(int64_t n, uint64_t seed, T 
       x[e] = cplx{probe_value(seed, (uint64_t)e + 1), probe_value(seed, (uint64_t)(total + e) + 1)};
     else
       x[e] = probe_value(seed, (uint64_t)e + 1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident right-preconditioned IDR(s) with biorthogonalization (van Gijzen / Sonneveld, ACM TOMS 38(1), 2011)
+// and x0 = 0, up to 64 columns in lock step (Engine::idrs_tile).  Same layout and row walk as k_cg_*: vectors [n][nc],
+// lane = column, wave w of block b owns the rows i = 4 b + w + k * 4 kCgBlocks, wave partials added in wave order and the
+// kCgBlocks block partials of a column in k_cg_finish's order by k_idr_finish; a column's bits do not depend on the batch
+// it travels in.  The shadow block P is [n][K], K = s padded with zero columns to 1, 2, 4 or 8, shared by all columns:
+// P^H r and P^H g are k_nsp_coef<T, K> + k_nsp_finish as they stand.  (t, r) and (t, t) are k_bs_tr, the omega update is
+// k_cg_xr.  A step is one M^{-1} apply plus one SpMM; a cycle is s + 1 steps.
+// ---------------------------------------------------------------------------------------------
+constexpr int kIdrMax = 8;  // HIFAMD_IDRS_MAX
+
+template <class T>
+struct IdState : KrylovState {  // (iter counts steps)
+  T *M;               // [s][s][64]  M[i][l] = p_i^H g_l (lower triangle in use; the identity at the start)
+  T *f, *c, *alpha;   // [s][64]     P^H r as the cycle updates it, the combination coefficients, the biorthogonalization's
+  T *omega, *beta;    // [64]        (beta: 0 for a frozen column)
+  double *rr;         // [64]        ||r||^2 at the last stopping test (||b||^2 at the start)
+  int s;
+};
+
+// a run of S work vectors of the pool (each [n][nc]) as a kernel argument
+template <class T, int S>
+struct IdRun {
+  T *w[S > 0 ? S : 1];
+};
+
+// y = z - sum_j c_j W_j (U false: v from r and G_k ..) or y = omega z + sum_j c_j W_j (U true: u from v^ and U_k ..), the sum
+// over the S vectors of the run formed first, j ascending.  The S loads of a row are unconditional, the coefficients stay
+// in registers, every input is read once and y written once; y may be W_0 itself (u goes to U_k in place).
+template <class T, int S, bool U>
+__global__ void __launch_bounds__(256) k_idr_comb(int64_t n, int nc, T *y, const T *z, IdRun<T, S> W,
+                                                  const T *__restrict__ coef /* [S][64] */, const T *__restrict__ omega) {
+  const int c = threadIdx.x & 63;
+  if (c >= nc) return;
+  T cj[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) cj[j] = coef[j * 64 + c];
+  const T om = U ? omega[c] : vzero(T());
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+    T wv[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) wv[j] = W.w[j][i * nc + c];
+    const T zi = z[i * nc + c];
+    T acc = vmul(cj[0], wv[0]);
+#pragma unroll
+    for (int j = 1; j < S; ++j) acc = vadd(acc, vmul(cj[j], wv[j]));
+    y[i * nc + c] = U ? vadd(vmul(om, zi), acc) : vsub(zi, acc);
+  }
+}
+
+// The fused pass after the recursion of step k = S on the active columns: g_k -= sum_{l<k} alpha_l g_l,
+// u_k -= sum_{l<k} alpha_l u_l (each sum formed first, l ascending), r -= beta g_k, x += beta u_k (x: row stride ldx), with
+// the block's share of |r|^2.  All loads of a row are unconditional; a frozen column is not written (k_cg_xr's use of active).
+template <class T, int S>
+__global__ void __launch_bounds__(256) k_idr_gu(int64_t n, int nc, T *__restrict__ x, int64_t ldx, T *__restrict__ r,
+                                                T *__restrict__ gk, T *__restrict__ uk, IdRun<T, S> G, IdRun<T, S> U,
+                                                IdState<T> St, T *__restrict__ partial /* [kCgBlocks][64] */) {
+  __shared__ T sm[256];
+  const int c = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  T acc = vzero(T());
+  if (c < nc) {
+    const bool act = St.active[c] != 0;
+    const T be = St.beta[c];
+    T al[S > 0 ? S : 1];
+#pragma unroll
+    for (int l = 0; l < S; ++l) al[l] = St.alpha[l * 64 + c];
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += stride) {
+      T gv[S > 0 ? S : 1], uv[S > 0 ? S : 1];
+#pragma unroll
+      for (int l = 0; l < S; ++l) gv[l] = G.w[l][i * nc + c], uv[l] = U.w[l][i * nc + c];
+      T gi = gk[i * nc + c], ui = uk[i * nc + c], ri = r[i * nc + c];
+      const T xi = x[i * ldx + c];
+      if (act) {
+        if constexpr (S > 0) {
+          T ag = vmul(al[0], gv[0]), au = vmul(al[0], uv[0]);
+#pragma unroll
+          for (int l = 1; l < S; ++l) ag = vadd(ag, vmul(al[l], gv[l])), au = vadd(au, vmul(al[l], uv[l]));
+          gi = vsub(gi, ag);
+          ui = vsub(ui, au);
+          gk[i * nc + c] = gi;
+          uk[i * nc + c] = ui;
+        }
+        ri = vsub(ri, vmul(be, gi));
+        r[i * nc + c] = ri;
+        x[i * ldx + c] = vadd(xi, vmul(be, ui));
+      }
+      acc = vadd(acc, vfromreal(vabs2(ri), T()));
+    }
+  }
+  cg_block_partial(acc, sm, partial);
+}
+
+// c_k .. c_{s-1} of column c by forward substitution on the lower triangle M[k:, k:] c = f[k:]
+template <class T>
+__device__ __forceinline__ void idr_forward(const IdState<T> &S, int c, int k) {
+  const int s = S.s;
+  for (int i = k; i < s; ++i) {
+    T v = S.f[i * 64 + c];
+    for (int l = k; l < i; ++l) v = vsub(v, vmul(S.M[(i * s + l) * 64 + c], S.c[l * 64 + c]));
+    S.c[i * 64 + c] = vdiv(v, S.M[(i * s + i) * 64 + c]);
+  }
+}
+
+constexpr double kIdrKappa = 0.7;  // the "maintaining convergence" bound on the cosine of t and r
+
+// Sums the kCgBlocks partials of every column of p0 (and of p1 when given; cg_sum_partials) and does the per-column scalar
+// work; step counts the steps completed before this one, k is the position in the cycle, C [K][64] what k_nsp_finish left:
+//   mode 0: p0 = ||b||^2: ||b||, omega = 1, M = I; b = 0 is done (x = 0, flag 0, 0 steps); not finite: flag 1, 0 steps
+//   mode 1: C = P^H r: f = C, c = the forward substitution from row 0
+//   mode 2: C = P^H g: alpha_i = (C_i - sum_{l<i} alpha_l M[i,l]) / M[i,i] (i < k), M[i,k] = C_i - sum_{l<k} alpha_l M[i,l]
+//           (i >= k); M[k,k] zero or not finite: flag 1, step + 1 steps; else beta = f_k / M[k,k], f_i = 0 (i <= k),
+//           f_i -= beta M[i,k] (i > k), and c = the forward substitution from row k + 1
+//   mode 3: p0 = |r|^2: ||r|| / ||b|| <= rtol -> flag 0, step + 1 steps; step + 1 >= maxit -> flag 2
+//   mode 4: p0 = (t, r), p1 = (t, t): either zero or not finite: flag 1, step + 1 steps; else omega = (t, r) / (t, t),
+//           rho = |(t, r)| / (||t|| ||r||), rho < kappa: omega *= kappa / rho
+// A column that stops gets beta = 0 and active = 0; ctl[0] = columns still active.
+template <class T>
+__global__ void __launch_bounds__(1024) k_idr_finish(const T *__restrict__ p0, const T *__restrict__ p1,
+                                                     const T *__restrict__ C, int nc, int mode, int k, int step,
+                                                     IdState<T> S) {
+  __shared__ T sm0[16 * 64], sm1[16 * 64];
+  __shared__ int cnt;
+  const int c = threadIdx.x & 63, s = S.s;
+  if (threadIdx.x == 0) cnt = 0;
+  const T t0 = cg_sum_partials(p0, nc, sm0), t1 = cg_sum_partials(p1, nc, sm1);
+  int act = 0, stop = -1, it = 0;  // stop, it: flag and steps of a column that stops here
+  if (threadIdx.x < nc) {
+    act = S.active[c];
+    if (mode == 0) {
+      const double bn = sqrt(vreal(t0));
+      S.bnorm[c] = bn;
+      S.rr[c] = vreal(t0);
+      S.iter[c] = 0;
+      S.flag[c] = 0;
+      S.omega[c] = vfromreal(1.0, T());
+      for (int i = 0; i < s; ++i) S.M[(i * s + i) * 64 + c] = vfromreal(1.0, T());  // (the state arrives zeroed)
+      act = !(bn == 0.0);
+      if (act && bs_bad(t0)) stop = 1, it = 0;
+    } else if (act && mode == 1) {
+      for (int i = 0; i < s; ++i) S.f[i * 64 + c] = C[i * 64 + c];
+      idr_forward(S, c, 0);
+    } else if (act && mode == 2) {
+      for (int i = 0; i < k; ++i) {
+        T a = C[i * 64 + c];
+        for (int l = 0; l < i; ++l) a = vsub(a, vmul(S.alpha[l * 64 + c], S.M[(i * s + l) * 64 + c]));
+        S.alpha[i * 64 + c] = vdiv(a, S.M[(i * s + i) * 64 + c]);
+      }
+      for (int i = k; i < s; ++i) {
+        T m = C[i * 64 + c];
+        for (int l = 0; l < k; ++l) m = vsub(m, vmul(S.alpha[l * 64 + c], S.M[(i * s + l) * 64 + c]));
+        S.M[(i * s + k) * 64 + c] = m;
+      }
+      const T mkk = S.M[(k * s + k) * 64 + c];
+      if (bs_bad(mkk)) {
+        stop = 1, it = step + 1;
+      } else {
+        const T be = vdiv(S.f[k * 64 + c], mkk);
+        S.beta[c] = be;
+        for (int i = 0; i <= k; ++i) S.f[i * 64 + c] = vzero(T());
+        for (int i = k + 1; i < s; ++i) S.f[i * 64 + c] = vsub(S.f[i * 64 + c], vmul(be, S.M[(i * s + k) * 64 + c]));
+        idr_forward(S, c, k + 1);
+      }
+    } else if (act && mode == 3) {
+      S.rr[c] = vreal(t0);
+      if (sqrt(vreal(t0)) / S.bnorm[c] <= S.rtol) stop = 0, it = step + 1;
+      else if (step + 1 >= S.maxit) stop = 2, it = S.maxit;
+    } else if (act && mode == 4) {
+      if (bs_bad(t1) || bs_bad(t0)) {
+        stop = 1, it = step + 1;
+      } else {
+        T om = vdiv(t0, t1);
+        const double rho = vabs1(t0) / (sqrt(vreal(t1)) * sqrt(S.rr[c]));
+        if (rho < kIdrKappa) om = vscale(kIdrKappa / rho, om);
+        S.omega[c] = om;
+      }
+    }
+  }
+  cg_close_mode(S, nc, act, stop, it, &cnt, [&](int c) { S.beta[c] = vzero(T()); });
+}
+
+// The generated shadow block P [n][K]: entry (i, j), j < s, from counter 16 i + j + 1 (the imaginary part of a complex entry
+// from counter 16 (n + i) + j + 1), the first s columns of k_probe_fill's block for the same seed; columns s .. K-1 zero.
+template <class T>
+__global__ void __launch_bounds__(256) k_idr_pfill(int64_t n, int s, int K, uint64_t seed, T *__restrict__ P) {
+  const int64_t total = n * K;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e / K;
+    const int j = (int)(e - i * K);
+    double re = 0.0, im = 0.0;
+    if (j < s) {
+      re = probe_value(seed, (uint64_t)(kNspMax * i + j) + 1);
+      if constexpr (std::is_same<T, cplx>::value) im = probe_value(seed, (uint64_t)(kNspMax * (n + i) + j) + 1);
+    }
+    if constexpr (std::is_same<T, cplx>::value)
+      P[e] = cplx{re, im};
+    else
+      P[e] = re;
   }
 }
 

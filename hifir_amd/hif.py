@@ -677,6 +677,21 @@ class HIF:
         flags: 0 converged, 1 breakdown, 2 reached maxit."""
         return self._krylov("bicgstab", b, rtol=rtol, maxit=maxit, full_rank=full_rank)
 
+    def idrs(self, b, s=4, rtol=1e-6, maxit=500, full_rank=False, P=None, seed=0):
+        """Right-preconditioned IDR(s) with biorthogonalization (x0 = 0) for a general pair (A, M), all columns of b ([n] or
+        [n][nrhs], host array or CUDA tensor) in lock step on the device (hifamd_idrs_batch / _dev).  Needs set_matrix.
+        s: 1 .. 8.  P: the [n][s] shadow block (a host array, used as given, one block for all columns), or None: generated
+        on the device from seed.  maxit and iters count steps (one apply plus one SpMM each; s + 1 per cycle).  Returns
+        (x, flags, iters); ints for a vector.  flags: 0 converged, 1 breakdown, 2 reached maxit."""
+        if P is None:
+            lead = (int(s), None, 0, int(seed))
+        else:
+            P = np.ascontiguousarray(P, dtype=self.dtype)
+            if P.ndim != 2 or P.shape[0] != self.nrows():
+                raise HifAmdError(2, "idrs: P must be [n][s]")
+            lead = (int(s), _p(P), P.shape[1], int(seed))
+        return self._krylov("idrs", b, *lead, rtol=rtol, maxit=maxit, full_rank=full_rank)
+
     def fgmres(self, b, restart=30, rtol=1e-6, maxit=500, full_rank=False):
         """Flexible GMRES with 2^k refinement sweeps as the preconditioner of outer cycle k (the reference's
         fgmres_hifir, examples/advanced/gmres.hpp:127-231); host arrays.  Returns (x, flags, iters, sweeps)."""

@@ -456,6 +456,45 @@ HifAmdStatus hifamd_bicgstab_batch(HifAmdHdl h, const void *B, int64_t ldb, void
 HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                        double rtol, int maxit, int64_t rank, int *flags, int *iters);
 
+/* ---- right-preconditioned IDR(s) for a general (non-Hermitian) pair (A, M), batched ------------ */
+/* IDR(s) with biorthogonalization (van Gijzen and Sonneveld, ACM TOMS 38(1), 2011) and its "maintaining convergence"
+ * choice of omega (kappa = 0.7), x0 = 0, for nrhs columns in lock step.  P is the [n][s] shadow block, (a, b) = sum
+ * conj(a_i) b_i:
+ *   r = b; G = U = 0 (n x s each); M = I_s; omega = 1
+ *   cycle: f = P^H r
+ *     for k = 0 .. s-1:  c_k .. c_{s-1} by forward substitution on the lower triangle M[k:, k:] c = f[k:];
+ *       v = r - sum_{i>=k} c_i g_i; v^ = M^{-1} v; u = omega v^ + sum_{i>=k} c_i u_i; g = A u   (a step); raw = P^H g;
+ *       alpha_i = (raw_i - sum_{l<i} alpha_l M[i,l]) / M[i,i] (i < k); M[i,k] = raw_i - sum_{l<k} alpha_l M[i,l] (i >= k);
+ *       g_k = g - sum_{l<k} alpha_l g_l; u_k = u - sum_{l<k} alpha_l u_l; beta = f_k / M[k,k]; r -= beta g_k;
+ *       x += beta u_k; test; f_i = 0 (i <= k); f_i -= beta M[i,k] (i > k)
+ *     v^ = M^{-1} r; t = A v^   (a step); omega = (t, r) / (t, t); rho = |(t, r)| / (||t|| ||r||);
+ *     rho < kappa: omega *= kappa / rho; r -= omega t; x += omega v^; test
+ * The test is ||r|| / ||b|| <= rtol, r by recurrence (the residual precision of the handle plays no part).  A STEP is
+ * one M^{-1} apply plus one SpMM, the unit of a BiCGSTAB step: maxit caps steps and iters[c] reports them.  Short
+ * recurrences, 2 s + 4 work vectors per 64-column tile (r, v, v^, t, G, U) and the per-column scalars in HBM; the host
+ * reads back one integer per step.  All columns of a tile share k; a column that stops is frozen.  The summation order
+ * of every inner product depends on n only, so a column's x, flag and steps depend on neither the batch width nor its
+ * neighbours.  s: 1 .. HIFAMD_IDRS_MAX.  P: a HOST pointer in both variants, [n][s] of the handle's value type,
+ * row-interleaved with row stride ldp >= s, one block for all columns, used exactly as given (not orthonormalized); or
+ * NULL: the block is generated on the device from seed, entry (i, j) = probe_value(seed, 16 i + j + 1), the imaginary
+ * part of a complex entry probe_value(seed, 16 (n + i) + j + 1) -- the first s columns of the block hifamd_nsp_find
+ * draws from the same seed (the generator is specified there), not orthonormalized either.  A null-space filter on
+ * HIFAMD_S (hifamd_set_nsp_const / hifamd_set_nsp_basis) filters every M^{-1} apply and nothing else, as in BiCGSTAB.
+ * Refusals as hifamd_bicgstab_batch, in its order (needs hifamd_set_matrix: HIFAMD_BAD_PREC; maxit < 1 or rtol <= 0:
+ * HIFAMD_MISMATCHED_SIZES), then s < 1, s > HIFAMD_IDRS_MAX or P given with ldp < s: HIFAMD_MISMATCHED_SIZES, then a
+ * non-finite entry of P: HIFAMD_BAD_PREC.  rank: 0 numerical rank, -1 full.  Per column: flags[c] = 0 converged /
+ * 1 breakdown (M[k,k], (t, t) or (t, r) exactly zero or not finite; x keeps its last completed update) / 2 reached maxit,
+ * iters[c] = steps taken (a zero column: x = 0, flag 0, 0 steps; a non-finite column: flag 1, 0 steps); either may be
+ * NULL.  Host pointers; the _dev variant takes device pointers for B, X (P, flags, iters stay host arrays), writes X in
+ * place and returns when the solve is done. */
+#define HIFAMD_IDRS_MAX 8
+HifAmdStatus hifamd_idrs_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int s,
+                               const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank,
+                               int *flags, int *iters);
+HifAmdStatus hifamd_idrs_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int s,
+                                   const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank,
+                                   int *flags, int *iters);
+
 /* ---- symmetric QMR for a Hermitian INDEFINITE pair (A, M), batched ---------------------------- */
 /* The symmetric QMR of Freund and Nachtigal with x0 = 0 for nrhs columns in lock step: PCG's coupled two-term
  * recurrence without the positivity requirement (A M^{-1} is self-adjoint in the indefinite form induced by M^{-1}),

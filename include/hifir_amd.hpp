@@ -336,6 +336,20 @@ class HIF {
     return std::make_tuple(std::move(x), flag, iters);
   }
 
+  // ---- right-preconditioned IDR(s) for a general pair (A, M) on the device (hifamd_idrs_batch) ----
+  // s: 1 .. HIFAMD_IDRS_MAX; the shadow block is generated from seed.  iters counts steps (one apply plus one SpMM each);
+  // flag 0 converged, 1 breakdown, 2 reached maxit.
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, int, int> idrs(const Matrix &A, const ArrayType &b, const int s, const double rtol, const int maxit,
+                                       const bool full_rank = false, const std::uint64_t seed = 0) {
+    ensure_matrix(A);
+    ArrayType x(b.size());
+    int flag = 0, iters = 0;
+    detail::check(hifamd_idrs_batch(_h, b.data(), 1, x.data(), 1, 1, s, nullptr, 0, seed, rtol, maxit, full_rank ? -1 : 0,
+                                    &flag, &iters));
+    return std::make_tuple(std::move(x), flag, iters);
+  }
+
  private:
   void require() const {
     if (!_h) throw std::runtime_error("hifir_amd: MILU-Prec is empty!");  // builder.hpp:412
