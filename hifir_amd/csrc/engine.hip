@@ -428,7 +428,13 @@ class EngineBase {
 template <class T>
 class Engine : public EngineBase {
  public:
+  typedef T value_type;
   typedef typename DevT<T>::type D;
+  // the C ABI's untyped blocks as this engine reads them: host arrays hold T, device arrays hold D
+  static const T *val(const void *p) { return (const T *)p; }
+  static T *val(void *p) { return (T *)p; }
+  static const D *dev(const void *p) { return (const D *)p; }
+  static D *dev(void *p) { return (D *)p; }
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = true;  // the adjoint engine runs on its primary's stream
@@ -1740,9 +1746,24 @@ class Engine : public EngineBase {
       ++count;
     }
   }
+  // one diagonal block of a block-dense thin band: t = rhs - (everything before the block); then
+  // x[rows] = Tinv * t on the matrix cores (LOWER: also v = x / d)
   template <bool LOWER>
   void launch_dense_block(hipStream_t st, const DevLevel &L, const DevCsr &M, int32_t q, int logR, int64_t &count,
-                          bool rhs_ready = false);
+                          bool rhs_ready = false) {
+    const int32_t r0 = M.blk_slot0[(size_t)q], r1 = M.blk_slot1[(size_t)q], nb = r1 - r0;
+    D *x = LOWER ? L.w.as<D>() : L.v.as<D>();
+    D *tb = blk_tmp.as<D>();
+    if (!rhs_ready) {  // (the first block of a band gets its right-hand side from the prefix pass)
+      tally(KF_THIN_UPDATE);
+      hipLaunchKernelGGL((k_thin_update<D>), dim3(grid_for(nb, logR)), dim3(256), 0, st, r0, r1, M.ptr.as<int32_t>(),
+                         M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(), M.srcslot.as<int32_t>(),
+                         M.rowid.as<int32_t>(), (const D *)x, tb, logR);
+      ++count;
+    }
+    zgemm_tri(st, nb, M.tinv.as<double>() + M.blk_inv_off[(size_t)q], (const D *)tb, logR, M.rowid.as<int32_t>() + r0, x,
+              (const D *)nullptr, (D *)nullptr, count);
+  }
   // Out[rowmap] = G X on the matrix cores (kernels.hip.hpp k_top_gemm): 64-row tiles x K splits chosen so that one wave
   // of workgroups fills the chip; the splits' partial tiles are added in order by k_top_reduce
   static constexpr size_t kTopGemmLds = 2 * 64 * 80 * sizeof(double);
@@ -1806,18 +1827,20 @@ class Engine : public EngineBase {
   // the level's top rows: t_T = w_T - (sources outside T) by the chip-wide prefix pass, straight into the product's
   // right-hand side; then v_T = G t_T on the matrix cores (G = U_TT^{-1} D_T^{-1} L_TT^{-1}, rows scattered by L's row ids)
   void launch_top(hipStream_t st, const DevLevel &L, int logR, int64_t &count, const FL &fl) {
+    if constexpr (!std::is_same<T, double>::value)
+      if (!(zop_flags & 2)) throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle that did not ask for it");
+    const DevCsr &M = L.L;
+    const size_t b = (size_t)L.top_bandL;
+    const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
+    tally(KF_TRSV_WIDE);
+    hipLaunchKernelGGL((k_trsv_wide<D, true, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
+                       M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<D>(),
+                       M.rowid.as<int32_t>(), L.d.as<D>(), L.w.as<D>(), L.v.as<D>(), logR, 1, blk_tmp.as<D>(), (int32_t)s1,
+                       fl);
+    ++count;  // (the prefix pass)
     if constexpr (std::is_same<T, double>::value) {
-      const DevCsr &M = L.L;
-      const size_t b = (size_t)L.top_bandL;
-      const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
       const int nt = (int)L.top_n;
-      tally(KF_TRSV_WIDE);
-      hipLaunchKernelGGL((k_trsv_wide<double, true, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
-                         M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(),
-                         M.rowid.as<int32_t>(), L.d.as<double>(), L.w.as<double>(), L.v.as<double>(), logR, 1,
-                         blk_tmp.as<double>(), (int32_t)s1, fl);
       const int ktop = (int)round_up32(nt);
-      ++count;  // (the prefix pass)
       if (top_gemm >= 4) {
         launch_top_gemm(st, nt, L.topG.as<double>(), (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0,
                         L.v.as<double>(), count);
@@ -1835,16 +1858,6 @@ class Engine : public EngineBase {
         hipLaunchKernelGGL(k_strip_gemm4_d<4>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, ktop, L.topG.as<double>(), ktop,
                            (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0, L.v.as<double>());
     } else {
-      if (!(zop_flags & 2)) throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle that did not ask for it");
-      const DevCsr &M = L.L;
-      const size_t b = (size_t)L.top_bandL;
-      const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
-      tally(KF_TRSV_WIDE);
-      hipLaunchKernelGGL((k_trsv_wide<cplx, true, true>), dim3(grid_for(s1 - s0, logR)), dim3(256), 0, st, s0, s1,
-                         M.ptr.as<int32_t>(), M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<cplx>(),
-                         M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(), logR, 1,
-                         blk_tmp.as<cplx>(), (int32_t)s1, fl);
-      ++count;  // (the prefix pass)
       launch_top_gemm_z(st, (int)L.top_n, L.topG.as<double>(), (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0,
                         L.v.as<double>(), count);
     }
@@ -2095,6 +2108,20 @@ class Engine : public EngineBase {
                        (const double *)t1, (const double *)t2, logR, rowmap, Out, dscale, Out2);
     count += 3;
   }
+  // the same step of a real handle: one product, one workgroup per 16-row strip (4 waves split K)
+  void zgemm(hipStream_t st, int rows_total, int rows_valid, int kend, int tri, const DevBuf &A, int lda, const double *X,
+             int logR, const int32_t *rowmap, double *Out, const double *dscale, double *Out2, int64_t &count) {
+    const dim3 grid((unsigned)((rows_total + 15) / 16), ((1u << logR) + 15) / 16);
+    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, rows_total, rows_valid, kend, tri, A.as<double>(), lda, X,
+                       logR, rowmap, Out, dscale, Out2);
+    tally(KF_DENSE_GEMM);
+    ++count;
+  }
+  void row_gather(hipStream_t st, const D *in, const int32_t *map, int rows, D *out, int logR, int64_t &count) {
+    hipLaunchKernelGGL((k_row_gather<D>), dim3(grid_for(rows, logR)), dim3(256), 0, st, in, map, (int64_t)rows, out, logR);
+    tally(KF_ROW_GATHER);
+    ++count;
+  }
   void zgemm_tri(hipStream_t st, int nb, const double *Aops, const cplx *X, int logR, const int32_t *rowmap, cplx *Out,
                  const cplx *dscale, cplx *Out2, int64_t &count) {
     const int lda = (int)round_up32(nb);
@@ -2111,8 +2138,48 @@ class Engine : public EngineBase {
                        (const double *)t2, logR, rowmap, Out, dscale, Out2);
     count += 3;
   }
+  // the same step of a real handle: one product, with as many waves as gemm_waves asks for
+  void zgemm_tri(hipStream_t st, int nb, const double *Aops, const double *X, int logR, const int32_t *rowmap, double *Out,
+                 const double *dscale, double *Out2, int64_t &count) {
+    const int lda = (int)round_up32(nb);
+    const unsigned pairs = (unsigned)(((nb + 15) / 16 + 1) / 2);
+    const dim3 grid(pairs, ((1u << logR) + 15) / 16);
+    tally(KF_TRI_GEMM);
+    if (gemm_waves >= 16)
+      hipLaunchKernelGGL(k_tri_gemm_d<16>, grid, dim3(1024), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
+    else if (gemm_waves >= 8)
+      hipLaunchKernelGGL(k_tri_gemm_d<8>, grid, dim3(512), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
+    else
+      hipLaunchKernelGGL(k_tri_gemm_d<4>, grid, dim3(256), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
+    ++count;
+  }
 
-  void launch_dense(hipStream_t st, const D *cin, D *zout, int logR, int64_t rank, int64_t &count);
+  // dense last level: z = P * [ Rinv(1:rk,1:rk) * (Q^H c)(1:rk) ; 0 ]   (QRCP::_solve_nt, QRCP.hpp:371-411)
+  void launch_dense(hipStream_t st, const D *cin, D *zout, int logR, int64_t rank, int64_t &count) {
+    const int nd = (int)dn.n, rk = (int)eff_rank(rank);
+    D *tmp = dn.tmp.as<D>();
+    if (dn.lup) {  // LUP::solve (LUP.hpp:141-152): ?getrs, here one product with the explicit inverse; rank is ignored
+      zgemm(st, nd, nd, nd, 0, dn.QH, nd, cin, logR, nullptr, zout, nullptr, nullptr, count);
+      return;
+    }
+    if (dn.symm) {  // SYEIG::solve (SYEIG.hpp:181-200): z = V(:,to(1:rk)) diag(1/w) V(:,to(1:rk))^H c
+      zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
+      zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
+      return;
+    }
+    if (adjoint) {  // QRCP::_solve_t (QRCP.hpp:413-452): z = Q(:,1:rk) R(1:rk,1:rk)^{-H} (P^T c)(1:rk)
+      D *tmp2 = dn.tmp2.as<D>();
+      row_gather(st, cin, dn.jpvt0.as<int32_t>(), nd, tmp2, logR, count);
+      // T1[i] = sum_{k<=i} conj(Rinv(k,i)) c[jpvt[k]], i < rk (rows >= rk come out as zeros)
+      zgemm(st, nd, rk, rk, 2, dn.RinvH, nd, tmp2, logR, nullptr, tmp, nullptr, nullptr, count);
+      zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
+      return;
+    }
+    // T1 = Q^H(1:rk, :) c   (rows >= rk come out as zeros and are never read)
+    zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
+    // z[jpvt[i]] = sum_{k>=i} Rinv(i,k) T1[k], i < rk; zero rows beyond rk
+    zgemm(st, nd, rk, rk, 1, dn.Rinv, nd, tmp, logR, dn.jpvt0.as<int32_t>(), zout, nullptr, nullptr, count);
+  }
 
   int64_t eff_rank(int64_t rank) const {
     if (rank == 0) return dn.rank;
@@ -2355,7 +2422,30 @@ class Engine : public EngineBase {
     prod_ready = true;
   }
 
-  void launch_dense_mul(hipStream_t st, const D *cin, D *zout, int logR, int64_t rank, int64_t &count);
+  // dense last level of the product: QRCP::_multiply_nt (QRCP.hpp:460-495) z = Q(:,1:rk) R(1:rk,1:rk) (P^T c)(1:rk);
+  // on the adjoint engine QRCP::_multiply_t (:502-541) z[jpvt] = R^H (Q^H c)(1:rk)
+  void launch_dense_mul(hipStream_t st, const D *cin, D *zout, int logR, int64_t rank, int64_t &count) {
+    const int nd = (int)dn.n, rk = (int)eff_rank(rank);
+    D *tmp = dn.tmp.as<D>();
+    if (dn.lup) {  // LUP::multiply (LUP.hpp:181-188): z = A c (adjoint engine: A^H c)
+      zgemm(st, nd, nd, nd, 0, dn.Rm, nd, cin, logR, nullptr, zout, nullptr, nullptr, count);
+      return;
+    }
+    if (dn.symm) {  // SYEIG::multiply (SYEIG.hpp:256-273): z = V(:,to(1:rk)) diag(w) V(:,to(1:rk))^H c
+      zgemm(st, nd, rk, nd, 0, dn.Rm, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
+      zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
+      return;
+    }
+    if (adjoint) {
+      zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
+      zgemm(st, nd, rk, rk, 2, dn.Rm, nd, tmp, logR, dn.jpvt0.as<int32_t>(), zout, nullptr, nullptr, count);
+      return;
+    }
+    D *tmp2 = dn.tmp2.as<D>();
+    row_gather(st, cin, dn.jpvt0.as<int32_t>(), nd, tmp2, logR, count);
+    zgemm(st, nd, rk, rk, 1, dn.Rm, nd, tmp2, logR, nullptr, tmp, nullptr, nullptr, count);
+    zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
+  }
 
   void enqueue_prod_level(hipStream_t st, size_t l, InP bin, int64_t ldb, OutP yout, int64_t ldy, int nrhs,
                           int logR, int64_t rank, int64_t &count) {
@@ -2876,10 +2966,7 @@ class Engine : public EngineBase {
   }
 
   void vec_op(int op, int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const D *z, int64_t ldz) {
-    int64_t g = (n * nrhs + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL((k_vec_op<D>), dim3((unsigned)g), dim3(256), 0, stream, op, n, (int)nrhs, y, ldy, x, ldx, z, ldz);
+    hipLaunchKernelGGL((k_vec_op<D>), dim3(vec_grid(n * nrhs)), dim3(256), 0, stream, op, n, (int)nrhs, y, ldy, x, ldx, z, ldz);
   }
 
   // per-column 2-norms of an [n][nrhs] block (nrhs <= 64 per pass); result on the host
@@ -2989,7 +3076,10 @@ class Engine : public EngineBase {
       for (int64_t c = 0; c < nrhs; ++c) ir_status[2 * c] = iters[(size_t)c], ir_status[2 * c + 1] = flag[(size_t)c];
   }
 
-  void launch_masked_add(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask);
+  // masked axpy of the bounded IR variant: where mask[c], y[:, c] += x[:, c]
+  void launch_masked_add(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
+    hipLaunchKernelGGL((k_masked_add<D>), dim3(vec_grid(n * nrhs)), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
+  }
 
   void hifir_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int nirs, const double *betas,
                   int64_t rank, int *ir_status) {
@@ -3275,7 +3365,9 @@ class Engine : public EngineBase {
   // flag 1 at once.  The restart residuals of the inner GMRES follow the handle's mode.  No pool vector is held while
   // gmres_dev runs (see kr_vec): r lives in ir_r, the previous iterate in ir_xk, the correction in gi_d.
   DevBuf gi_d, gi_mask;
-  void launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask);
+  void launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
+    hipLaunchKernelGGL((k_masked_set<D>), dim3(vec_grid(n * nrhs)), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
+  }
   void gmres_ir_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, int restart, double rtol, double inner_rtol,
                      int max_outer, int inner_maxit, int64_t rank, int *flags, int *outer, int *iters, double *relres) {
     const int64_t n = lv[0]->n;
@@ -3930,244 +4022,6 @@ class Engine : public EngineBase {
   }
 };
 
-// masked axpy kernel for the bounded IR variant
-template <class D>
-__global__ void __launch_bounds__(256) k_masked_add(int64_t n, int nrhs, D *y, int64_t ldy, const D *x, int64_t ldx,
-                                                    const int *mask) {
-  const int64_t total = n * nrhs;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = e / nrhs;
-    const int c = (int)(e - i * nrhs);
-    if (mask[c]) y[i * ldy + c] = vadd(y[i * ldy + c], x[i * ldx + c]);
-  }
-}
-
-// where mask[c]: y[:, c] = x[:, c], or 0 when x is NULL
-template <class D>
-__global__ void __launch_bounds__(256) k_masked_set(int64_t n, int nrhs, D *y, int64_t ldy, const D *x, int64_t ldx,
-                                                    const int *mask) {
-  const int64_t total = n * nrhs;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = e / nrhs;
-    const int c = (int)(e - i * nrhs);
-    if (mask[c]) y[i * ldy + c] = x ? x[i * ldx + c] : vzero(D());
-  }
-}
-
-template <class T>
-void Engine<T>::launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
-  int64_t g = (n * nrhs + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL((k_masked_set<D>), dim3((unsigned)g), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
-}
-
-template <class T>
-void Engine<T>::launch_masked_add(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
-  int64_t g = (n * nrhs + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL((k_masked_add<D>), dim3((unsigned)g), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
-}
-
-// dense last level: z = P * [ Rinv(1:rk,1:rk) * (Q^H c)(1:rk) ; 0 ]   (QRCP::_solve_nt, QRCP.hpp:371-411)
-template <>
-void Engine<double>::launch_dense(hipStream_t st, const double *cin, double *zout, int logR, int64_t rank, int64_t &count) {
-  const int nd = (int)dn.n, rk = (int)eff_rank(rank);
-  const unsigned g = (unsigned)((nd + 15) / 16);  // one workgroup per 16-row strip (4 waves split K)
-  double *tmp = dn.tmp.as<double>();
-  if (dn.lup) {  // LUP::solve (LUP.hpp:141-152): ?getrs, here one product with the explicit inverse; rank is ignored
-    tally(KF_DENSE_GEMM);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, nd, nd, 0,
-                       dn.QH.as<double>(), nd, cin, logR, (const int32_t *)nullptr, zout, (const double *)nullptr,
-                       (double *)nullptr);
-    ++count;
-    return;
-  }
-  if (dn.symm) {  // SYEIG::solve (SYEIG.hpp:181-200): z = V(:,to(1:rk)) diag(1/w) V(:,to(1:rk))^H c
-    tally(KF_DENSE_GEMM, 2);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, nd, 0,
-                       dn.QH.as<double>(), nd, cin, logR, (const int32_t *)nullptr, tmp, (const double *)nullptr,
-                       (double *)nullptr);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, nd, rk, 0,
-                       dn.Qm.as<double>(), nd, (const double *)tmp, logR, (const int32_t *)nullptr, zout,
-                       (const double *)nullptr, (double *)nullptr);
-    count += 2;
-    return;
-  }
-  if (adjoint) {  // QRCP::_solve_t (QRCP.hpp:413-452): z = Q(:,1:rk) R(1:rk,1:rk)^{-H} (P^T c)(1:rk)
-    double *tmp2 = dn.tmp2.as<double>();
-    tally(KF_ROW_GATHER), tally(KF_DENSE_GEMM, 2);
-    hipLaunchKernelGGL((k_row_gather<double>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
-                       (int64_t)nd, tmp2, logR);
-    // T1[i] = sum_{k<=i} conj(Rinv(k,i)) c[jpvt[k]], i < rk (rows >= rk come out as zeros)
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, rk, 2,
-                       dn.RinvH.as<double>(), nd, (const double *)tmp2, logR, (const int32_t *)nullptr, tmp,
-                       (const double *)nullptr, (double *)nullptr);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, nd, rk, 0,
-                       dn.Qm.as<double>(), nd, (const double *)tmp, logR, (const int32_t *)nullptr, zout,
-                       (const double *)nullptr, (double *)nullptr);
-    count += 3;
-    return;
-  }
-  // T1 = Q^H(1:rk, :) c   (rows >= rk come out as zeros and are never read)
-  tally(KF_DENSE_GEMM, 2);
-  hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, nd, 0, dn.QH.as<double>(), nd, cin, logR,
-                     (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
-  // z[jpvt[i]] = sum_{k>=i} Rinv(i,k) T1[k], i < rk; zero rows beyond rk
-  hipLaunchKernelGGL(k_dense_gemm_d<4>, dim3(g, ((1u << logR) + 15) / 16), dim3(256), 0, st, nd, rk, rk, 1, dn.Rinv.as<double>(), nd, tmp, logR,
-                     dn.jpvt0.as<int32_t>(), zout, (const double *)nullptr, (double *)nullptr);
-  count += 2;
-}
-
-template <>
-void Engine<zdouble>::launch_dense(hipStream_t st, const cplx *cin, cplx *zout, int logR, int64_t rank, int64_t &count) {
-  const int nd = (int)dn.n, rk = (int)eff_rank(rank);
-  cplx *tmp = dn.tmp.as<cplx>();
-  if (dn.lup) {
-    zgemm(st, nd, nd, nd, 0, dn.QH, nd, cin, logR, nullptr, zout, nullptr, nullptr, count);
-    return;
-  }
-  if (dn.symm) {
-    zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
-    zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
-    return;
-  }
-  if (adjoint) {
-    cplx *tmp2 = dn.tmp2.as<cplx>();
-    tally(KF_ROW_GATHER);
-    hipLaunchKernelGGL((k_row_gather<cplx>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
-                       (int64_t)nd, tmp2, logR);
-    ++count;
-    zgemm(st, nd, rk, rk, 2, dn.RinvH, nd, tmp2, logR, nullptr, tmp, nullptr, nullptr, count);
-    zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
-    return;
-  }
-  zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
-  zgemm(st, nd, rk, rk, 1, dn.Rinv, nd, tmp, logR, dn.jpvt0.as<int32_t>(), zout, nullptr, nullptr, count);
-}
-
-// dense last level of the product: QRCP::_multiply_nt (QRCP.hpp:460-495) z = Q(:,1:rk) R(1:rk,1:rk) (P^T c)(1:rk);
-// on the adjoint engine QRCP::_multiply_t (:502-541) z[jpvt] = R^H (Q^H c)(1:rk)
-template <>
-void Engine<double>::launch_dense_mul(hipStream_t st, const double *cin, double *zout, int logR, int64_t rank, int64_t &count) {
-  const int nd = (int)dn.n, rk = (int)eff_rank(rank);
-  const unsigned g = (unsigned)((nd + 15) / 16);
-  const dim3 grid(g, ((1u << logR) + 15) / 16);
-  double *tmp = dn.tmp.as<double>();
-  if (dn.lup) {  // LUP::multiply (LUP.hpp:181-188): z = A c (adjoint engine: A^H c)
-    tally(KF_DENSE_GEMM);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, nd, nd, 0, dn.Rm.as<double>(), nd, cin, logR,
-                       (const int32_t *)nullptr, zout, (const double *)nullptr, (double *)nullptr);
-    ++count;
-    return;
-  }
-  if (dn.symm) {  // SYEIG::multiply (SYEIG.hpp:256-273): z = V(:,to(1:rk)) diag(w) V(:,to(1:rk))^H c
-    tally(KF_DENSE_GEMM, 2);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, nd, 0, dn.Rm.as<double>(), nd, cin, logR,
-                       (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, nd, rk, 0, dn.Qm.as<double>(), nd, (const double *)tmp,
-                       logR, (const int32_t *)nullptr, zout, (const double *)nullptr, (double *)nullptr);
-    count += 2;
-    return;
-  }
-  if (adjoint) {
-    tally(KF_DENSE_GEMM, 2);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, nd, 0, dn.QH.as<double>(), nd, cin, logR,
-                       (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
-    hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, rk, 2, dn.Rm.as<double>(), nd, (const double *)tmp,
-                       logR, dn.jpvt0.as<int32_t>(), zout, (const double *)nullptr, (double *)nullptr);
-    count += 2;
-    return;
-  }
-  double *tmp2 = dn.tmp2.as<double>();
-  tally(KF_ROW_GATHER), tally(KF_DENSE_GEMM, 2);
-  hipLaunchKernelGGL((k_row_gather<double>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
-                     (int64_t)nd, tmp2, logR);
-  hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, rk, rk, 1, dn.Rm.as<double>(), nd, (const double *)tmp2,
-                     logR, (const int32_t *)nullptr, tmp, (const double *)nullptr, (double *)nullptr);
-  hipLaunchKernelGGL(k_dense_gemm_d<4>, grid, dim3(256), 0, st, nd, nd, rk, 0, dn.Qm.as<double>(), nd, (const double *)tmp,
-                     logR, (const int32_t *)nullptr, zout, (const double *)nullptr, (double *)nullptr);
-  count += 3;
-}
-
-template <>
-void Engine<zdouble>::launch_dense_mul(hipStream_t st, const cplx *cin, cplx *zout, int logR, int64_t rank, int64_t &count) {
-  const int nd = (int)dn.n, rk = (int)eff_rank(rank);
-  cplx *tmp = dn.tmp.as<cplx>();
-  if (dn.lup) {
-    zgemm(st, nd, nd, nd, 0, dn.Rm, nd, cin, logR, nullptr, zout, nullptr, nullptr, count);
-    return;
-  }
-  if (dn.symm) {
-    zgemm(st, nd, rk, nd, 0, dn.Rm, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
-    zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
-    return;
-  }
-  if (adjoint) {
-    zgemm(st, nd, rk, nd, 0, dn.QH, nd, cin, logR, nullptr, tmp, nullptr, nullptr, count);
-    zgemm(st, nd, rk, rk, 2, dn.Rm, nd, tmp, logR, dn.jpvt0.as<int32_t>(), zout, nullptr, nullptr, count);
-    return;
-  }
-  cplx *tmp2 = dn.tmp2.as<cplx>();
-  tally(KF_ROW_GATHER);
-  hipLaunchKernelGGL((k_row_gather<cplx>), dim3(grid_for(nd, logR)), dim3(256), 0, st, cin, dn.jpvt0.as<int32_t>(),
-                     (int64_t)nd, tmp2, logR);
-  ++count;
-  zgemm(st, nd, rk, rk, 1, dn.Rm, nd, tmp2, logR, nullptr, tmp, nullptr, nullptr, count);
-  zgemm(st, nd, nd, rk, 0, dn.Qm, nd, tmp, logR, nullptr, zout, nullptr, nullptr, count);
-}
-
-// one diagonal block of a block-dense thin band: t = rhs - (everything before the block); then
-// x[rows] = Tinv * t on the matrix cores (LOWER: also v = x / d)
-template <>
-template <bool LOWER>
-void Engine<double>::launch_dense_block(hipStream_t st, const DevLevel &L, const DevCsr &M, int32_t q, int logR,
-                                        int64_t &count, bool rhs_ready) {
-  const int32_t r0 = M.blk_slot0[(size_t)q], r1 = M.blk_slot1[(size_t)q], nb = r1 - r0;
-  double *x = LOWER ? L.w.as<double>() : L.v.as<double>();
-  double *tb = blk_tmp.as<double>();
-  tally(KF_TRI_GEMM);
-  if (!rhs_ready) tally(KF_THIN_UPDATE);
-  if (!rhs_ready)  // (the first block of a band gets its right-hand side from the prefix pass)
-    hipLaunchKernelGGL((k_thin_update<double>), dim3(grid_for(nb, logR)), dim3(256), 0, st, r0, r1, M.ptr.as<int32_t>(),
-                       M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.srcslot.as<int32_t>(),
-                       M.rowid.as<int32_t>(), (const double *)x, tb, logR);
-  const unsigned g = (unsigned)((nb + 15) / 16);
-const unsigned pairs = (g + 1) / 2;
-#define HIFAMD_BLOCK_GEMM(NW)                                                                                   \
-  hipLaunchKernelGGL(k_tri_gemm_d<NW>, dim3(pairs, ((1u << logR) + 15) / 16), dim3(NW * 64), 0, st, nb,         \
-                     M.tinv.as<double>() + M.blk_inv_off[(size_t)q], (int)round_up32(nb), (const double *)tb,    \
-                     logR, M.rowid.as<int32_t>() + r0, x, (const double *)nullptr, (double *)nullptr)
-  if (gemm_waves >= 16) {
-    HIFAMD_BLOCK_GEMM(16);
-  } else if (gemm_waves >= 8) {
-    HIFAMD_BLOCK_GEMM(8);
-  } else {
-    HIFAMD_BLOCK_GEMM(4);
-  }
-#undef HIFAMD_BLOCK_GEMM
-  count += rhs_ready ? 1 : 2;
-}
-
-template <>
-template <bool LOWER>
-void Engine<zdouble>::launch_dense_block(hipStream_t st, const DevLevel &L, const DevCsr &M, int32_t q, int logR,
-                                         int64_t &count, bool rhs_ready) {
-  const int32_t r0 = M.blk_slot0[(size_t)q], r1 = M.blk_slot1[(size_t)q], nb = r1 - r0;
-  cplx *x = LOWER ? L.w.as<cplx>() : L.v.as<cplx>();
-  cplx *tb = blk_tmp.as<cplx>();
-  if (!rhs_ready) {
-    tally(KF_THIN_UPDATE);
-    hipLaunchKernelGGL((k_thin_update<cplx>), dim3(grid_for(nb, logR)), dim3(256), 0, st, r0, r1, M.ptr.as<int32_t>(),
-                       M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<cplx>(), M.srcslot.as<int32_t>(),
-                       M.rowid.as<int32_t>(), (const cplx *)x, tb, logR);
-    ++count;
-  }
-  zgemm_tri(st, nb, M.tinv.as<double>() + M.blk_inv_off[(size_t)q], (const cplx *)tb, logR, M.rowid.as<int32_t>() + r0, x,
-            (const cplx *)nullptr, (cplx *)nullptr, count);
-}
-
 }  // namespace hifamd
 
 // =============================================================================================
@@ -4198,14 +4052,12 @@ struct HifAmdPrec {
   }                                                    \
   return HIFAMD_SUCCESS;
 
-#define ENG_D ((Engine<double> *)h->eng)
-#define ENG_Z ((Engine<zdouble> *)h->eng)
-#define DISPATCH(call_d, call_z) \
-  if (h->vt == HIFAMD_D) {       \
-    call_d;                      \
-  } else {                       \
-    call_z;                      \
-  }
+// f(the handle's engine under its own type); the casts of an entry's untyped blocks come from that type (Engine::val, dev)
+template <class F>
+static decltype(auto) visit(HifAmdPrec *h, F &&f) {
+  if (h->vt == HIFAMD_D) return f(*(Engine<double> *)h->eng);
+  return f(*(Engine<zdouble> *)h->eng);
+}
 
 template <class E>
 static int64_t q_nrows(E *e) {
@@ -4257,12 +4109,13 @@ static void do_time(E *e, const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t 
 }
 
 template <class E>
-static void do_copy_columns(E *e, size_t elem, const void *src, int64_t lds, int64_t ncols, void *dst, int64_t ldd, int64_t col0) {
+static void do_copy_columns(E *e, const void *src, int64_t lds, int64_t ncols, void *dst, int64_t ldd, int64_t col0) {
   if (!e->finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
   if (!src || !dst) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
   if (ncols < 1 || lds < ncols || col0 < 0 || ldd < col0 + ncols) throw Error(HIFAMD_MISMATCHED_SIZES, "column block does not fit");
   HIP_OK(hipSetDevice(e->device));
   const int64_t n = e->lv[0]->n;
+  const size_t elem = sizeof(typename E::value_type);
   // a destination on ANOTHER device: the copy is a peer copy and needs peer access from this handle's device (enabled
   // once per pair; "already enabled" is fine); where the platform grants none the call fails loudly instead of a copy
   // that the runtime would stage or refuse at its own discretion
@@ -4362,12 +4215,10 @@ HifAmdStatus hifamd_add_level(HifAmdHdl h, int64_t m, int64_t n, const int64_t *
                               const double *s, const double *t, const int32_t *p, const int32_t *p_inv,
                               const int32_t *q, const int32_t *q_inv) {
   API_BEGIN
-  DISPATCH(ENG_D->add_level(m, n, Lcp, Lri, (const double *)Lv, Ucp, Uri, (const double *)Uv, Ecp, Eri,
-                            (const double *)Ev, F_ncols, Fcp, Fri, (const double *)Fv, (const double *)d, s, t, p,
-                            p_inv, q, q_inv),
-           ENG_Z->add_level(m, n, Lcp, Lri, (const zdouble *)Lv, Ucp, Uri, (const zdouble *)Uv, Ecp, Eri,
-                            (const zdouble *)Ev, F_ncols, Fcp, Fri, (const zdouble *)Fv, (const zdouble *)d, s, t,
-                            p, p_inv, q, q_inv))
+  visit(h, [&](auto &E) {
+    E.add_level(m, n, Lcp, Lri, E.val(Lv), Ucp, Uri, E.val(Uv), Ecp, Eri, E.val(Ev), F_ncols, Fcp, Fri, E.val(Fv), E.val(d), s,
+                t, p, p_inv, q, q_inv);
+  });
   API_END
 }
 
@@ -4376,15 +4227,11 @@ HifAmdStatus hifamd_set_nsp_const(HifAmdHdl h, HifAmdOp op, int64_t start, int64
   if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the filter belongs to HIFAMD_S or HIFAMD_SH");
   const bool on = !(end >= 0 && start > end);
   // (one filter per op: a constant-mode filter that is switched on replaces a basis)
-  if (h->vt == HIFAMD_D) {
-    Engine<double> &E = ENG_D->for_op(op);
+  visit(h, [&](auto &P) {
+    auto &E = P.for_op(op);
     E.nsp_on = on, E.nsp_r0 = start, E.nsp_r1 = end;
     if (on && E.nsp_k > 0) E.set_nsp_basis(0, nullptr, 0);
-  } else {
-    Engine<zdouble> &E = ENG_Z->for_op(op);
-    E.nsp_on = on, E.nsp_r0 = start, E.nsp_r1 = end;
-    if (on && E.nsp_k > 0) E.set_nsp_basis(0, nullptr, 0);
-  }
+  });
   API_END
 }
 
@@ -4393,41 +4240,37 @@ HifAmdStatus hifamd_set_nsp_basis(HifAmdHdl h, HifAmdOp op, int64_t k, const voi
   if (op != HIFAMD_S && op != HIFAMD_SH) throw Error(HIFAMD_MISMATCHED_SIZES, "the filter belongs to HIFAMD_S or HIFAMD_SH");
   if (k < 0 || k > HIFAMD_NSP_MAX) throw Error(HIFAMD_MISMATCHED_SIZES, "a null-space basis has 0 to 16 vectors (HIFAMD_NSP_MAX)");
   if (k > 0 && (!V || ldv < k)) throw Error(HIFAMD_MISMATCHED_SIZES, "null-space basis: NULL array or row stride smaller than k");
-  const bool fin = h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized;
-  if (!fin) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
-  // (removing a filter from an adjoint engine that was never built has nothing to do)
-  if (k == 0 && op == HIFAMD_SH && !(h->vt == HIFAMD_D ? (bool)ENG_D->adj : (bool)ENG_Z->adj)) return HIFAMD_SUCCESS;
-  DISPATCH(ENG_D->for_op(op).set_nsp_basis(k, (const double *)V, ldv), ENG_Z->for_op(op).set_nsp_basis(k, (const zdouble *)V, ldv))
+  visit(h, [&](auto &E) {
+    if (!E.finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    // (removing a filter from an adjoint engine that was never built has nothing to do)
+    if (k == 0 && op == HIFAMD_SH && !E.adj) return;
+    E.for_op(op).set_nsp_basis(k, E.val(V), ldv);
+  });
   API_END
 }
 
 int64_t hifamd_nsp_dim(HifAmdHdl h, HifAmdOp op) {
   if (!h || !h->eng) return -1;
-  if (op == HIFAMD_S) return h->vt == HIFAMD_D ? ENG_D->nsp_k : ENG_Z->nsp_k;
-  if (op == HIFAMD_SH) {
-    if (h->vt == HIFAMD_D) return ENG_D->adj ? ENG_D->adj->nsp_k : 0;
-    return ENG_Z->adj ? ENG_Z->adj->nsp_k : 0;
-  }
-  return 0;
+  return visit(h, [&](auto &E) -> int64_t {
+    if (op == HIFAMD_S) return E.nsp_k;
+    if (op == HIFAMD_SH) return E.adj ? E.adj->nsp_k : 0;
+    return 0;
+  });
 }
 
 HifAmdStatus hifamd_nsp_filter_batch(HifAmdHdl h, HifAmdOp op, void *X, int64_t ldx, int64_t nrhs) {
   API_BEGIN
-  if (h->vt == HIFAMD_D) {
-    if (Engine<double> *E = nsp_engine(ENG_D, op)) E->nsp_filter_host((double *)X, ldx, nrhs);
-  } else {
-    if (Engine<zdouble> *E = nsp_engine(ENG_Z, op)) E->nsp_filter_host((zdouble *)X, ldx, nrhs);
-  }
+  visit(h, [&](auto &E) {
+    if (auto *F = nsp_engine(&E, op)) F->nsp_filter_host(E.val(X), ldx, nrhs);
+  });
   API_END
 }
 
 HifAmdStatus hifamd_nsp_filter_batch_dev(HifAmdHdl h, HifAmdOp op, void *dX, int64_t ldx, int64_t nrhs, void *stream) {
   API_BEGIN
-  if (h->vt == HIFAMD_D) {
-    if (Engine<double> *E = nsp_engine(ENG_D, op)) E->nsp_filter_dev((double *)dX, ldx, nrhs, (hipStream_t)stream);
-  } else {
-    if (Engine<zdouble> *E = nsp_engine(ENG_Z, op)) E->nsp_filter_dev((cplx *)dX, ldx, nrhs, (hipStream_t)stream);
-  }
+  visit(h, [&](auto &E) {
+    if (auto *F = nsp_engine(&E, op)) F->nsp_filter_dev(E.dev(dX), ldx, nrhs, (hipStream_t)stream);
+  });
   API_END
 }
 
@@ -4443,39 +4286,38 @@ HifAmdStatus hifamd_nsp_find(HifAmdHdl h, HifAmdOp op, int64_t kmax, double tol,
   if (Q && ldq < kmax) throw Error(HIFAMD_MISMATCHED_SIZES, "basis output: row stride smaller than kmax");
   if (!found) throw Error(HIFAMD_MISMATCHED_SIZES, "found: NULL output");
   *found = 0;
-  // (before for_op: asking for the adjoint engine of a handle that cannot serve the call would build it first)
-  if (!(h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized)) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
-  if (!(h->vt == HIFAMD_D ? ENG_D->has_A : ENG_Z->has_A)) throw Error(HIFAMD_BAD_PREC, "the null-space search needs the matrix (hifamd_set_matrix)");
-  DISPATCH(ENG_D->for_op(op).nsp_find(kmax, tol, rtol, restart, maxit, rank, (const double *)X0, ldx0, seed, install != 0, found,
-                                      (double *)Q, ldq, resid16, info4),
-           ENG_Z->for_op(op).nsp_find(kmax, tol, rtol, restart, maxit, rank, (const zdouble *)X0, ldx0, seed, install != 0, found,
-                                      (zdouble *)Q, ldq, resid16, info4))
+  visit(h, [&](auto &E) {
+    // (before for_op: asking for the adjoint engine of a handle that cannot serve the call would build it first)
+    if (!E.finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!E.has_A) throw Error(HIFAMD_BAD_PREC, "the null-space search needs the matrix (hifamd_set_matrix)");
+    E.for_op(op).nsp_find(kmax, tol, rtol, restart, maxit, rank, E.val(X0), ldx0, seed, install != 0, found, E.val(Q), ldq,
+                          resid16, info4);
+  });
   API_END
 }
 
 int64_t hifamd_nsp_get_basis(HifAmdHdl h, HifAmdOp op, void *Q, int64_t ldq) {
   if (!h || !h->eng) return -1;
   try {
-    if (op == HIFAMD_S) return h->vt == HIFAMD_D ? ENG_D->nsp_get_basis((double *)Q, ldq) : ENG_Z->nsp_get_basis((zdouble *)Q, ldq);
-    if (op == HIFAMD_SH) {
-      if (h->vt == HIFAMD_D) return ENG_D->adj ? ENG_D->adj->nsp_get_basis((double *)Q, ldq) : 0;
-      return ENG_Z->adj ? ENG_Z->adj->nsp_get_basis((zdouble *)Q, ldq) : 0;
-    }
+    return visit(h, [&](auto &E) -> int64_t {
+      if (op == HIFAMD_S) return E.nsp_get_basis(E.val(Q), ldq);
+      if (op == HIFAMD_SH) return E.adj ? E.adj->nsp_get_basis(E.val(Q), ldq) : 0;
+      return 0;
+    });
   } catch (const std::exception &e) {
     set_err(e.what());
     return -1;
   }
-  return 0;
 }
 
 int hifamd_debug_checksums(HifAmdHdl h, uint64_t *out, int cap) {
   if (!h || !h->eng) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->debug_checksums(out, cap) : ENG_Z->debug_checksums(out, cap);
+  return visit(h, [&](auto &E) { return E.debug_checksums(out, cap); });
 }
 
 HifAmdStatus hifamd_set_complex_operators(HifAmdHdl h, int flags) {
   API_BEGIN
-  DISPATCH(ENG_D->set_complex_operators(flags), ENG_Z->set_complex_operators(flags))
+  visit(h, [&](auto &E) { E.set_complex_operators(flags); });
   API_END
 }
 
@@ -4492,7 +4334,7 @@ HifAmdStatus hifamd_save_ex(HifAmdHdl h, const char *path, int flags) {
   try {
     const int64_t vt = h->vt;
     if (std::fwrite(kFileMagic, 8, 1, f) != 1 || std::fwrite(&vt, 8, 1, f) != 1) throw Error(HIFAMD_HIFIR_ERROR, "short write");
-    DISPATCH(ENG_D->save(f, flags), ENG_Z->save(f, flags))
+    visit(h, [&](auto &E) { E.save(f, flags); });
   } catch (...) {
     std::fclose(f);
     throw;
@@ -4537,7 +4379,7 @@ HifAmdStatus hifamd_load_ex(const char *path, int device, int complex_operators,
     }
   }
   try {
-    DISPATCH(ENG_D->load(f), ENG_Z->load(f))
+    visit(h, [&](auto &E) { E.load(f); });
   } catch (const Error &e) {
     std::fclose(f);
     hifamd_destroy(h);
@@ -4556,130 +4398,131 @@ HifAmdStatus hifamd_load_ex(const char *path, int device, int complex_operators,
 
 HifAmdStatus hifamd_set_dense(HifAmdHdl h, int64_t nd, const void *mat, double rrqr_cond) {
   API_BEGIN
-  DISPATCH(ENG_D->set_dense(nd, (const double *)mat, rrqr_cond), ENG_Z->set_dense(nd, (const zdouble *)mat, rrqr_cond))
+  visit(h, [&](auto &E) { E.set_dense(nd, E.val(mat), rrqr_cond); });
   API_END
 }
 
 HifAmdStatus hifamd_set_dense_symm(HifAmdHdl h, int64_t nd, const void *mat, int spd) {
   API_BEGIN
-  DISPATCH(ENG_D->set_dense_symm(nd, (const double *)mat, spd), ENG_Z->set_dense_symm(nd, (const zdouble *)mat, spd))
+  visit(h, [&](auto &E) { E.set_dense_symm(nd, E.val(mat), spd); });
   API_END
 }
 
 HifAmdStatus hifamd_set_dense_lup(HifAmdHdl h, int64_t nd, const void *mat) {
   API_BEGIN
-  DISPATCH(ENG_D->set_dense_lup(nd, (const double *)mat), ENG_Z->set_dense_lup(nd, (const zdouble *)mat))
+  visit(h, [&](auto &E) { E.set_dense_lup(nd, E.val(mat)); });
   API_END
 }
 
 HifAmdStatus hifamd_finalize(HifAmdHdl h, int64_t max_nrhs) {
   API_BEGIN
-  DISPATCH(ENG_D->finalize(max_nrhs), ENG_Z->finalize(max_nrhs))
+  visit(h, [&](auto &E) { E.finalize(max_nrhs); });
   API_END
 }
-
-#define QUERY(expr_d, expr_z) \
-  if (!h || !h->eng) return 0; \
-  return h->vt == HIFAMD_D ? (expr_d) : (expr_z);
-
 
 int hifamd_value_type(HifAmdHdl h) { return (h && h->eng) ? h->vt : -1; }
 int hifamd_device(HifAmdHdl h) {
   if (!h || !h->eng) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->device : ENG_Z->device;
+  return visit(h, [](auto &E) { return E.device; });
 }
-int64_t hifamd_nrows(HifAmdHdl h) { QUERY(q_nrows(ENG_D), q_nrows(ENG_Z)) }
-int64_t hifamd_levels(HifAmdHdl h) { QUERY(q_levels(ENG_D), q_levels(ENG_Z)) }
-int64_t hifamd_nnz(HifAmdHdl h) { QUERY(ENG_D->nnz_total(), ENG_Z->nnz_total()) }
-int64_t hifamd_schur_size(HifAmdHdl h) { QUERY(q_schur_size(ENG_D), q_schur_size(ENG_Z)) }
-int64_t hifamd_schur_rank(HifAmdHdl h) { QUERY(q_schur_rank(ENG_D), q_schur_rank(ENG_Z)) }
+int64_t hifamd_nrows(HifAmdHdl h) {
+  if (!h || !h->eng) return 0;
+  return visit(h, [](auto &E) { return q_nrows(&E); });
+}
+int64_t hifamd_levels(HifAmdHdl h) {
+  if (!h || !h->eng) return 0;
+  return visit(h, [](auto &E) { return q_levels(&E); });
+}
+int64_t hifamd_nnz(HifAmdHdl h) {
+  if (!h || !h->eng) return 0;
+  return visit(h, [](auto &E) { return E.nnz_total(); });
+}
+int64_t hifamd_schur_size(HifAmdHdl h) {
+  if (!h || !h->eng) return 0;
+  return visit(h, [](auto &E) { return q_schur_size(&E); });
+}
+int64_t hifamd_schur_rank(HifAmdHdl h) {
+  if (!h || !h->eng) return 0;
+  return visit(h, [](auto &E) { return q_schur_rank(&E); });
+}
 
 int hifamd_launch_map(HifAmdHdl h, int32_t *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->launch_map(out, cap) : ENG_Z->launch_map(out, cap);
+  return visit(h, [&](auto &E) { return E.launch_map(out, cap); });
 }
 int hifamd_kernel_census(HifAmdHdl h, int32_t *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;
-  const bool fin = h->vt == HIFAMD_D ? ENG_D->finalized : ENG_Z->finalized;
-  if (!fin) return 0;
-  return h->vt == HIFAMD_D ? ENG_D->kernel_census(out, cap) : ENG_Z->kernel_census(out, cap);
+  return visit(h, [&](auto &E) { return E.finalized ? E.kernel_census(out, cap) : 0; });
 }
 const char *hifamd_kernel_family_name(int family) {
   return (family >= 0 && family < hifamd::KF_COUNT) ? hifamd::kFamilyNames[family] : nullptr;
 }
 int hifamd_level_stats(HifAmdHdl h, int level, double *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->level_stats(level, out, cap) : ENG_Z->level_stats(level, out, cap);
+  return visit(h, [&](auto &E) { return E.level_stats(level, out, cap); });
 }
 int hifamd_stats_ext(HifAmdHdl h, double *out, int cap) {
   if (!h || !h->eng || (cap > 0 && !out)) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->stats_ext(out, cap) : ENG_Z->stats_ext(out, cap);
+  return visit(h, [&](auto &E) { return E.stats_ext(out, cap); });
 }
 
 HifAmdStatus hifamd_stats(HifAmdHdl h, double *stats16) {
   API_BEGIN
   if (!stats16) throw Error(HIFAMD_NULL_OBJ, "NULL stats array");
-  DISPATCH(ENG_D->stats(stats16), ENG_Z->stats(stats16))
+  visit(h, [&](auto &E) { E.stats(stats16); });
   API_END
 }
 
 
 HifAmdStatus hifamd_level_schedule(HifAmdHdl h, int level, int which, int64_t *nwf, int32_t *order, int64_t *wf_ptr) {
   API_BEGIN
-  DISPATCH(do_schedule(ENG_D, level, which, nwf, order, wf_ptr), do_schedule(ENG_Z, level, which, nwf, order, wf_ptr))
+  visit(h, [&](auto &E) { do_schedule(&E, level, which, nwf, order, wf_ptr); });
   API_END
 }
 
 HifAmdStatus hifamd_solve(HifAmdHdl h, const void *b, void *x, int64_t rank) {
   API_BEGIN
-  DISPATCH(ENG_D->solve_host((const double *)b, 1, (double *)x, 1, 1, rank),
-           ENG_Z->solve_host((const zdouble *)b, 1, (zdouble *)x, 1, 1, rank))
+  visit(h, [&](auto &E) { E.solve_host(E.val(b), 1, E.val(x), 1, 1, rank); });
   API_END
 }
 
 HifAmdStatus hifamd_solve_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int64_t rank) {
   API_BEGIN
-  DISPATCH(ENG_D->solve_host((const double *)B, ldb, (double *)X, ldx, nrhs, rank),
-           ENG_Z->solve_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rank))
+  visit(h, [&](auto &E) { E.solve_host(E.val(B), ldb, E.val(X), ldx, nrhs, rank); });
   API_END
 }
 
 HifAmdStatus hifamd_solve_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                     int64_t rank, void *stream) {
   API_BEGIN
-  DISPATCH(ENG_D->solve_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rank, (hipStream_t)stream),
-           ENG_Z->solve_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rank, (hipStream_t)stream))
+  visit(h, [&](auto &E) { E.solve_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rank, (hipStream_t)stream); });
   API_END
 }
 
 HifAmdStatus hifamd_set_matrix(HifAmdHdl h, int64_t n, const int64_t *indptr, const int32_t *indices, const void *vals) {
   API_BEGIN
-  DISPATCH(ENG_D->set_matrix(n, indptr, indices, (const double *)vals),
-           ENG_Z->set_matrix(n, indptr, indices, (const zdouble *)vals))
+  visit(h, [&](auto &E) { E.set_matrix(n, indptr, indices, E.val(vals)); });
   API_END
 }
 
 HifAmdStatus hifamd_spmv_batch_dev(HifAmdHdl h, const void *dX, int64_t ldx, void *dY, int64_t ldy, int64_t nrhs,
                                    void *stream) {
   API_BEGIN
-  DISPATCH(ENG_D->spmv_dev((const double *)dX, ldx, (double *)dY, ldy, nrhs, (hipStream_t)stream),
-           ENG_Z->spmv_dev((const cplx *)dX, ldx, (cplx *)dY, ldy, nrhs, (hipStream_t)stream))
+  visit(h, [&](auto &E) { E.spmv_dev(E.dev(dX), ldx, E.dev(dY), ldy, nrhs, (hipStream_t)stream); });
   API_END
 }
 
 HifAmdStatus hifamd_hifir_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int nirs,
                                 const double *betas, int64_t rank, int *ir_status) {
   API_BEGIN
-  DISPATCH(ENG_D->hifir_host((const double *)B, ldb, (double *)X, ldx, nrhs, nirs, betas, rank, ir_status),
-           ENG_Z->hifir_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, nirs, betas, rank, ir_status))
+  visit(h, [&](auto &E) { E.hifir_host(E.val(B), ldb, E.val(X), ldx, nrhs, nirs, betas, rank, ir_status); });
   API_END
 }
 
 HifAmdStatus hifamd_hifir_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                     int nirs, const double *betas, int64_t rank, int *ir_status) {
   API_BEGIN
-  DISPATCH(ENG_D->hifir_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, nirs, betas, rank, ir_status),
-           ENG_Z->hifir_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, nirs, betas, rank, ir_status))
+  visit(h, [&](auto &E) { E.hifir_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, nirs, betas, rank, ir_status); });
   API_END
 }
 
@@ -4690,13 +4533,11 @@ HifAmdStatus hifamd_apply_batch(HifAmdHdl h, HifAmdOp op, const void *B, int64_t
   const bool prod = (op == HIFAMD_M || op == HIFAMD_MH);
   if (rank == -2) rank = (prod || nirs > 1) ? -1 : 0;  // LHF_DEFAULT_RANK, libhifir.cpp:453-455
   if (prod) {
-    DISPATCH(ENG_D->for_op(op).prod_host((const double *)B, ldb, (double *)X, ldx, nrhs, rank),
-             ENG_Z->for_op(op).prod_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rank))
+    visit(h, [&](auto &E) { E.for_op(op).prod_host(E.val(B), ldb, E.val(X), ldx, nrhs, rank); });
     if (ir_status)
       for (int64_t c = 0; c < nrhs; ++c) ir_status[2 * c] = 1, ir_status[2 * c + 1] = -1;
   } else {
-    DISPATCH(ENG_D->for_op(op).hifir_host((const double *)B, ldb, (double *)X, ldx, nrhs, nirs, betas, rank, ir_status),
-             ENG_Z->for_op(op).hifir_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, nirs, betas, rank, ir_status))
+    visit(h, [&](auto &E) { E.for_op(op).hifir_host(E.val(B), ldb, E.val(X), ldx, nrhs, nirs, betas, rank, ir_status); });
   }
   API_END
 }
@@ -4706,24 +4547,21 @@ HifAmdStatus hifamd_apply_batch_dev(HifAmdHdl h, HifAmdOp op, const void *dB, in
   API_BEGIN
   const int kind = (op == HIFAMD_M || op == HIFAMD_MH) ? 1 : 0;
   if (rank == -2) rank = kind ? -1 : 0;
-  DISPATCH(ENG_D->for_op(op).solve_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rank, (hipStream_t)stream, kind),
-           ENG_Z->for_op(op).solve_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rank, (hipStream_t)stream, kind))
+  visit(h, [&](auto &E) { E.for_op(op).solve_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rank, (hipStream_t)stream, kind); });
   API_END
 }
 
 HifAmdStatus hifamd_gmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int restart,
                                 double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->gmres_host((const double *)B, ldb, (double *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters),
-           ENG_Z->gmres_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.gmres_host(E.val(B), ldb, E.val(X), ldx, nrhs, restart, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_gmres_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                     int restart, double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->gmres_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, restart, rtol, maxit, rank, flags, iters),
-           ENG_Z->gmres_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, restart, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.gmres_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, restart, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
@@ -4731,30 +4569,32 @@ HifAmdStatus hifamd_set_residual_precision(HifAmdHdl h, int mode) {
   API_BEGIN
   if (mode != HIFAMD_RESID_WORKING && mode != HIFAMD_RESID_COMPENSATED)
     throw Error(HIFAMD_MISMATCHED_SIZES, "residual precision: HIFAMD_RESID_WORKING or HIFAMD_RESID_COMPENSATED");
-  DISPATCH(ENG_D->set_resid_mode(mode), ENG_Z->set_resid_mode(mode))
+  visit(h, [&](auto &E) { E.set_resid_mode(mode); });
   API_END
 }
 
 int hifamd_residual_precision(HifAmdHdl h) {
   if (!h || !h->eng) return -1;
-  return h->vt == HIFAMD_D ? ENG_D->resid_mode : ENG_Z->resid_mode;
+  return visit(h, [](auto &E) { return E.resid_mode; });
 }
 
 HifAmdStatus hifamd_residual_batch(HifAmdHdl h, HifAmdOp op, const void *B, int64_t ldb, const void *X, int64_t ldx, void *R,
                                    int64_t ldr, int64_t nrhs, int mode) {
   API_BEGIN
-  DISPATCH(residual_pre(ENG_D, op, mode), residual_pre(ENG_Z, op, mode))
-  DISPATCH(ENG_D->for_op(op).residual_host((const double *)B, ldb, (const double *)X, ldx, (double *)R, ldr, nrhs, mode),
-           ENG_Z->for_op(op).residual_host((const zdouble *)B, ldb, (const zdouble *)X, ldx, (zdouble *)R, ldr, nrhs, mode))
+  visit(h, [&](auto &E) {
+    residual_pre(&E, op, mode);
+    E.for_op(op).residual_host(E.val(B), ldb, E.val(X), ldx, E.val(R), ldr, nrhs, mode);
+  });
   API_END
 }
 
 HifAmdStatus hifamd_residual_batch_dev(HifAmdHdl h, HifAmdOp op, const void *dB, int64_t ldb, const void *dX, int64_t ldx,
                                        void *dR, int64_t ldr, int64_t nrhs, int mode, void *stream) {
   API_BEGIN
-  DISPATCH(residual_pre(ENG_D, op, mode), residual_pre(ENG_Z, op, mode))
-  DISPATCH(ENG_D->for_op(op).residual_dev((const double *)dB, ldb, (const double *)dX, ldx, (double *)dR, ldr, nrhs, mode, (hipStream_t)stream),
-           ENG_Z->for_op(op).residual_dev((const cplx *)dB, ldb, (const cplx *)dX, ldx, (cplx *)dR, ldr, nrhs, mode, (hipStream_t)stream))
+  visit(h, [&](auto &E) {
+    residual_pre(&E, op, mode);
+    E.for_op(op).residual_dev(E.dev(dB), ldb, E.dev(dX), ldx, E.dev(dR), ldr, nrhs, mode, (hipStream_t)stream);
+  });
   API_END
 }
 
@@ -4762,8 +4602,10 @@ HifAmdStatus hifamd_gmres_ir_batch(HifAmdHdl h, const void *B, int64_t ldb, void
                                    double rtol, double inner_rtol, int max_outer, int inner_maxit, int64_t rank, int *flags,
                                    int *outer, int *iters, double *relres) {
   API_BEGIN
-  DISPATCH(ENG_D->gmres_ir_host((const double *)B, ldb, (double *)X, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres),
-           ENG_Z->gmres_ir_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres))
+  visit(h, [&](auto &E) {
+    E.gmres_ir_host(E.val(B), ldb, E.val(X), ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters,
+                    relres);
+  });
   API_END
 }
 
@@ -4771,48 +4613,45 @@ HifAmdStatus hifamd_gmres_ir_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb,
                                        int restart, double rtol, double inner_rtol, int max_outer, int inner_maxit,
                                        int64_t rank, int *flags, int *outer, int *iters, double *relres) {
   API_BEGIN
-  DISPATCH(ENG_D->gmres_ir_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres),
-           ENG_Z->gmres_ir_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters, relres))
+  visit(h, [&](auto &E) {
+    E.gmres_ir_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, restart, rtol, inner_rtol, max_outer, inner_maxit, rank, flags, outer, iters,
+                   relres);
+  });
   API_END
 }
 
 HifAmdStatus hifamd_fgmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int restart,
                                  double rtol, int maxit, int64_t rank, int *flags, int *iters, int *sweeps) {
   API_BEGIN
-  DISPATCH(ENG_D->gmres_host((const double *)B, ldb, (double *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps),
-           ENG_Z->gmres_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps))
+  visit(h, [&](auto &E) { E.gmres_host(E.val(B), ldb, E.val(X), ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps); });
   API_END
 }
 
 HifAmdStatus hifamd_pcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, double rtol,
                               int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->pcg_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->pcg_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.pcg_host(E.val(B), ldb, E.val(X), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                   double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->pcg_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->pcg_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.pcg_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_bicgstab_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs,
                                    double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->bicgstab_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->bicgstab_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.bicgstab_host(E.val(B), ldb, E.val(X), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_bicgstab_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                        double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->bicgstab_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->bicgstab_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.bicgstab_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
@@ -4820,8 +4659,7 @@ HifAmdStatus hifamd_idrs_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X,
                                const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank, int *flags,
                                int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->idrs_host((const double *)B, ldb, (double *)X, ldx, nrhs, s, (const double *)P, ldp, seed, rtol, maxit, rank, flags, iters),
-           ENG_Z->idrs_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, s, (const zdouble *)P, ldp, seed, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.idrs_host(E.val(B), ldb, E.val(X), ldx, nrhs, s, E.val(P), ldp, seed, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
@@ -4829,31 +4667,29 @@ HifAmdStatus hifamd_idrs_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, voi
                                    const void *P, int64_t ldp, uint64_t seed, double rtol, int maxit, int64_t rank,
                                    int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->idrs_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, s, (const double *)P, ldp, seed, rtol, maxit, rank, flags, iters),
-           ENG_Z->idrs_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, s, (const zdouble *)P, ldp, seed, rtol, maxit, rank, flags, iters))
+  // (the shadow block P is a host array on both entries)
+  visit(h, [&](auto &E) { E.idrs_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, s, E.val(P), ldp, seed, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_sqmr_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, double rtol,
                                int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->sqmr_host((const double *)B, ldb, (double *)X, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->sqmr_host((const zdouble *)B, ldb, (zdouble *)X, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.sqmr_host(E.val(B), ldb, E.val(X), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 HifAmdStatus hifamd_sqmr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                    double rtol, int maxit, int64_t rank, int *flags, int *iters) {
   API_BEGIN
-  DISPATCH(ENG_D->sqmr_dev((const double *)dB, ldb, (double *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters),
-           ENG_Z->sqmr_dev((const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rtol, maxit, rank, flags, iters))
+  visit(h, [&](auto &E) { E.sqmr_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rtol, maxit, rank, flags, iters); });
   API_END
 }
 
 int hifamd_hermitian(HifAmdHdl h) {
   if (!h || !h->eng) return -1;
   try {
-    const HermCheck &hc = h->vt == HIFAMD_D ? ENG_D->hermitian() : ENG_Z->hermitian();
+    const HermCheck &hc = visit(h, [](auto &E) -> const HermCheck & { return E.hermitian(); });
     if (hc.ok) return 1;
     set_err("level " + std::to_string(hc.level) + ": " + hc.what);
     return 0;
@@ -4866,23 +4702,21 @@ int hifamd_hermitian(HifAmdHdl h) {
 HifAmdStatus hifamd_time_apply(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                int64_t rank, int warmup, int reps, double *ms_avg) {
   API_BEGIN
-  DISPATCH(do_time(ENG_D, (const double *)dB, ldb, (double *)dX, ldx, nrhs, rank, warmup, reps, ms_avg),
-           do_time(ENG_Z, (const cplx *)dB, ldb, (cplx *)dX, ldx, nrhs, rank, warmup, reps, ms_avg))
+  visit(h, [&](auto &E) { do_time(&E, E.dev(dB), ldb, E.dev(dX), ldx, nrhs, rank, warmup, reps, ms_avg); });
   API_END
 }
 
 
 HifAmdStatus hifamd_sync(HifAmdHdl h) {
   API_BEGIN
-  DISPATCH(do_sync(ENG_D), do_sync(ENG_Z))
+  visit(h, [&](auto &E) { do_sync(&E); });
   API_END
 }
 
 HifAmdStatus hifamd_copy_columns_dev(HifAmdHdl h, const void *src, int64_t lds, int64_t ncols, void *dst, int64_t ldd,
                                      int64_t col0) {
   API_BEGIN
-  DISPATCH(do_copy_columns(ENG_D, sizeof(double), src, lds, ncols, dst, ldd, col0),
-           do_copy_columns(ENG_Z, 2 * sizeof(double), src, lds, ncols, dst, ldd, col0))
+  visit(h, [&](auto &E) { do_copy_columns(&E, src, lds, ncols, dst, ldd, col0); });
   API_END
 }
 

@@ -1604,6 +1604,30 @@ __global__ void __launch_bounds__(256) k_vec_op(int op, int64_t n, int nrhs, T *
   }
 }
 
+// masked axpy kernel for the bounded IR variant
+template <class D>
+__global__ void __launch_bounds__(256) k_masked_add(int64_t n, int nrhs, D *y, int64_t ldy, const D *x, int64_t ldx,
+                                                    const int *mask) {
+  const int64_t total = n * nrhs;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e / nrhs;
+    const int c = (int)(e - i * nrhs);
+    if (mask[c]) y[i * ldy + c] = vadd(y[i * ldy + c], x[i * ldx + c]);
+  }
+}
+
+// where mask[c]: y[:, c] = x[:, c], or 0 when x is NULL
+template <class D>
+__global__ void __launch_bounds__(256) k_masked_set(int64_t n, int nrhs, D *y, int64_t ldy, const D *x, int64_t ldx,
+                                                    const int *mask) {
+  const int64_t total = n * nrhs;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e / nrhs;
+    const int c = (int)(e - i * nrhs);
+    if (mask[c]) y[i * ldy + c] = x ? x[i * ldx + c] : vzero(D());
+  }
+}
+
 __device__ __forceinline__ double vabs2(double a) { return a * a; }
 __device__ __forceinline__ double vabs2(cplx a) { return a.x * a.x + a.y * a.y; }
 

@@ -302,6 +302,9 @@ VARIANTS = [
     V("gemm_waves=4", {"GEMM_WAVES": "4", "CD_ROWS": "0", "DENSE_BLOCK": "256"}, GOLD, need=("tri_gemm", "thin_update"), also=("blocks",)),
     V("gemm_waves=8", {"GEMM_WAVES": "8", "CD_ROWS": "0", "DENSE_BLOCK": "256"}, GOLD, need=("tri_gemm", "thin_update"), also=("blocks",)),
     V("gemm_waves=4-z", {"GEMM_WAVES": "4"}, ("kkt", "young", "blocksz"), need=("tri_gemm", "zcombine")),
+    # (several blocks per thin band on a complex handle: the blocks behind a band's first take their right-hand side from
+    # k_thin_update -- at the default block size every band of the complex fixtures is one block)
+    V("dense_block=256-z", {"DENSE_BLOCK": "256"}, ("kkt",), need=("tri_gemm", "thin_update", "zcombine")),
     # -- the band planner
     V("band_pipe=0", {"BAND_PIPE": "0"}, ("blocks", "leaves") + GOLD, need=("gather_scale",), deny=("trsv_band_p",)),
     V("band_pipe=0-flag-bands", _u(NOCD, {"BAND_PIPE": "0"}), ("blocks",) + GOLD, need=("trsv_band",), deny=("trsv_band_p",) + CT_ANY),
