@@ -701,22 +701,8 @@ class Engine : public EngineBase {
     if (device >= cnt) throw Error(HIFAMD_HIFIR_ERROR, "device ordinal out of range");
     HIP_OK(hipSetDevice(device));
     if (!stream) HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    if (sizeof(T) == sizeof(double) && band_opt.cd_rows > 0) {  // k_band_cd keeps a component in up to 128 KB of LDS
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<true, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_ct<false, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ct_lds_bytes(4)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes(false)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_us, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      for (int cw = 2; cw <= 4; ++cw)
-        for (int nch = 2; nch <= ls_max_chunks(cw); ++nch)
-          HIP_OK(hipFuncSetAttribute(ls_kernel(cw, nch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLsLdsMax));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cd_lds_bytes(true), 160 * 1024)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cd_lds_bytes(true), 160 * 1024)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cs<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cs_lds_bytes(true), 160 * 1024)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cs<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(cs_lds_bytes(true), 160 * 1024)));
-    }
+    for (const auto &e : band_lds_table())  // (a launch of up to 64 KB needs no raised limit)
+      if (e.second > 64 * 1024) HIP_OK(hipFuncSetAttribute(e.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.second));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
@@ -724,12 +710,6 @@ class Engine : public EngineBase {
     if (sizeof(T) != sizeof(double) && zop_flags) {
       HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
       HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
-    }
-    if (sizeof(T) != sizeof(double) && band_opt.cd_rows > 0) {
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cs_z<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(csz_lds_bytes(true, kCdOwnCap), 160 * 1024)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cs_z<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(csz_lds_bytes(true, kCdOwnCap), 160 * 1024)));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd_z<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes_z()));
-      HIP_OK(hipFuncSetAttribute((const void *)k_band_cd_z<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cd_lds_bytes_z()));
     }
   }
 
@@ -1641,6 +1621,8 @@ class Engine : public EngineBase {
   static FL no_fl() { return FL{IoPtr<const D>{nullptr, nullptr, 0}, 0, 0, nullptr, nullptr}; }
   typedef LastU<D> LU;
   static LU no_lu() { return LU{IoPtr<D>{nullptr, nullptr, 0}, 0, 0, nullptr, nullptr}; }
+  // the band's rows start at split[]: [ptr, split) is folded in by a prefix pass first (its own, or carried by the launch before)
+  static bool band_has_prefix(const DevCsr &M, size_t b) { return M.band_prefix[b] || (!M.band_fused.empty() && M.band_fused[b]); }
   // flp != NULL: S1 is fused into this L solve -- whichever kernel touches a row first reads s[p] * b[p] (kernels FirstL)
   template <bool LOWER>
   void launch_trsv(hipStream_t st, const DevLevel &L, int logR, int64_t &count, const FL *flp = nullptr, bool with_f = false,
@@ -1665,7 +1647,7 @@ class Engine : public EngineBase {
       // the kernel that touches a U row first starts it from w[i] / d[i] (the L kernels no longer write v).
       // pre: the band's rows start at split[] and [ptr, split) is folded in by a prefix pass first -- its own launch,
       // unless the previous band's launch carried it
-      int pre = (M.band_prefix[b] || fused) ? 1 : 0;
+      int pre = band_has_prefix(M, b) ? 1 : 0;
       // a component band split into a chip-wide prefix pass over ALL outside sources + the band kernel without its walk
       const bool cd_two = cd_split_min > 0 && logR == 6 && act_cols > 48 && !M.band_cd.empty() && M.band_cd[b] && !M.band_dense[b] &&
                           !M.cd_sparse && !(LOWER && with_f) && b < M.band_chunk_max.size() && M.band_chunk_max[b] >= cd_split_min &&
@@ -1766,7 +1748,6 @@ class Engine : public EngineBase {
   }
   // Out[rowmap] = G X on the matrix cores (kernels.hip.hpp k_top_gemm): 64-row tiles x K splits chosen so that one wave
   // of workgroups fills the chip; the splits' partial tiles are added in order by k_top_reduce
-  static constexpr size_t kTopGemmLds = 2 * 64 * 80 * sizeof(double);
   static constexpr int kTopGemmSplits = 8;
   static constexpr int kTopGemmTilesMax = 4096;  // arrival counters of the last-arriver reduction (rows / 64)
   void launch_top_gemm(hipStream_t st, int nt, const double *G, const double *X, const int32_t *rowmap, double *Out,
@@ -1862,32 +1843,10 @@ class Engine : public EngineBase {
                         L.v.as<double>(), count);
     }
   }
-  // one component-dense band (kernels.hip.hpp k_band_cd): real data, R = 64
-  // LDS of k_band_cd: the component's right-hand sides + row ids; sparse-own plans add the own nonzeros (value + source
-  // row, kCdOwnCap of them), the row offsets and the depth levels
-  // (dense-own plans: the rows are rounded up to a multiple of 32 -- the inverse product reads whole operand sets)
+  // rows the LDS layout of a component band kernel is built for (band_lds.hpp); dense-own plans: rounded up to a multiple
+  // of 32 -- the inverse product reads whole operand sets
   int32_t cd_lds_rows(bool sparse) const {
     return (int32_t)(sparse ? band_opt.cd_sparse_rows : ((band_opt.cd_rows + 31) & ~(int64_t)31));
-  }
-  size_t cd_lds_bytes(bool sparse, int32_t own_cap = kCdOwnCap) const {
-    const size_t rows = (size_t)cd_lds_rows(sparse);
-    size_t b = rows * 64 * sizeof(double) + ((rows + 1) & ~(size_t)1) * sizeof(int32_t);
-    if (sparse) b += (size_t)own_cap * (sizeof(double) + 1) + 260 * sizeof(uint16_t) + 264;
-    b += rows * (sizeof(double) + sizeof(int32_t)) + 8;  // fused S7 (LastU): output row and scale of every row
-    return b;
-  }
-  // LDS of k_band_cs (one 16-column slice of a component): right-hand sides [rows][16], per row two doubles and three
-  // int32 (pivot / scale, output scale, row id, input row, output row); sparse-own plans add the own nonzeros
-  size_t cs_lds_bytes(bool sparse, int32_t own_cap = kCdOwnCap) const {
-    const size_t rows = (size_t)cd_lds_rows(sparse);
-    size_t b = rows * 18 * sizeof(double) + rows * 3 * sizeof(int32_t);
-    if (sparse) b += (size_t)own_cap * (sizeof(double) + 1) + 260 * sizeof(uint16_t) + 264;
-    return b + 16;
-  }
-  // LDS of k_band_ct: right-hand sides [rows][16], per row two doubles and three int32, 17 strip offsets
-  size_t ct_lds_bytes(int nct) const {
-    const size_t rows = (size_t)cd_lds_rows(false);
-    return rows * (16 * (size_t)nct + 2) * sizeof(double) + rows * 3 * sizeof(int32_t) + 32 * sizeof(int32_t);
   }
   // v_tail = G c_tail (build_tail_operator); the product reads up to 31 rows behind c_tail: they lie inside the level's
   // arena (v follows w) and meet zero columns of the operand
@@ -1908,23 +1867,6 @@ class Engine : public EngineBase {
       return true;
     }
   }
-  // LDS of k_band_cs_z: two real planes [rows][16], per row two doubles and two int32; sparse-own plans add the own nonzeros
-  // (two doubles + a byte each), row offsets and depth levels
-  size_t csz_lds_bytes(bool sparse, int32_t own_cap) const {
-    const size_t rows = (size_t)(sparse ? band_opt.cd_sparse_rows : ((band_opt.cd_rows + 31) & ~(int64_t)31));
-    size_t b = rows * (2 * 16 + 2) * sizeof(double) + (((rows + 1) & ~(size_t)1) + rows) * sizeof(int32_t) + 16;
-    if (sparse) b += (size_t)own_cap * (2 * sizeof(double) + 2);
-    b += 260 * sizeof(uint16_t) + 264;  // (the kernel lays the row-offset / level arrays out in either variant)
-    b += rows * (sizeof(double) + sizeof(int32_t)) + 32;  // fused S7 (LastU): output scale and row of every row
-    return b;
-  }
-  // does the last U band of this level run through a kernel that can write the level's output itself (LastU)?  real data:
-  // every component band kernel; complex data: the slice kernel k_band_cs_z (sparse-own bands, narrow batches)
-  bool s7_kernel_ok(const DevLevel &L) const {
-    if (sizeof(T) == sizeof(double)) return true;
-    const int nslz = std::min(4, (act_cols + 15) / 16);
-    return L.U.cd_sparse || (ct_mode && L.U.ct_on) || (cs_mode && nslz < 4);
-  }
   // the instances of k_band_ls: CW = chunk rows / 16, NCH = chunks whose rows a wave holds in registers (CW * NCH <= kLsMaxSlots)
   static const void *ls_kernel(int cw, int nch) {
     typedef void (*K)(int32_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *, const uint16_t *, const int32_t *,
@@ -1935,28 +1877,31 @@ class Engine : public EngineBase {
                                 {k_band_ls<4, 2>, nullptr, nullptr}};
     return (cw < 2 || cw > 4 || nch < 2 || nch > 4) ? nullptr : (const void *)tab[cw - 2][nch - 2];
   }
-  static size_t us_lds_bytes(int32_t lds_black, int32_t own_cap) {  // k_band_us: black rows, own values, S7 scales, row ids, S7 rows, offsets, sources, levels
-    return (size_t)lds_black * 64 * sizeof(double) + (size_t)own_cap * sizeof(double) + 256 * sizeof(double) + 2 * 256 * sizeof(int32_t) +
-           260 * sizeof(uint16_t) + (size_t)own_cap + 264;
-  }
-  size_t cd_lds_bytes_z() const {  // complex: two real planes of the component's right-hand sides + row ids
-    const size_t rows = (size_t)band_opt.cd_rows;
-    return rows * 128 * sizeof(double) + ((rows + 1) & ~(size_t)1) * sizeof(int32_t);
-  }
+  // ---- component bands: ONE choice of kernel (choose_band), one launch site per kernel (launch_band_cd) ----------------
+  static constexpr size_t kBandLdsMax = 160 * 1024;  // a compute unit's LDS
+  struct BandChoice {
+    int family;        // census family (KF_BAND_*): names the kernel
+    unsigned grid, block;
+    size_t lds;        // bytes of dynamic LDS: the kernel's layout (band_lds.hpp) at the sizes below
+    int32_t lds_rows;  // rows the layout holds (k_band_us: black rows, k_band_ls: dependent rows)
+    int nsl = 1;       // column slices per component workgroup (the slice and tile kernels)
+    int nct = 1;       // k_band_ct: column tiles per workgroup
+    int32_t own_cap = 0, rptr_cap = 0;  // k_band_us / k_band_ls: own entries, row offsets of the layout
+    int cw = 0, nch = 0;                // k_band_ls: the instance
+  };
+  // does the family's kernel take LastU, i.e. can it write the level's output itself (the fused S7)?
+  static bool family_takes_last_u(int family) { return family != KF_BAND_CD_Z && family != KF_BAND_LS; }
+  // Which kernel runs component band `band` of M (workgroups [g0, g1)) in a launch with these facts, and its launch shape.
+  // Decides only; every condition of the choice is here and nowhere else.
   template <bool LOWER>
-  void launch_band_cd(hipStream_t st, const DevLevel &L, const DevCsr &M, int32_t g0, int32_t g1, int pre, int32_t ps0,
-                      int32_t ps1, unsigned extra, const FL &fl, bool with_f = false, const LU &lu = no_lu(), size_t band = 0,
-                      bool no_walk = false, RowSkip rs = RowSkip{nullptr}) {
+  BandChoice choose_band(const DevCsr &M, int32_t g0, int32_t g1, int pre, unsigned extra, bool with_f, size_t band,
+                         bool no_walk) const {
+    const unsigned n = (unsigned)(g1 - g0);
     if constexpr (std::is_same<T, double>::value) {
-      // LDS: the component's right-hand sides + its row ids (the attribute for > 64 KB is set in bind_device)
-      const size_t lds = cd_lds_bytes(M.cd_sparse, M.own_cap);
-      if (lds > 160 * 1024)  // (only with HIFIR_AMD_CD_SPARSE_ROWS / HIFIR_AMD_CD_ROWS raised beyond their defaults)
-        throw Error(HIFAMD_HIFIR_ERROR, "component band needs more than 160 KB of LDS: lower HIFIR_AMD_CD_SPARSE_ROWS / HIFIR_AMD_CD_ROWS");
       const int32_t lds_rows = cd_lds_rows(M.cd_sparse);
-      // one component per workgroup (the usual case): the kernel derives the component from blockIdx
-      const int32_t c0 = M.host_wg_grp_ptr[(size_t)g0], c1 = M.host_wg_grp_ptr[(size_t)g1];
-      const int32_t single_c0 = (c1 - c0 == g1 - g0) ? c0 : -1;
-      (void)pre;  // (the packed streams already start at split[] for a carried band, at ptr[] otherwise)
+      const size_t lds = BandCdLds(lds_rows, M.cd_sparse, M.own_cap).bytes();
+      if (lds > kBandLdsMax)  // (only with HIFIR_AMD_CD_SPARSE_ROWS / HIFIR_AMD_CD_ROWS raised beyond their defaults)
+        throw Error(HIFAMD_HIFIR_ERROR, "component band needs more than 160 KB of LDS: lower HIFIR_AMD_CD_SPARSE_ROWS / HIFIR_AMD_CD_ROWS");
       // column slices (k_band_cs): narrow batches always, full batches where the band is narrow
       const int nsl = std::min(4, (act_cols + 15) / 16);
       const bool fits = (int64_t)(g1 - g0) * nsl + 4 * (int64_t)extra < (1LL << 30);
@@ -1966,122 +1911,189 @@ class Engine : public EngineBase {
         const int ncols = (act_cols + 15) / 16;  // column tiles in use
         const int nct = (ncols == 4 && g1 - g0 > ct_wide4_wgs) ? 4 : ((ncols >= 2 && g1 - g0 > ct_wide_wgs) ? 2 : 1);
         const int nslc = (ncols + nct - 1) / nct;
-        const unsigned grid = (unsigned)(((g1 - g0 + 7) / 8) * 8 * nslc) + 4 * extra;
-        const bool ct_ahead = !(cd_dbg & kDbgCtPlain);
-        auto kct = ct_ahead ? (nct == 4 ? k_band_ct<LOWER, 4, true> : (nct == 2 ? k_band_ct<LOWER, 2, true> : k_band_ct<LOWER, 1, true>))
-                            : (nct == 4 ? k_band_ct<LOWER, 4, false> : (nct == 2 ? k_band_ct<LOWER, 2, false> : k_band_ct<LOWER, 1, false>));
-        tally(nct == 4 ? KF_BAND_CT4 : (nct == 2 ? KF_BAND_CT2 : KF_BAND_CT1));
-        hipLaunchKernelGGL(kct, dim3(grid), dim3(256), ct_lds_bytes(nct), st, g0,
-                           M.wg_grp_ptr.as<int32_t>(), M.ct_desc.as<int32_t>(), M.ptr.as<int32_t>(), M.split.as<int32_t>(),
-                           M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(), L.w.as<double>(),
-                           L.v.as<double>(), M.tinv.as<double>(), M.ct_sptr.as<int32_t>(), M.ct_src.as<int32_t>(),
-                           M.ct_coef.as<double>(), pre ? 0 : 1, (int32_t)(g1 - g0), (int32_t)nslc, ps0, ps1, single_c0, lds_rows,
-                           cd_dbg | (no_walk ? 1 : 0), fl, lu);
-        return;
+        return {nct == 4 ? KF_BAND_CT4 : (nct == 2 ? KF_BAND_CT2 : KF_BAND_CT1), (unsigned)(((g1 - g0 + 7) / 8) * 8 * nslc) + 4 * extra, 256,
+                BandCtLds(lds_rows, nct).bytes(), lds_rows, nslc, nct};
       }
       if (!LOWER && us_mode && M.cd_sparse && nsl == 4 && !pre && !extra && !with_f && band < M.us_band_ok.size() && M.us_band_ok[band] &&
           !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {  // black rows in LDS, sinks streamed: two workgroups per unit
         const int32_t own_cap2 = (M.us_band_own[band] + 63) & ~63;
         const int32_t lds_black = std::max(1, M.us_band_nbk[band]);
-        const size_t lds2 = us_lds_bytes(lds_black, own_cap2);
-        if (lds2 <= 160 * 1024) {
-          tally(KF_BAND_US);
-          hipLaunchKernelGGL(k_band_us, dim3((unsigned)(g1 - g0)), dim3(1024), lds2, st, M.us_band_c0[band], M.us_desc.as<int32_t>(),
-                             M.us_rowid.as<int32_t>(), M.us_oslot.as<int32_t>(), M.us_mptr.as<int32_t>(), M.us_mcol.as<int32_t>(),
-                             M.us_mval.as<double>(), M.us_own_val.as<double>(), M.us_own_src.as<uint8_t>(), M.us_own_rptr.as<uint16_t>(),
-                             M.us_own_lvl.as<uint8_t>(), L.d.as<double>(), (const double *)L.w.as<double>(), L.v.as<double>(), lds_black,
-                             own_cap2, fl, lu, M.cd_sparse ? rs : RowSkip{nullptr});
-          return;
-        }
+        const size_t lds2 = BandUsLds(lds_black, own_cap2).bytes();
+        if (lds2 <= kBandLdsMax) return {KF_BAND_US, n, 1024, lds2, lds_black, 1, 1, own_cap2};
       }
       if (LOWER && ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
           (!with_f || M.ls_fused) && !(cd_dbg & ~kDbgCtPlain) && !no_walk && !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {
         // dependent rows in LDS, sources through a chunk: two workgroups per unit
-        const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]), f = with_f ? 1 : 0;
+        const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]);
         const int32_t own_cap2 = std::max(64, (M.ls_band_own[band] + 63) & ~63), rptr_cap = (M.ls_band_rptr[band] + 3) & ~3;
         const int32_t lds_dep = std::max(1, M.ls_band_nd[band]);
         const size_t lds2 = ls_lds_bytes(lds_dep, 16 * cw, own_cap2, rptr_cap);
-        const void *kls = ls_kernel(cw, nch);
-        if (kls && lds2 <= kLsLdsMax) {
-          int32_t a_c0 = M.ls_band_c0[band], a_dep = lds_dep, a_own = own_cap2, a_rp = rptr_cap;
-          const int32_t *a_desc = M.ls_desc.as<int32_t>(), *a_rowid = M.ls_rowid.as<int32_t>(), *a_oslot = M.ls_oslot.as<int32_t>();
-          const int32_t *a_eb = M.ls_ebase[f].template as<int32_t>(), *a_ec = M.ls_ecol[f].template as<int32_t>();
-          const uint16_t *a_ew = M.ls_ewptr[f].template as<uint16_t>(), *a_or = M.ls_own_rptr.as<uint16_t>();
-          const double *a_ev = M.ls_eval[f].template as<double>(), *a_ov = M.ls_own_val.as<double>();
-          const uint8_t *a_et = M.ls_etag[f].template as<uint8_t>(), *a_os = M.ls_own_src.as<uint8_t>(), *a_ol = M.ls_own_lvl.as<uint8_t>();
-          double *a_w = L.w.as<double>();
-          FL a_fl = fl;
-          RowSkip a_rs = rs;
-          void *args[] = {&a_c0, &a_desc, &a_rowid, &a_oslot, &a_eb, &a_ew, &a_ec, &a_ev, &a_et, &a_ov, &a_os, &a_or, &a_ol, &a_w,
-                          &a_dep, &a_own, &a_rp, &a_fl, &a_rs};
-          tally(KF_BAND_LS);
-          HIP_OK(hipLaunchKernel(kls, dim3((unsigned)(g1 - g0)), dim3(1024), args, lds2, st));
-          return;
-        }
+        if (ls_kernel(cw, nch) && lds2 <= kLsLdsMax) return {KF_BAND_LS, n, 1024, lds2, lds_dep, 1, 1, own_cap2, rptr_cap, cw, nch};
       }
-      if (cs_mode && (nsl < 4 || g1 - g0 <= cs_max_wgs || (cs_sparse && M.cd_sparse)) && fits) {
-        auto kcs = M.cd_sparse ? k_band_cs<LOWER, true> : k_band_cs<LOWER, false>;
-        tally(M.cd_sparse ? KF_BAND_CS_SPARSE : KF_BAND_CS);
-        hipLaunchKernelGGL(kcs, dim3((unsigned)((g1 - g0) * nsl) + 4 * extra), dim3(256), cs_lds_bytes(M.cd_sparse, M.own_cap), st, g0,
+      if (cs_mode && (nsl < 4 || g1 - g0 <= cs_max_wgs || (cs_sparse && M.cd_sparse)) && fits)
+        return {M.cd_sparse ? KF_BAND_CS_SPARSE : KF_BAND_CS, n * (unsigned)nsl + 4 * extra, 256,
+                BandCsLds(lds_rows, M.cd_sparse, M.own_cap).bytes(), lds_rows, nsl};
+      return {M.cd_sparse ? KF_BAND_CD_SPARSE : KF_BAND_CD, n + extra, 1024, lds, lds_rows};
+    } else {
+      (void)pre, (void)with_f, (void)band, (void)no_walk;
+      if (extra) throw Error(HIFAMD_HIFIR_ERROR, "internal error: carried prefix on a complex handle");
+      const int nslz = std::min(4, (act_cols + 15) / 16);
+      const int32_t lds_rows = cd_lds_rows(M.cd_sparse);
+      if (ct_mode && M.ct_on && !M.cd_sparse)  // coefficient tiles (round 4): 16-column slices at every batch width
+        return {KF_BAND_CT_Z, n * (unsigned)nslz, 256, BandCtzLds(lds_rows).bytes(), lds_rows, nslz};
+      if (M.cd_sparse) {  // sparse-own components (round 4): 16-column slices at every batch width
+        const BandCszLds lay(lds_rows, true, M.own_cap);  // (lay.rows: even)
+        return {KF_BAND_CS_Z, n * (unsigned)nslz, 256, lay.bytes(), lay.rows, nslz, 1, M.own_cap};
+      }
+      if (cs_mode && nslz < 4 && (int64_t)(g1 - g0) * nslz < (1LL << 30))  // a narrow batch: only the slices it has
+        return {KF_BAND_CS_Z, n * (unsigned)nslz, 256, BandCszLds(lds_rows, false, 0).bytes(), lds_rows, nslz};
+      const int32_t rows = (int32_t)band_opt.cd_rows;  // (two planes of 64 columns: not rounded)
+      return {KF_BAND_CD_Z, n, 1024, BandCdzLds(rows).bytes(), rows};
+    }
+  }
+  // does the last U band of this level run through a kernel that can write the level's output itself (LastU)?  The band
+  // as launch_trsv<false> launches it: nothing carried behind the last band, no F product.  (launch_trsv may split a
+  // dense-own band of a real handle in two -- cd_two -- and then passes pre = 1 and no_walk: those two facts move the
+  // choice only between k_band_us / k_band_ls and the kernels behind them, never to or from a family without LastU)
+  bool s7_kernel_ok(const DevLevel &L) const {
+    const DevCsr &M = L.U;
+    const size_t b = M.band_wg_ptr.size() - 2;
+    return family_takes_last_u(
+        choose_band<false>(M, M.band_wg_ptr[b], M.band_wg_ptr[b + 1], band_has_prefix(M, b) ? 1 : 0, 0, false, b, false).family);
+  }
+  // every instance of the component band kernels with the most LDS the engine can ask of it: the layouts at the option
+  // caps, never more than a compute unit has (choose_band refuses such a band) -- bind_device raises the limit from this
+  std::vector<std::pair<const void *, size_t>> band_lds_table() const {
+    std::vector<std::pair<const void *, size_t>> t;
+    auto add = [&t](auto kernel, size_t bytes) { t.emplace_back((const void *)kernel, std::min(bytes, kBandLdsMax)); };
+    if (band_opt.cd_rows <= 0) return t;
+    const int32_t rd = cd_lds_rows(false), rs = cd_lds_rows(true);
+    if constexpr (std::is_same<T, double>::value) {
+      const size_t ct1 = BandCtLds(rd, 1).bytes(), ct2 = BandCtLds(rd, 2).bytes(), ct4 = BandCtLds(rd, 4).bytes();
+      add(k_band_ct<true, 1, true>, ct1), add(k_band_ct<false, 1, true>, ct1), add(k_band_ct<true, 1, false>, ct1), add(k_band_ct<false, 1, false>, ct1);
+      add(k_band_ct<true, 2, true>, ct2), add(k_band_ct<false, 2, true>, ct2), add(k_band_ct<true, 2, false>, ct2), add(k_band_ct<false, 2, false>, ct2);
+      add(k_band_ct<true, 4, true>, ct4), add(k_band_ct<false, 4, true>, ct4), add(k_band_ct<true, 4, false>, ct4), add(k_band_ct<false, 4, false>, ct4);
+      const size_t cdd = BandCdLds(rd, false, 0).bytes(), cds = BandCdLds(rs, true, kCdOwnCap).bytes();
+      add(k_band_cd<true, false>, cdd), add(k_band_cd<false, false>, cdd), add(k_band_cd<true, true>, cds), add(k_band_cd<false, true>, cds);
+      const size_t csd = BandCsLds(rd, false, 0).bytes(), css = BandCsLds(rs, true, kCdOwnCap).bytes();
+      add(k_band_cs<true, false>, csd), add(k_band_cs<false, false>, csd), add(k_band_cs<true, true>, css), add(k_band_cs<false, true>, css);
+      add(k_band_us, BandUsLds(rs, kCdOwnCap).bytes());
+      for (int cw = 2; cw <= 4; ++cw)
+        for (int nch = 2; nch <= ls_max_chunks(cw); ++nch)  // (choose_band takes the kernel up to kLsLdsMax)
+          t.emplace_back(ls_kernel(cw, nch), std::min(ls_lds_bytes(rs, 16 * cw, kCdOwnCap, (nch + 1) * rs + 4), kLsLdsMax));
+    } else {
+      add(k_band_ct_z<true>, BandCtzLds(rd).bytes()), add(k_band_ct_z<false>, BandCtzLds(rd).bytes());
+      const size_t csd = BandCszLds(rd, false, 0).bytes(), css = BandCszLds(rs, true, kCdOwnCap).bytes();
+      add(k_band_cs_z<true, false>, csd), add(k_band_cs_z<false, false>, csd), add(k_band_cs_z<true, true>, css), add(k_band_cs_z<false, true>, css);
+      const size_t cdz = BandCdzLds((int32_t)band_opt.cd_rows).bytes();
+      add(k_band_cd_z<true>, cdz), add(k_band_cd_z<false>, cdz);
+    }
+    return t;
+  }
+  template <bool LOWER>
+  void launch_band_cd(hipStream_t st, const DevLevel &L, const DevCsr &M, int32_t g0, int32_t g1, int pre, int32_t ps0,
+                      int32_t ps1, unsigned extra, const FL &fl, bool with_f = false, const LU &lu = no_lu(), size_t band = 0,
+                      bool no_walk = false, RowSkip rs = RowSkip{nullptr}) {
+    const BandChoice c = choose_band<LOWER>(M, g0, g1, pre, extra, with_f, band, no_walk);
+    const dim3 grid(c.grid), block(c.block);
+    const int first_u = pre ? 0 : 1;  // (the packed streams already start at split[] for a carried band, at ptr[] otherwise)
+    const int dbg = cd_dbg | (no_walk ? 1 : 0);
+    const int32_t n_band = g1 - g0;
+    tally(c.family);
+    if constexpr (std::is_same<T, double>::value) {
+      // one component per workgroup (the usual case): the kernel derives the component from blockIdx
+      const int32_t c0 = M.host_wg_grp_ptr[(size_t)g0], c1 = M.host_wg_grp_ptr[(size_t)g1];
+      const int32_t single_c0 = (c1 - c0 == g1 - g0) ? c0 : -1;
+      const RowSkip rsk = M.cd_sparse ? rs : RowSkip{nullptr};
+      switch (c.family) {
+      case KF_BAND_CT1:
+      case KF_BAND_CT2:
+      case KF_BAND_CT4: {
+        const bool ct_ahead = !(cd_dbg & kDbgCtPlain);
+        auto kct = ct_ahead ? (c.nct == 4 ? k_band_ct<LOWER, 4, true> : (c.nct == 2 ? k_band_ct<LOWER, 2, true> : k_band_ct<LOWER, 1, true>))
+                            : (c.nct == 4 ? k_band_ct<LOWER, 4, false> : (c.nct == 2 ? k_band_ct<LOWER, 2, false> : k_band_ct<LOWER, 1, false>));
+        hipLaunchKernelGGL(kct, grid, block, c.lds, st, g0,
+                           M.wg_grp_ptr.as<int32_t>(), M.ct_desc.as<int32_t>(), M.ptr.as<int32_t>(), M.split.as<int32_t>(),
+                           M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(), L.w.as<double>(),
+                           L.v.as<double>(), M.tinv.as<double>(), M.ct_sptr.as<int32_t>(), M.ct_src.as<int32_t>(),
+                           M.ct_coef.as<double>(), first_u, n_band, (int32_t)c.nsl, ps0, ps1, single_c0, c.lds_rows, dbg, fl, lu);
+        break;
+      }
+      case KF_BAND_US:
+        hipLaunchKernelGGL(k_band_us, grid, block, c.lds, st, M.us_band_c0[band], M.us_desc.as<int32_t>(),
+                           M.us_rowid.as<int32_t>(), M.us_oslot.as<int32_t>(), M.us_mptr.as<int32_t>(), M.us_mcol.as<int32_t>(),
+                           M.us_mval.as<double>(), M.us_own_val.as<double>(), M.us_own_src.as<uint8_t>(), M.us_own_rptr.as<uint16_t>(),
+                           M.us_own_lvl.as<uint8_t>(), L.d.as<double>(), (const double *)L.w.as<double>(), L.v.as<double>(), c.lds_rows,
+                           c.own_cap, fl, lu, rsk);
+        break;
+      case KF_BAND_LS: {
+        const int f = with_f ? 1 : 0;
+        int32_t a_c0 = M.ls_band_c0[band], a_dep = c.lds_rows, a_own = c.own_cap, a_rp = c.rptr_cap;
+        const int32_t *a_desc = M.ls_desc.as<int32_t>(), *a_rowid = M.ls_rowid.as<int32_t>(), *a_oslot = M.ls_oslot.as<int32_t>();
+        const int32_t *a_eb = M.ls_ebase[f].template as<int32_t>(), *a_ec = M.ls_ecol[f].template as<int32_t>();
+        const uint16_t *a_ew = M.ls_ewptr[f].template as<uint16_t>(), *a_or = M.ls_own_rptr.as<uint16_t>();
+        const double *a_ev = M.ls_eval[f].template as<double>(), *a_ov = M.ls_own_val.as<double>();
+        const uint8_t *a_et = M.ls_etag[f].template as<uint8_t>(), *a_os = M.ls_own_src.as<uint8_t>(), *a_ol = M.ls_own_lvl.as<uint8_t>();
+        double *a_w = L.w.as<double>();
+        FL a_fl = fl;
+        RowSkip a_rs = rs;
+        void *args[] = {&a_c0, &a_desc, &a_rowid, &a_oslot, &a_eb, &a_ew, &a_ec, &a_ev, &a_et, &a_ov, &a_os, &a_or, &a_ol, &a_w,
+                        &a_dep, &a_own, &a_rp, &a_fl, &a_rs};
+        HIP_OK(hipLaunchKernel(ls_kernel(c.cw, c.nch), grid, block, args, c.lds, st));
+        break;
+      }
+      case KF_BAND_CS:
+      case KF_BAND_CS_SPARSE:
+        hipLaunchKernelGGL((M.cd_sparse ? k_band_cs<LOWER, true> : k_band_cs<LOWER, false>), grid, block, c.lds, st, g0,
                            M.wg_grp_ptr.as<int32_t>(), (with_f ? M.f_desc : M.cd_desc).template as<int32_t>(), M.ptr.as<int32_t>(),
                            M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(),
                            L.w.as<double>(), L.v.as<double>(), M.tinv.as<double>(), (with_f ? M.f_col : M.mid_col).template as<int32_t>(),
                            (with_f ? M.f_val : M.mid_val).template as<double>(), (with_f ? M.f_lrow : M.mid_lrow).template as<uint8_t>(),
-                           pre ? 0 : 1, (int32_t)(g1 - g0), (int32_t)nsl, ps0, ps1, single_c0,
-                           lds_rows, M.own_cap, cd_dbg | (no_walk ? 1 : 0), fl, M.own_val.as<double>(), M.own_lsrc.as<uint8_t>(), M.own_rptr.as<uint16_t>(),
-                           M.own_lvl.as<uint8_t>(), lu, M.cd_sparse ? rs : RowSkip{nullptr});
-        return;
+                           first_u, n_band, (int32_t)c.nsl, ps0, ps1, single_c0, c.lds_rows, M.own_cap, dbg, fl, M.own_val.as<double>(),
+                           M.own_lsrc.as<uint8_t>(), M.own_rptr.as<uint16_t>(), M.own_lvl.as<uint8_t>(), lu, rsk);
+        break;
+      default:  // KF_BAND_CD, KF_BAND_CD_SPARSE
+        hipLaunchKernelGGL((M.cd_sparse ? k_band_cd<LOWER, true> : k_band_cd<LOWER, false>), grid, block, c.lds, st, g0,
+                           M.wg_grp_ptr.as<int32_t>(), (with_f ? M.f_desc : M.cd_desc).template as<int32_t>(), M.ptr.as<int32_t>(),
+                           M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(),
+                           L.w.as<double>(), L.v.as<double>(), M.tinv.as<double>(), (with_f ? M.f_col : M.mid_col).template as<int32_t>(),
+                           (with_f ? M.f_val : M.mid_val).template as<double>(), (with_f ? M.f_lrow : M.mid_lrow).template as<uint8_t>(),
+                           first_u, n_band, ps0, ps1, single_c0, c.lds_rows, M.own_cap, dbg, fl, M.own_val.as<double>(),
+                           M.own_lsrc.as<uint8_t>(), M.own_rptr.as<uint16_t>(), M.own_lvl.as<uint8_t>(), lu, rsk);
       }
-      auto kern = M.cd_sparse ? k_band_cd<LOWER, true> : k_band_cd<LOWER, false>;
-      tally(M.cd_sparse ? KF_BAND_CD_SPARSE : KF_BAND_CD);
-      hipLaunchKernelGGL(kern, dim3((unsigned)(g1 - g0) + extra), dim3(1024), lds, st, g0,
-                         M.wg_grp_ptr.as<int32_t>(), (with_f ? M.f_desc : M.cd_desc).template as<int32_t>(), M.ptr.as<int32_t>(),
-                         M.split.as<int32_t>(), M.col.as<int32_t>(), M.val.as<double>(), M.rowid.as<int32_t>(), L.d.as<double>(),
-                         L.w.as<double>(), L.v.as<double>(), M.tinv.as<double>(), (with_f ? M.f_col : M.mid_col).template as<int32_t>(),
-                         (with_f ? M.f_val : M.mid_val).template as<double>(), (with_f ? M.f_lrow : M.mid_lrow).template as<uint8_t>(),
-                         pre ? 0 : 1, (int32_t)(g1 - g0), ps0, ps1, single_c0,
-                         lds_rows, M.own_cap, cd_dbg | (no_walk ? 1 : 0), fl, M.own_val.as<double>(), M.own_lsrc.as<uint8_t>(), M.own_rptr.as<uint16_t>(),
-                         M.own_lvl.as<uint8_t>(), lu, M.cd_sparse ? rs : RowSkip{nullptr});
     } else {
-      (void)ps0, (void)ps1, (void)with_f;
-      if (extra) throw Error(HIFAMD_HIFIR_ERROR, "internal error: carried prefix on a complex handle");
-      const int nslz = std::min(4, (act_cols + 15) / 16);
-      if (ct_mode && M.ct_on && !M.cd_sparse) {  // coefficient tiles (round 4): 16-column slices at every batch width
-        const size_t rows = (size_t)((band_opt.cd_rows + 31) & ~(int64_t)31);
-        const size_t ldsz = rows * (2 * 16 + 3) * sizeof(double) + rows * 3 * sizeof(int32_t) + 32 * sizeof(int32_t);
-        tally(KF_BAND_CT_Z);
-        hipLaunchKernelGGL(k_band_ct_z<LOWER>, dim3((unsigned)((g1 - g0) * nslz)), dim3(256), ldsz, st, g0, M.wg_grp_ptr.as<int32_t>(),
+      (void)ps0, (void)ps1, (void)n_band, (void)rs;
+      switch (c.family) {
+      case KF_BAND_CT_Z:
+        hipLaunchKernelGGL(k_band_ct_z<LOWER>, grid, block, c.lds, st, g0, M.wg_grp_ptr.as<int32_t>(),
                            M.ct_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(),
-                           M.tinv.as<double>(), M.ct_sptr.as<int32_t>(), M.ct_src.as<int32_t>(), M.ct_coef.as<double>(), pre ? 0 : 1,
-                           (int32_t)nslz, (int32_t)rows, cd_dbg | (no_walk ? 1 : 0), fl, lu);
-        return;
+                           M.tinv.as<double>(), M.ct_sptr.as<int32_t>(), M.ct_src.as<int32_t>(), M.ct_coef.as<double>(), first_u,
+                           (int32_t)c.nsl, c.lds_rows, dbg, fl, lu);
+        break;
+      case KF_BAND_CS_Z:
+        if (M.cd_sparse)
+          hipLaunchKernelGGL((k_band_cs_z<LOWER, true>), grid, block, c.lds, st, g0,
+                             M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
+                             L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
+                             first_u, (int32_t)c.nsl, c.lds_rows, fl, c.own_cap, M.own_val.as<cplx>(), M.own_lsrc.as<uint8_t>(),
+                             M.own_rptr.as<uint16_t>(), M.own_lvl.as<uint8_t>(), lu);
+        else
+          hipLaunchKernelGGL((k_band_cs_z<LOWER, false>), grid, block, c.lds, st, g0,
+                             M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
+                             L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
+                             first_u, (int32_t)c.nsl, c.lds_rows, fl, 0, (const cplx *)nullptr, (const uint8_t *)nullptr,
+                             (const uint16_t *)nullptr, (const uint8_t *)nullptr, lu);
+        break;
+      default:  // KF_BAND_CD_Z
+        hipLaunchKernelGGL(k_band_cd_z<LOWER>, grid, block, c.lds, st, g0, M.wg_grp_ptr.as<int32_t>(),
+                           M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(),
+                           M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(), first_u,
+                           c.lds_rows, fl);
       }
-      if (M.cd_sparse) {  // sparse-own components (round 4): 16-column slices at every batch width
-        const int32_t rows = (int32_t)band_opt.cd_sparse_rows;
-        tally(KF_BAND_CS_Z);
-        hipLaunchKernelGGL((k_band_cs_z<LOWER, true>), dim3((unsigned)((g1 - g0) * nslz)), dim3(256), csz_lds_bytes(true, M.own_cap), st, g0,
-                           M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
-                           L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
-                           pre ? 0 : 1, (int32_t)nslz, rows, fl, M.own_cap, M.own_val.as<cplx>(), M.own_lsrc.as<uint8_t>(),
-                           M.own_rptr.as<uint16_t>(), M.own_lvl.as<uint8_t>(), lu);
-        return;
-      }
-      if (cs_mode && nslz < 4 && (int64_t)(g1 - g0) * nslz < (1LL << 30)) {  // a narrow batch: only the slices it has
-        const int32_t rows = (int32_t)((band_opt.cd_rows + 31) & ~(int64_t)31);
-        tally(KF_BAND_CS_Z);
-        hipLaunchKernelGGL((k_band_cs_z<LOWER, false>), dim3((unsigned)((g1 - g0) * nslz)), dim3(256), csz_lds_bytes(false, 0), st, g0,
-                           M.wg_grp_ptr.as<int32_t>(), M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(),
-                           L.v.as<cplx>(), M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(),
-                           pre ? 0 : 1, (int32_t)nslz, rows, fl, 0, (const cplx *)nullptr, (const uint8_t *)nullptr,
-                           (const uint16_t *)nullptr, (const uint8_t *)nullptr, lu);
-        return;
-      }
-      tally(KF_BAND_CD_Z);
-      hipLaunchKernelGGL(k_band_cd_z<LOWER>, dim3((unsigned)(g1 - g0)), dim3(1024), cd_lds_bytes_z(), st, g0, M.wg_grp_ptr.as<int32_t>(),
-                         M.cd_desc.as<int32_t>(), M.rowid.as<int32_t>(), L.d.as<cplx>(), L.w.as<cplx>(), L.v.as<cplx>(),
-                         M.tinv.as<double>(), M.mid_col.as<int32_t>(), M.mid_val.as<cplx>(), M.mid_lrow.as<uint8_t>(), pre ? 0 : 1,
-                         (int32_t)band_opt.cd_rows, fl);
     }
+    // a refused launch is an error, not a band that did not run (launches happen at capture, not at replay).  The call
+    // also returns and clears an earlier error of this thread that nobody looked at: that one is then reported here
+    HIP_OK(hipGetLastError());
   }
 
   // first: this is the level's FIRST solve with S1 fused -- the bands may leave out what build_row_flags marked

@@ -22,6 +22,8 @@
 #include <string>
 #include <vector>
 
+#include "band_lds.hpp"
+
 namespace hifamd {
 
 // Host-side parallel loop on plain std::thread (dynamic chunks off an atomic counter).  Deliberately NOT
@@ -1168,9 +1170,7 @@ constexpr size_t kLsLdsMax = 80 * 1024;  // two workgroups share a compute unit'
 constexpr int kLsMaxSlots = 9;           // source rows one wave holds in registers (kernel: CW * NCH <= 9 keeps it within 64 VGPRs without scratch)
 inline int ls_max_chunks(int cw) { return std::min(4, kLsMaxSlots / cw); }
 inline size_t ls_lds_bytes(int32_t lds_dep, int32_t chunk_rows, int32_t own_cap, int32_t rptr_cap) {
-  // dependent rows, chunk, own values | dependent row ids | offsets | own sources | levels
-  return ((size_t)lds_dep + (size_t)chunk_rows) * 64 * sizeof(double) + (size_t)own_cap * sizeof(double) +
-         (size_t)((lds_dep + 1) & ~1) * sizeof(int32_t) + (size_t)rptr_cap * sizeof(uint16_t) + (size_t)own_cap + 264;
+  return BandLsLds(lds_dep, chunk_rows, own_cap, rptr_cap).bytes();
 }
 inline bool ls_band_qualifies(const BandPlan &P, int64_t b) {
   if (!P.cd_sparse || P.band_cd.empty() || !P.band_cd[(size_t)b]) return false;

@@ -41,6 +41,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "band_lds.hpp"
+
 namespace hifamd {
 
 struct cplx {
@@ -3108,7 +3110,7 @@ __global__ void __launch_bounds__(1024) k_top_gemm(int nrows, int kvalid, int kp
   // and writes the rows out; release / acquire fences at agent scope carry the partials across the XCDs' L2s.
   constexpr int nct = NCT;
   constexpr int XS = 80;               // LDS row stride of the panel (doubles)
-  extern __shared__ double tg_lds[];   // two chunks of 64 panel rows: 2 x 64 x 80 doubles = 80 KB; reused for the reduction
+  extern __shared__ double tg_lds[];   // kTopGemmLds (band_lds.hpp): two chunks of 64 panel rows; reused for the reduction
   double (*xb)[64 * XS] = reinterpret_cast<double (*)[64 * XS]>(tg_lds);
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;     // 0..15
@@ -3584,6 +3586,58 @@ __device__ unsigned g_csprobe_cap = 0, g_csprobe_cnt = 0;
 #define HIFAMD_CSP_FLUSH(kind, a, b)
 #endif
 
+// ---- what the heads of the component-band kernels share ---------------------------------------------------------------
+// The array at byte offset `off` of the kernel's LDS layout (band_lds.hpp), reached from the array in front of it (`prev`,
+// at `prev_off`).  The step is taken in ELEMENTS of `prev`: the compiler then folds each scaled size into the uses, as it
+// does for pointer arithmetic, instead of keeping every byte offset in a scalar register from the kernel's head on
+// (k_band_ls and k_band_us have none to spare).  tests/cpp/band_lds_test.cpp checks that every step is a whole number
+// of elements.
+template <class E, class P>
+__device__ __forceinline__ E *lds_next(P *prev, int32_t prev_off, int32_t off) {
+  return reinterpret_cast<E *>(prev + (off - prev_off) / (int32_t)sizeof(P));
+}
+// the carried prefix of the NEXT band over the sources older than this band: the launch's extra workgroups, wave pw of nwaves
+template <bool LOWER>
+__device__ __forceinline__ void band_carried_prefix(int32_t pw, int32_t nwaves, int32_t ps0, int32_t ps1, const int32_t *__restrict__ ptr,
+                                                    const int32_t *__restrict__ split, const int32_t *__restrict__ col,
+                                                    const double *__restrict__ val, const int32_t *__restrict__ rowid,
+                                                    const double *__restrict__ d, double *w, double *v, int lane,
+                                                    const FirstL<double> &fl) {
+  const double *pf_bin = (LOWER && fl.on()) ? fl.bin.get() : nullptr;
+  trsv_stream_r64<double, 0, LOWER, true>(ps0 + pw, ps1, nwaves, ptr, split, col, val, nullptr, rowid, d, LOWER ? w : v, w, lane,
+                                          nullptr, 0, nullptr, true, nullptr, 0, 0, pf_bin, &fl);
+}
+// the components [c_first, c_last) of band workgroup bw.  single_c0 >= 0: every workgroup of this band owns exactly ONE
+// component, number single_c0 + bw (saves the dependent load of the workgroup's group range)
+__device__ __forceinline__ void band_components(int32_t single_c0, const int32_t *__restrict__ wg_grp_ptr, int32_t wg0, int32_t bw,
+                                                int32_t &c_first, int32_t &c_last) {
+  if (single_c0 >= 0) {
+    c_first = single_c0 + bw;
+    c_last = c_first + 1;
+  } else {
+    c_first = wg_grp_ptr[wg0 + bw];
+    c_last = wg_grp_ptr[wg0 + bw + 1];
+  }
+}
+// where a band's rows start from.  div_u: the kernel that touches a U row first starts it from w[i] / d[i]; first_l (S1
+// fused, FirstL): a band that touches its L rows first takes rhs[i] = s[p[i]] * b[p[i]] from the level's input
+template <class D>
+struct BandRhs {
+  bool div_u, first_l;
+  const D *rhs;
+  int64_t rstride;
+  __device__ __forceinline__ int col(int c, const FirstL<D> &fl) const { return first_l ? min(c, fl.nrhs - 1) : c; }
+};
+template <bool LOWER, class D>
+__device__ __forceinline__ BandRhs<D> band_rhs(int first_u, const FirstL<D> &fl, D *w, D *x) {
+  BandRhs<D> r;
+  r.div_u = !LOWER && first_u;
+  r.first_l = LOWER && first_u && fl.on();
+  r.rhs = r.div_u ? (const D *)w : (r.first_l ? fl.bin.get() : (const D *)x);
+  r.rstride = r.first_l ? fl.ldb : 64;
+  return r;
+}
+
 template <bool LOWER, bool SPARSE>
 __global__ void __launch_bounds__(1024) k_band_cd(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
                                                   const int32_t *__restrict__ cd_desc, const int32_t *__restrict__ ptr,
@@ -3605,42 +3659,31 @@ __global__ void __launch_bounds__(1024) k_band_cd(int32_t wg0, const int32_t *__
   if ((int32_t)blockIdx.x >= n_band) {  // carried prefix of the next band over the sources older than this band
     const int32_t pw = __builtin_amdgcn_readfirstlane(((int32_t)blockIdx.x - n_band) * nw + wave);
     if (dbg & 4) return;
-    const double *pf_bin = (LOWER && fl.on()) ? fl.bin.get() : nullptr;
-    trsv_stream_r64<double, 0, LOWER, true>(ps0 + pw, ps1, ((int32_t)gridDim.x - n_band) * nw, ptr, split, col, val, nullptr,
-                                            rowid, d, LOWER ? w : v, w, lane, nullptr, 0, nullptr, true, nullptr, 0, 0, pf_bin, &fl);
+    band_carried_prefix<LOWER>(pw, ((int32_t)gridDim.x - n_band) * nw, ps0, ps1, ptr, split, col, val, rowid, d, w, v, lane, fl);
     HIFAMD_CSP(6)
     HIFAMD_CSP_FLUSH(2 + (LOWER ? 0 : 4) + 16, n_band, 0)
     return;
   }
   double *x = LOWER ? w : v;
-  const bool div_u = !LOWER && first_u;
-  // S1 fused (FirstL): a band that touches its L rows first takes rhs[i] = s[p[i]] * b[p[i]] from the level's input
-  const bool first_l = LOWER && first_u && fl.on();
-  const double *rhs = div_u ? (const double *)w : (first_l ? fl.bin.get() : (const double *)x);
-  const int64_t rstride = first_l ? fl.ldb : 64;
-  const int rlane = first_l ? min(lane, fl.nrhs - 1) : lane;
-  // single_c0 >= 0: every workgroup of this band owns exactly ONE component, number single_c0 + blockIdx.x (saves the
-  // dependent load of the workgroup's group range)
+  const BandRhs<double> br = band_rhs<LOWER>(first_u, fl, w, x);
+  const bool div_u = br.div_u, first_l = br.first_l;
+  const double *rhs = br.rhs;
+  const int64_t rstride = br.rstride;
+  const int rlane = br.col(lane, fl);
   int32_t c_first, c_last;
-  if (single_c0 >= 0) {
-    c_first = single_c0 + (int32_t)blockIdx.x;
-    c_last = c_first + 1;
-  } else {
-    const int g = wg0 + (int)blockIdx.x;
-    c_first = wg_grp_ptr[g];
-    c_last = wg_grp_ptr[g + 1];
-  }
+  band_components(single_c0, wg_grp_ptr, wg0, (int32_t)blockIdx.x, c_first, c_last);
   const int kq = lane >> 4;
-  int32_t *cd_rowid = reinterpret_cast<int32_t *>(cd_tbuf + (size_t)lds_rows * 64);  // the component's row ids, for phase 2
+  const BandCdLds lay(lds_rows, SPARSE, own_cap);  // (own_cap: multiple of 64, host: the plan's maximum)
+  int32_t *cd_rowid = lds_next<int32_t>(cd_tbuf, lay.tb, lay.rowid);  // the component's row ids, for phase 2
   // SPARSE: the component's own nonzeros (value, local source row), their row offsets and the depth levels
-  double *ow_val = reinterpret_cast<double *>(cd_rowid + ((lds_rows + 1) & ~1));
-  uint8_t *ow_src = reinterpret_cast<uint8_t *>(ow_val + own_cap);  // (own_cap: multiple of 64, host: the plan's maximum)
-  uint16_t *ow_rptr = reinterpret_cast<uint16_t *>(ow_src + own_cap);
-  uint8_t *ow_lvl = reinterpret_cast<uint8_t *>(ow_rptr + 260);
+  double *ow_val = lds_next<double>(cd_rowid, lay.rowid, lay.ow_val);
+  uint8_t *ow_src = lds_next<uint8_t>(ow_val, lay.ow_val, lay.ow_src);
+  uint16_t *ow_rptr = lds_next<uint16_t>(ow_src, lay.ow_src, lay.ow_rptr);
+  uint8_t *ow_lvl = lds_next<uint8_t>(ow_rptr, lay.ow_rptr, lay.ow_lvl);
   // fused S7 (LastU): output row and scale of every row of the component, behind everything else
   const bool last_u = !LOWER && lu.on();
-  double *cd_ot = SPARSE ? reinterpret_cast<double *>(ow_lvl + 264) : reinterpret_cast<double *>(cd_rowid + ((lds_rows + 1) & ~1));
-  int32_t *cd_oi = reinterpret_cast<int32_t *>(cd_ot + lds_rows);
+  double *cd_ot = SPARSE ? lds_next<double>(ow_lvl, lay.ow_lvl, lay.ot) : lds_next<double>(ow_val, lay.ow_val, lay.ot);
+  int32_t *cd_oi = lds_next<int32_t>(cd_ot, lay.ot, lay.oi);
   double *yout = last_u ? lu.out.get() : nullptr;
   for (int32_t c = c_first; c < c_last; ++c) {
     const int32_t *dsc = cd_desc + (int64_t)c * 28;
@@ -3892,13 +3935,14 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
   constexpr int NW = 16;
   const int32_t *dsc = desc + (int64_t)(c0 + (int32_t)blockIdx.x) * 8;
   const int32_t s0 = dsc[0], nb = dsc[1], nbk = dsc[2], own0 = dsc[3], orp0 = dsc[4], lvl0 = dsc[5], nlvl = dsc[6];
-  double *ow_val = us_tb + (size_t)lds_black * 64;
-  double *s_ot = ow_val + own_cap;
-  int32_t *s_rowid = reinterpret_cast<int32_t *>(s_ot + 256);
-  int32_t *s_oi = s_rowid + 256;
-  uint16_t *ow_rptr = reinterpret_cast<uint16_t *>(s_oi + 256);
-  uint8_t *ow_src = reinterpret_cast<uint8_t *>(ow_rptr + 260);
-  uint8_t *ow_lvl = ow_src + own_cap;
+  const BandUsLds lay(lds_black, own_cap);
+  double *ow_val = lds_next<double>(us_tb, lay.tb, lay.ow_val);
+  double *s_ot = lds_next<double>(ow_val, lay.ow_val, lay.ot);
+  int32_t *s_rowid = lds_next<int32_t>(s_ot, lay.ot, lay.rowid);
+  int32_t *s_oi = lds_next<int32_t>(s_rowid, lay.rowid, lay.oi);
+  uint16_t *ow_rptr = lds_next<uint16_t>(s_oi, lay.oi, lay.ow_rptr);
+  uint8_t *ow_src = lds_next<uint8_t>(ow_rptr, lay.ow_rptr, lay.ow_src);
+  uint8_t *ow_lvl = lds_next<uint8_t>(ow_src, lay.ow_src, lay.ow_lvl);
   const bool last_u = lu.on();
   const bool from_b = rs.flag != nullptr;
   const double *bsrc = from_b ? fl.bin.get() : nullptr;
@@ -4061,12 +4105,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
   const int32_t comp = c0 + (int32_t)blockIdx.x;
   const int32_t *dsc = desc + (int64_t)comp * 8;
   const int32_t s0 = dsc[0], nb = dsc[1], nd = dsc[2], own0 = dsc[3], orp0 = dsc[4], lvl0 = dsc[5], nlvl = dsc[6], nch = dsc[7];
-  double *chunk = ls_tb + (size_t)lds_dep * 64;
-  double *ow_val = chunk + C * 64;
-  int32_t *s_rowid = reinterpret_cast<int32_t *>(ow_val + own_cap);
-  uint16_t *ow_rptr = reinterpret_cast<uint16_t *>(s_rowid + ((lds_dep + 1) & ~1));
-  uint8_t *ow_src = reinterpret_cast<uint8_t *>(ow_rptr + rptr_cap);
-  uint8_t *ow_lvl = ow_src + own_cap;
+  const BandLsLds lay(lds_dep, C, own_cap, rptr_cap);
+  double *chunk = lds_next<double>(ls_tb, lay.tb, lay.chunk);
+  double *ow_val = lds_next<double>(chunk, lay.chunk, lay.ow_val);
+  int32_t *s_rowid = lds_next<int32_t>(ow_val, lay.ow_val, lay.rowid);
+  uint16_t *ow_rptr = lds_next<uint16_t>(s_rowid, lay.rowid, lay.ow_rptr);
+  uint8_t *ow_src = lds_next<uint8_t>(ow_rptr, lay.ow_rptr, lay.ow_src);
+  uint8_t *ow_lvl = lds_next<uint8_t>(ow_src, lay.ow_src, lay.ow_lvl);
   const bool first_l = fl.on();
   const double *rhs = first_l ? fl.bin.get() : (const double *)w;
   const int64_t rstride = first_l ? fl.ldb : 64;
@@ -4324,9 +4369,7 @@ __global__ void __launch_bounds__(256) k_band_cs(int32_t wg0, const int32_t *__r
   if ((int32_t)blockIdx.x >= nbw) {  // carried prefix of the next band over the sources older than this band
     const int32_t pw = __builtin_amdgcn_readfirstlane(((int32_t)blockIdx.x - nbw) * 4 + wave);
     if (dbg & 4) return;
-    const double *pf_bin = (LOWER && fl.on()) ? fl.bin.get() : nullptr;
-    trsv_stream_r64<double, 0, LOWER, true>(ps0 + pw, ps1, ((int32_t)gridDim.x - nbw) * 4, ptr, split, col, val, nullptr,
-                                            rowid, d, LOWER ? w : v, w, lane, nullptr, 0, nullptr, true, nullptr, 0, 0, pf_bin, &fl);
+    band_carried_prefix<LOWER>(pw, ((int32_t)gridDim.x - nbw) * 4, ps0, ps1, ptr, split, col, val, rowid, d, w, v, lane, fl);
     HIFAMD_CSP(6)
     HIFAMD_CSP_FLUSH(2 + (LOWER ? 0 : 4), n_band, nsl)
     return;
@@ -4335,31 +4378,26 @@ __global__ void __launch_bounds__(256) k_band_cs(int32_t wg0, const int32_t *__r
   const int grp = lane >> 4, l16 = lane & 15, gq = wave * 4 + grp;  // lane group gq of 16 owns chunk gq
   const int cc = slice * 16 + l16;                                   // this lane's column of the 64-column arena
   double *x = LOWER ? w : v;
-  const bool div_u = !LOWER && first_u;
-  const bool first_l = LOWER && first_u && fl.on();
-  const double *rhs = div_u ? (const double *)w : (first_l ? fl.bin.get() : (const double *)x);
-  const int64_t rstride = first_l ? fl.ldb : 64;
-  const int rcol = first_l ? min(cc, fl.nrhs - 1) : cc;
+  const BandRhs<double> br = band_rhs<LOWER>(first_u, fl, w, x);
+  const bool div_u = br.div_u, first_l = br.first_l;
+  const double *rhs = br.rhs;
+  const int64_t rstride = br.rstride;
+  const int rcol = br.col(cc, fl);
   int32_t c_first, c_last;
-  if (single_c0 >= 0) {
-    c_first = single_c0 + bw;
-    c_last = c_first + 1;
-  } else {
-    c_first = wg_grp_ptr[wg0 + bw];
-    c_last = wg_grp_ptr[wg0 + bw + 1];
-  }
+  band_components(single_c0, wg_grp_ptr, wg0, bw, c_first, c_last);
   // LDS: right-hand sides [lds_rows][16], then per row: pivot / scale, output scale, row id, input row, output row;
   // sparse-own plans: the component's own nonzeros (value, local source), row offsets, depth levels
+  const BandCsLds lay(lds_rows, SPARSE, own_cap);
   double *tb = cs_buf;
-  double *s_hd = tb + (size_t)lds_rows * 16;
-  double *s_ot = s_hd + lds_rows;
-  double *ow_val = s_ot + lds_rows;
-  int32_t *s_rowid = reinterpret_cast<int32_t *>(ow_val + (SPARSE ? own_cap : 0));
-  int32_t *s_hp = s_rowid + lds_rows;
-  int32_t *s_oi = s_hp + lds_rows;
-  uint16_t *ow_rptr = reinterpret_cast<uint16_t *>(s_oi + lds_rows);
-  uint8_t *ow_src = reinterpret_cast<uint8_t *>(ow_rptr + 260);
-  uint8_t *ow_lvl = ow_src + own_cap;
+  double *s_hd = lds_next<double>(tb, lay.tb, lay.hd);
+  double *s_ot = lds_next<double>(s_hd, lay.hd, lay.ot);
+  double *ow_val = lds_next<double>(s_ot, lay.ot, lay.ow_val);
+  int32_t *s_rowid = lds_next<int32_t>(ow_val, lay.ow_val, lay.rowid);
+  int32_t *s_hp = lds_next<int32_t>(s_rowid, lay.rowid, lay.hp);
+  int32_t *s_oi = lds_next<int32_t>(s_hp, lay.hp, lay.oi);
+  uint16_t *ow_rptr = lds_next<uint16_t>(s_oi, lay.oi, lay.ow_rptr);
+  uint8_t *ow_src = lds_next<uint8_t>(ow_rptr, lay.ow_rptr, lay.ow_src);
+  uint8_t *ow_lvl = lds_next<uint8_t>(ow_src, lay.ow_src, lay.ow_lvl);
   const bool last_u = !LOWER && lu.on();
   double *yout = last_u ? lu.out.get() : nullptr;
   const int kq = grp;
@@ -4611,9 +4649,7 @@ k_band_ct(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
   if (car_first ? bx < 0 : bx >= nbp) {  // carried prefix of the next band over the sources older than this band
     const int32_t pw = __builtin_amdgcn_readfirstlane((car_first ? (int32_t)blockIdx.x : bx - nbp) * 4 + wave);
     if (dbg & 4) return;
-    const double *pf_bin = (LOWER && fl.on()) ? fl.bin.get() : nullptr;
-    trsv_stream_r64<double, 0, LOWER, true>(ps0 + pw, ps1, ncar * 4, ptr, split, col, val, nullptr,
-                                            rowid, d, LOWER ? w : v, w, lane, nullptr, 0, nullptr, true, nullptr, 0, 0, pf_bin, &fl);
+    band_carried_prefix<LOWER>(pw, ncar * 4, ps0, ps1, ptr, split, col, val, rowid, d, w, v, lane, fl);
     HIFAMD_CSP(6)
     HIFAMD_CSP_FLUSH(2 + (LOWER ? 0 : 4) + 32, n_band, nsl)
     return;
@@ -4624,10 +4660,10 @@ k_band_ct(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
   const int kq = lane >> 4, l16 = lane & 15;
   const int cc = slice * W + l16;  // this lane's column of the 64-column arena (first column tile)
   double *x = LOWER ? w : v;
-  const bool div_u = !LOWER && first_u;
-  const bool first_l = LOWER && first_u && fl.on();
-  const double *rhs = div_u ? (const double *)w : (first_l ? fl.bin.get() : (const double *)x);
-  const int64_t rstride = first_l ? fl.ldb : 64;
+  const BandRhs<double> br = band_rhs<LOWER>(first_u, fl, w, x);
+  const bool div_u = br.div_u, first_l = br.first_l;
+  const double *rhs = br.rhs;
+  const int64_t rstride = br.rstride;
   // The batch's input and output blocks arrive as pointers read from memory (IoPtr): the compiler takes them for generic
   // addresses, and ONE generic access anywhere in the kernel makes every later wait for a load a wait for ALL loads (a
   // generic access may return out of order) -- phase 2's counted waits would be lost.  Both blocks are device memory:
@@ -4637,22 +4673,17 @@ k_band_ct(int32_t wg0, const int32_t *__restrict__ wg_grp_ptr,
   const gdouble *x_g = (const gdouble *)x, *coef_g = (const gdouble *)ct_coef;
   const gint32 *src_g = (const gint32 *)ct_src;
   int32_t c_first, c_last;
-  if (single_c0 >= 0) {
-    c_first = single_c0 + bw;
-    c_last = c_first + 1;
-  } else {
-    c_first = wg_grp_ptr[wg0 + bw];
-    c_last = wg_grp_ptr[wg0 + bw + 1];
-  }
+  band_components(single_c0, wg_grp_ptr, wg0, bw, c_first, c_last);
   // LDS: right-hand sides [lds_rows][W], per row: pivot / scale, output scale, row id, input row, output row; the
   // component's strip -> tile offsets
+  const BandCtLds lay(lds_rows, NCT);
   double *tb = cs_buf;
-  double *s_hd = tb + (size_t)lds_rows * W;
-  double *s_ot = s_hd + lds_rows;
-  int32_t *s_rowid = reinterpret_cast<int32_t *>(s_ot + lds_rows);
-  int32_t *s_hp = s_rowid + lds_rows;
-  int32_t *s_oi = s_hp + lds_rows;
-  int32_t *s_sptr = s_oi + lds_rows;  // 17 entries (a component has at most 16 strips)
+  double *s_hd = lds_next<double>(tb, lay.tb, lay.hd);
+  double *s_ot = lds_next<double>(s_hd, lay.hd, lay.ot);
+  int32_t *s_rowid = lds_next<int32_t>(s_ot, lay.ot, lay.rowid);
+  int32_t *s_hp = lds_next<int32_t>(s_rowid, lay.rowid, lay.hp);
+  int32_t *s_oi = lds_next<int32_t>(s_hp, lay.hp, lay.oi);
+  int32_t *s_sptr = lds_next<int32_t>(s_oi, lay.oi, lay.sptr);  // 17 entries (a component has at most 16 strips)
   const bool last_u = !LOWER && lu.on();
   gdouble *yout = last_u ? (gdouble *)lu.out.get() : nullptr;
   constexpr int KU = 8;
@@ -4955,6 +4986,9 @@ __global__ void __launch_bounds__(256) k_band_cs_z(int32_t wg0, const int32_t *_
                                                    int32_t own_cap, const cplx *__restrict__ own_val,
                                                    const uint8_t *__restrict__ own_lsrc, const uint16_t *__restrict__ own_rptr,
                                                    const uint8_t *__restrict__ own_lvl, LastU<cplx> lu) {
+  // (LDS: BandCszLds in band_lds.hpp states this layout for the host; the pointers keep their own derivation here -- the
+  // code the compiler makes of this kernel moved with every other way to write it -- and tests/cpp/band_lds_test.cpp holds
+  // the two together.  lds_rows is even: the host rounds up)
   extern __shared__ double cs_buf[];
   double *t_re = cs_buf, *t_im = cs_buf + (size_t)lds_rows * 16;
   double *s_hdx = t_im + (size_t)lds_rows * 16, *s_hdy = s_hdx + lds_rows;
@@ -5209,26 +5243,27 @@ __global__ void __launch_bounds__(256) k_band_ct_z(int32_t wg0, const int32_t *_
                                                    int first_u, int32_t nsl, int32_t lds_rows, int dbg, FirstL<cplx> fl,
                                                    LastU<cplx> lu) {
   extern __shared__ double cs_buf[];
-  double *t_re = cs_buf, *t_im = cs_buf + (size_t)lds_rows * 16;
-  double *s_hdx = t_im + (size_t)lds_rows * 16, *s_hdy = s_hdx + lds_rows;
-  double *s_ot = s_hdy + lds_rows;
-  int32_t *s_rowid = reinterpret_cast<int32_t *>(s_ot + lds_rows);
-  int32_t *s_hp = s_rowid + lds_rows;
-  int32_t *s_oi = s_hp + lds_rows;
-  int32_t *s_sptr = s_oi + lds_rows;  // 17 entries
+  const BandCtzLds lay(lds_rows);
+  double *t_re = cs_buf, *t_im = lds_next<double>(t_re, lay.t_re, lay.t_im);
+  double *s_hdx = lds_next<double>(t_im, lay.t_im, lay.hdx), *s_hdy = lds_next<double>(s_hdx, lay.hdx, lay.hdy);
+  double *s_ot = lds_next<double>(s_hdy, lay.hdy, lay.ot);
+  int32_t *s_rowid = lds_next<int32_t>(s_ot, lay.ot, lay.rowid);
+  int32_t *s_hp = lds_next<int32_t>(s_rowid, lay.rowid, lay.hp);
+  int32_t *s_oi = lds_next<int32_t>(s_hp, lay.hp, lay.oi);
+  int32_t *s_sptr = lds_next<int32_t>(s_oi, lay.oi, lay.sptr);  // 17 entries
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int32_t bw = (int32_t)blockIdx.x / nsl, slice = (int32_t)blockIdx.x - bw * nsl;
   const int kq = lane >> 4, l16 = lane & 15;
   const int cc = slice * 16 + l16;
   cplx *x = LOWER ? w : v;
-  const bool div_u = !LOWER && first_u;
-  const bool first_l = LOWER && first_u && fl.on();
+  const BandRhs<cplx> br = band_rhs<LOWER>(first_u, fl, w, x);
+  const bool div_u = br.div_u, first_l = br.first_l;
+  const cplx *rhs = br.rhs;
+  const int64_t rstride = br.rstride;
   const bool last_u = !LOWER && lu.on();
   cplx *yout = last_u ? lu.out.get() : nullptr;
-  const cplx *rhs = div_u ? (const cplx *)w : (first_l ? fl.bin.get() : (const cplx *)x);
-  const int64_t rstride = first_l ? fl.ldb : 64;
-  const int rcol = first_l ? min(cc, fl.nrhs - 1) : cc;
+  const int rcol = br.col(cc, fl);
   const int32_t c_first = wg_grp_ptr[wg0 + bw], c_last = wg_grp_ptr[wg0 + bw + 1];
   for (int32_t c = c_first; c < c_last; ++c) {
     const int32_t *dsc = ct_desc + (int64_t)c * 28;
@@ -5399,6 +5434,7 @@ __global__ void __launch_bounds__(1024) k_band_cd_z(int32_t wg0, const int32_t *
                                                     const double *__restrict__ tinv, const int32_t *__restrict__ mid_col,
                                                     const cplx *__restrict__ mid_val, const uint8_t *__restrict__ mid_lrow,
                                                     int first_u, int32_t lds_rows, FirstL<cplx> fl) {
+  // (LDS: BandCdzLds in band_lds.hpp states this layout for the host; tests/cpp/band_lds_test.cpp holds the two together)
   extern __shared__ double cd_tbuf[];  // re[lds_rows][64], im[lds_rows][64], then lds_rows row ids
   double *t_re = cd_tbuf, *t_im = cd_tbuf + (size_t)lds_rows * 64;
   int32_t *cd_rowid = reinterpret_cast<int32_t *>(cd_tbuf + (size_t)lds_rows * 128);

@@ -328,12 +328,18 @@ VARIANTS = [
     V("cd_nnz=0", {"CD_NNZ": "0"}, ("blocks",) + GOLD),
     V("cd_nnz=200", {"CD_NNZ": "200"}, ("blocks",), need=("band_ct1",), bands=True),
     V("cd_rows=16", {"CD_ROWS": "16"}, ("blocks",), need=("band_ct1",), bands="band_workgroups"),
+    # (the largest components: the LDS layouts are built for 256 rows, and k_band_ct with two column tiles then needs more
+    # than 64 KB -- every instance gets its limit from the layouts, not from a list kept by hand)
+    V("cd_rows=240-ct_wide=0", {"CD_ROWS": "240", "CT_WIDE": "0"}, ("blocks",), need=("band_ct2",)),
+    V("cd_rows=240", {"CD_ROWS": "240"}, ("blocks",), need=("band_ct1",)),
     V("top_rows=0", {"TOP_ROWS": "0"}, ("blocks",), need=("tri_gemm",), count64={"top_gemm": 1}, also=GOLD),
     V("device_inverses=0", {"DEVICE_INVERSES": "0"}, ("deep", "blocks", "kkt", "blocksz"), same_bits=True),
     # -- the band planner, complex handles
     V("cd_rows_z=48", {"CD_ROWS_Z": "48"}, ("blocksz", "ladderz"), need=("band_cd_z",), need16=("band_cs_z",), also=("kkt", "young", "synthz")),
     V("cd_rows_z=16", {"CD_ROWS_Z": "16"}, ("blocksz",), need=("band_cd_z",), bands="band_workgroups"),
     V("cd_sparse_rows_z=64", {"CD_SPARSE_ROWS_Z": "64"}, ("synthz",), need=("band_cs_z",), bands="band_workgroups", also=("kkt", "young", "blocksz")),
+    # (an odd row count: the LDS layout of k_band_cs_z is built for the next even one, so that its own values stay 8-byte aligned)
+    V("cd_sparse_rows_z=63", {"CD_SPARSE_ROWS_Z": "63"}, ("synthz",), need=("band_cs_z",), also=("shapesz",)),
     V("cd_nnz_z", {"CD_NNZ_Z": "200"}, ("blocksz",), need=("band_cd_z",), bands="band_workgroups", also=("kkt", "young", "synthz")),
     V("ct_z", {"CT_Z": "1"}, ("blocksz",), need=("band_ct_z",), deny=("band_cd_z",), need16=("band_ct_z",), lower=("band_ct_z",),
       also=("kkt", "young", "synthz")),
