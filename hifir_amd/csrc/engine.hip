@@ -3100,7 +3100,7 @@ class Engine : public EngineBase {
   }
 
   // ---- what the lock-step Krylov solvers share -------------------------------------------------------
-  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG 4, BiCGSTAB 5, symmetric QMR 7,
+  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG and block CG 4, BiCGSTAB 5, symmetric QMR 7,
   // IDR(s) 2 s + 4), each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
   // That holds because no solver runs inside another one's tile: the null-space search calls gmres_dev between its own
   // local blocks, flexible GMRES calls the refinement (ir_r, ir_xk) and the projected PCG / QMR call apply_nsp
@@ -3160,15 +3160,15 @@ class Engine : public EngineBase {
   }
 
   // A device-pointer entry: the batch checks, the solver's own (check), then tile(b, x, nc, flags, iters, sweeps) on
-  // every 64 columns
+  // every 64 columns (block CG: every `width` columns)
   template <class Check, class Tile>
   void krylov_batch(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int *flags, int *iters, int *sweeps,
-                    Check check, Tile tile) {
+                    Check check, Tile tile, int width = 64) {
     check_batch(dB, ldb, dX, ldx, nrhs);
     check();
     HIP_OK(hipSetDevice(device));
-    for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
-      const int nc = (int)std::min<int64_t>(64, nrhs - c0);
+    for (int64_t c0 = 0; c0 < nrhs; c0 += width) {
+      const int nc = (int)std::min<int64_t>(width, nrhs - c0);
       auto at = [c0](int *p) { return p ? p + c0 : nullptr; };
       tile(dB + c0, dX + c0, nc, at(flags), at(iters), at(sweeps));
     }
@@ -3549,6 +3549,103 @@ class Engine : public EngineBase {
                 int *flags, int *iters) {
     staged(B, ldb, X, ldx, nrhs, false, [&] { pcg_check(maxit, rtol); },
            [&](const D *b, D *x) { pcg_dev(b, nrhs, x, nrhs, nrhs, rtol, maxit, rank, flags, iters); });
+  }
+
+  // ---- breakdown-free block CG: the columns of a tile share one block Krylov space ---------------------------
+  // Dubrulle's BCGrQ, preconditioned.  The block residual is kept factored, R = Q C with Q^H M^{-1} Q = I, and a pivoted
+  // Cholesky of the Gram shrinks the block where its columns become dependent (duplicate, zero or converged directions):
+  //   start: beta_j = ||b_j||, R = B diag(1 / beta) (zero and non-finite columns enter as exact zeros), Z = M^{-1} R,
+  //          G = R^H Z = S^H S (pivoted, rank r), E = I[:, piv] inv(S[:, piv]), Q = R E, P = Z E, C = S;
+  //   step:  T = A P, alpha = (P^H T)^{-1}, X += P alpha C diag(beta), Q -= T alpha, relres_j = sqrt(c_j^H Q^H Q c_j), test;
+  //          W = M^{-1} Q, G = Q^H W = S^H S (pivoted, rank r'), Q <- Q E, P <- W E + P S^H, C <- S C.
+  // Per step one batched apply, one SpMM, two Gram passes (k_bcg_gram), two row-local passes (k_bcg_xq, which also gives
+  // Q^H Q, and k_bcg_qp), three one-workgroup kernels (k_bcg_small) and ONE read-back, after the test.  The vectors are
+  // kr_vec[0..3] = Q, W, P, T at [n][nc]; the small matrices live beside the KrylovState (BcgState).  flags 0 converged /
+  // 1 breakdown or excluded / 2 reached maxit; the iteration count is the tile's.  ranks (may be null): the tile's rank
+  // after the start and during its last step.
+  void bcg_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, double deftol, int maxit, int64_t rank,
+                int *flags, int *iters, int *ranks) {
+    const int64_t n = lv[0]->n;
+    const size_t vec = (size_t)n * nc * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
+    const size_t part = std::max((size_t)kBcgBlocks * mat, (size_t)kCgBlocks * 64 * sizeof(D));
+    krylov_vectors(4, vec);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    D *Q = kr_vec[0].as<D>(), *W = kr_vec[1].as<D>(), *P = kr_vec[2].as<D>(), *Tm = kr_vec[3].as<D>(), *pt = ir_part.as<D>();
+    const size_t lds_pass = 2 * mat, lds_small = 2 * mat + 64 * sizeof(double) + 128 * sizeof(int);
+    if (lds_small > 64 * 1024 && !bcg_lds_raised) {  // (the small kernel's 65 KB; a complex handle's 128 KB)
+      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_xq<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
+      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_qp<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
+      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
+      bcg_lds_raised = true;
+    }
+    StreamWait wait{stream};
+    BcgState<D> S;
+    krylov_state(S, {{&S.C, 64}, {&S.E1, 64}, {&S.E2, 64}, {&S.G, 64}}, {&S.bnorm, &S.relres}, rtol, maxit);
+    S.deftol = deftol;
+    auto gram = [&](const D *a, const D *b) {  // S.G = a^H b
+      hipLaunchKernelGGL((k_bcg_gram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
+    };
+    auto small = [&](int mode, int k) {
+      hipLaunchKernelGGL((k_bcg_small<D>), dim3(1), dim3(256), lds_small, stream, mode, k, nc, S);
+    };
+    auto qp = [&] {  // Q <- Q E1, P <- W E1 + P E2
+      hipLaunchKernelGGL((k_bcg_qp<D>), dim3(kBcgBlocks), dim3(256), lds_pass, stream, n, nc, Q, (const D *)W, P, (const D *)S.E1,
+                         (const D *)S.E2);
+    };
+    vec_op(1, n, nc, Q, nc, dB, ldb, nullptr, 0);  // R = b (R lives in Q, Z in W)
+    if (nsp_k > 0) apply_nsp(Q, nc, nc, stream);  // projected, as PCG: R = P b, beta = ||P b||
+    hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, (const D *)Q, (int64_t)nc, (const D *)nullptr, pt);
+    hipLaunchKernelGGL((k_bcg_beta<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, S);
+    hipLaunchKernelGGL((k_bcg_norm<D>), dim3(vec_grid(n * nc)), dim3(256), 0, stream, n, nc, Q, (const double *)S.bnorm,
+                       (const int *)S.active);
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
+    HIP_OK(hipMemsetAsync(P, 0, vec, stream));
+    solve_dev((const D *)Q, nc, W, nc, nc, rank, nullptr);  // Z = M^{-1} R
+    gram(Q, W);
+    small(1, 0);
+    qp();  // Q = R E, P = Z E (E2 = 0)
+    HIP_OK(hipGetLastError());
+    for (int k = 1, go = krylov_active(S); k <= maxit && go > 0; ++k) {
+      spmv_dev((const D *)P, nc, Tm, nc, nc, nullptr);  // T = A P
+      gram(P, Tm);
+      small(2, k);  // alpha = (P^H T)^{-1}
+      hipLaunchKernelGGL((k_bcg_xq<D>), dim3(kBcgBlocks), dim3(256), lds_pass, stream, n, nc, dX, ldx, Q, (const D *)P,
+                         (const D *)Tm, (const D *)S.E1, (const D *)S.E2, pt);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
+      small(3, k);  // the residual test
+      if ((go = krylov_active(S)) == 0) break;
+      solve_dev((const D *)Q, nc, W, nc, nc, rank, nullptr);  // W = M^{-1} Q
+      gram(Q, W);
+      small(4, k);  // the next block: rank, E, S^H, C
+      qp();
+      HIP_OK(hipGetLastError());
+    }
+    krylov_result(S, nc, flags, iters);
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+  }
+  bool bcg_lds_raised = false;
+
+  void bcg_check(int block, double deftol, int maxit, double rtol) {
+    krylov_check("block CG", maxit, rtol);
+    hermitian_check("block CG", "GMRES", "a null-space filter");
+    if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
+    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < deftol < 1");
+  }
+  void bcg_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int block, double rtol, double deftol, int maxit,
+               int64_t rank, int *flags, int *iters, int *ranks) {
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { bcg_check(block, deftol, maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) {
+                   bcg_tile(b, ldb, x, ldx, nc, rtol, deftol, maxit, rank, fl, it, ranks ? ranks + 2 * ((b - dB) / block) : nullptr);
+                 },
+                 block >= 1 && block <= 64 ? block : 64);
+  }
+  void bcg_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int block, double rtol, double deftol, int maxit,
+                int64_t rank, int *flags, int *iters, int *ranks) {
+    staged(B, ldb, X, ldx, nrhs, false, [&] { bcg_check(block, deftol, maxit, rtol); },
+           [&](const D *b, D *x) { bcg_dev(b, nrhs, x, nrhs, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
   }
 
   // ---- right-preconditioned BiCGSTAB, batched over columns ----------------------------------------
@@ -4636,6 +4733,20 @@ HifAmdStatus hifamd_fgmres_batch(HifAmdHdl h, const void *B, int64_t ldb, void *
                                  double rtol, int maxit, int64_t rank, int *flags, int *iters, int *sweeps) {
   API_BEGIN
   visit(h, [&](auto &E) { E.gmres_host(E.val(B), ldb, E.val(X), ldx, nrhs, restart, rtol, maxit, rank, flags, iters, true, sweeps); });
+  API_END
+}
+
+HifAmdStatus hifamd_bcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int block,
+                              double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
+  API_BEGIN
+  visit(h, [&](auto &E) { E.bcg_host(E.val(B), ldb, E.val(X), ldx, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
+  API_END
+}
+
+HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
+                                  double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
+  API_BEGIN
+  visit(h, [&](auto &E) { E.bcg_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
   API_END
 }
 

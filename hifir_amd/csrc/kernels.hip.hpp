@@ -33,6 +33,8 @@
 //                    with k_cg_dot and k_cg_p)
 //   k_idr_comb / k_idr_gu / k_idr_finish / k_idr_pfill   device-resident IDR(s) (same reductions; with k_cg_dot, k_cg_xr,
 //                    k_bs_tr and, for P^H x, k_nsp_coef / k_nsp_finish)
+//   k_bcg_gram / k_bcg_sum / k_bcg_xq / k_bcg_qp / k_bcg_small / k_bcg_beta / k_bcg_norm   device-resident block CG: Grams and
+//                    row-local products on the f64 matrix cores, the small matrices in one workgroup (blockcg_small.hpp)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -42,6 +44,7 @@
 #include <type_traits>
 
 #include "band_lds.hpp"
+#include "blockcg_small.hpp"
 
 namespace hifamd {
 
@@ -5672,6 +5675,389 @@ __global__ void __launch_bounds__(256) k_block_inverse(const int32_t *__restrict
   }
   // largest entry of the block: positive doubles order like their bit patterns; NaN (all ones in the exponent) wins
   if (live) atomicMax(&growth_bits[q], (unsigned long long)__double_as_longlong(isnan(g) ? __builtin_nan("") : g));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident breakdown-free block CG (Dubrulle's BCGrQ, preconditioned) for a Hermitian positive-definite pair
+// (A, M), one tile of nc <= 64 columns in a shared block Krylov space (Engine::bcg_tile).  Vectors are [n][nc] contiguous;
+// a block of rank r < nc keeps its columns >= r exactly zero.  Three kinds of kernel:
+//   k_bcg_gram            partials of X^H Y, rows as the K dimension of v_mfma_f64_16x16x4_f64
+//   k_bcg_xq / k_bcg_qp   the two row-local passes: a 16-row strip of [n][nc] times coefficient matrices of at most 64 x 64
+//                         that every workgroup stages in LDS once
+//   k_bcg_small           one workgroup: Cholesky factors, inverses and every decision (blockcg_small.hpp, shared with the host)
+// Lane maps of the instruction: A: lane l holds A[i = l & 15][k = l >> 4]; B: B[k = l >> 4][j = l & 15]; C / D: col = l & 15,
+// row = (l >> 4) + 4 reg.  A complex handle runs the same kernels on its real planes: four instructions per tile pair into
+// a real and an imaginary accumulator.  Partials are summed in a fixed order (waves of a block in wave order, blocks in block
+// order by k_bcg_sum): no atomics, and the same inputs give the same bits.  Unlike k_cg_*, a column's bits DO depend on the
+// other columns of its tile: that is what a shared Krylov space means.
+// ---------------------------------------------------------------------------------------------
+constexpr int kBcgBlocks = 256;  // workgroups of 4 waves of every pass (one per compute unit) and partial matrices per Gram
+
+template <class T>
+struct BcgState : KrylovState {
+  // bnorm: beta = ||b|| per column; active: 1 for a column of the block (not zero, not excluded)
+  // ctl: [0] 1 while the tile runs, [1] rank after the start, [2] rank during the last step, [3] current rank
+  T *C, *E1, *E2, *G;  // [64][64] each: R = Q C | the two coefficient matrices of the next row pass | the summed Gram
+  double *relres;      // [64]  ||r|| / ||b|| at the last test (infinite before the first)
+  double deftol;
+};
+
+template <class T>
+struct BcgAcc;
+template <>
+struct BcgAcc<double> {
+  v4f64 re;
+};
+template <>
+struct BcgAcc<cplx> {
+  v4f64 re, im;
+};
+__device__ __forceinline__ void bcg_clear(BcgAcc<double> &c) { c.re = v4f64{0.0, 0.0, 0.0, 0.0}; }
+__device__ __forceinline__ void bcg_clear(BcgAcc<cplx> &c) { c.re = c.im = v4f64{0.0, 0.0, 0.0, 0.0}; }
+// c += A B for the operand values of this lane
+__device__ __forceinline__ void bcg_mma(BcgAcc<double> &c, double a, double b) {
+  c.re = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c.re, 0, 0, 0);
+}
+__device__ __forceinline__ void bcg_mma(BcgAcc<cplx> &c, cplx a, cplx b) {
+  c.re = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, c.re, 0, 0, 0);
+  c.re = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.y, c.re, 0, 0, 0);
+  c.im = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, c.im, 0, 0, 0);
+  c.im = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.x, c.im, 0, 0, 0);
+}
+__device__ __forceinline__ double bcg_get(const BcgAcc<double> &c, int reg) { return c.re[reg]; }
+__device__ __forceinline__ cplx bcg_get(const BcgAcc<cplx> &c, int reg) { return cplx{c.re[reg], c.im[reg]}; }
+
+// element (row, col) of an [n][nc] block, an exact zero outside it; the load itself is unconditional (a clamped address)
+template <class T>
+__device__ __forceinline__ T bcg_load(const T *__restrict__ x, int64_t n, int nc, int64_t row, int col) {
+  const bool ok = row < n && col < nc;
+  const T v = x[ok ? row * nc + col : 0];
+  return ok ? v : vzero(T());
+}
+
+// Adds the 4 x 4 accumulator tiles of the four waves of a block in wave order and writes the nt x nt tiles in use to
+// partial[blockIdx.x] ([64][64]).  lds: 64 x 64 values, free to use from the barrier this function starts with.
+template <class T>
+__device__ __forceinline__ void bcg_block_partial(BcgAcc<T> (&acc)[4][4], int nt, T *lds, T *__restrict__ partial) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  for (int w = 1; w < 4; ++w) {
+    __syncthreads();
+    if (wave == w) {
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) lds[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[ti][tj], reg);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const T v = lds[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci];
+            if constexpr (std::is_same<T, cplx>::value)
+              acc[ti][tj].re[reg] += v.x, acc[ti][tj].im[reg] += v.y;
+            else
+              acc[ti][tj].re[reg] += v;
+          }
+    }
+  }
+  if (wave != 0) return;
+  T *__restrict__ out = partial + (int64_t)blockIdx.x * 64 * 64;
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+      if (ti < nt && tj < nt) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) out[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[ti][tj], reg);
+      }
+}
+
+// partial[blockIdx.x] = the block's share of X^H Y: wave w of block b owns the row groups g = 4 b + w + k * 4 gridDim.x
+// (rows 4 g .. 4 g + 3, one K step of the instruction each)
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_gram(int64_t n, int nc, const T *__restrict__ X, const T *__restrict__ Y,
+                                                  T *__restrict__ partial /* [gridDim.x][64][64] */) {
+  __shared__ T lds[64 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  BcgAcc<T> acc[4][4];
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) bcg_clear(acc[ti][tj]);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  // (two row groups per turn, all their loads issued before the first product; a group past the last row loads zeros)
+  for (int64_t g = (int64_t)blockIdx.x * 4 + wave; 4 * g < n; g += 2 * stride) {
+    T a[2][4], b[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        a[u][t] = vconj(bcg_load(X, n, nc, 4 * (g + u * stride) + kq, 16 * t + ci));
+        b[u][t] = bcg_load(Y, n, nc, 4 * (g + u * stride) + kq, 16 * t + ci);
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (ti < nt && tj < nt) bcg_mma(acc[ti][tj], a[u][ti], b[u][tj]);
+  }
+  bcg_block_partial(acc, nt, lds, partial);
+}
+
+// G[i][j] = the partials of entry (i, j), i, j < m, in block order (bcg::sum_partials; one thread per entry)
+struct BcgGridTeam {
+  __device__ int rank() const { return blockIdx.x * blockDim.x + threadIdx.x; }
+  __device__ int size() const { return gridDim.x * blockDim.x; }
+  __device__ void sync() const {}
+};
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_sum(const T *__restrict__ partial, int nb, int m, T *__restrict__ G) {
+  bcg::sum_partials(partial, nb, m, G, BcgGridTeam{});
+}
+
+// stages the two 64 x 64 coefficient matrices of a row pass in LDS (e1 | e2)
+template <class T>
+__device__ __forceinline__ void bcg_stage(const T *__restrict__ E1, const T *__restrict__ E2, T *e1, T *e2) {
+  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) e1[e] = E1[e], e2[e] = E2[e];
+  __syncthreads();
+}
+
+// Step 3 in one pass over the rows: X += P E1 (E1 = alpha C diag(beta)), Q -= Tm E2 (E2 = alpha), and the block's share of
+// H = Q^H Q of the new Q.  A wave owns the 16-row strips 4 b + w + k * 4 gridDim.x; the new Q of a strip is, register by
+// register, already the operand of the Gram instruction (rows 4 reg .. 4 reg + 3 of the strip are one K step).
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_xq(int64_t n, int nc, T *__restrict__ X, int64_t ldx, T *__restrict__ Q,
+                                                const T *__restrict__ P, const T *__restrict__ Tm,
+                                                const T *__restrict__ E1, const T *__restrict__ E2,
+                                                T *__restrict__ partial /* [gridDim.x][64][64] */) {
+  extern __shared__ double bcg_lds_raw[];
+  T *e1 = (T *)bcg_lds_raw, *e2 = e1 + 64 * 64;
+  bcg_stage(E1, E2, e1, e2);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  BcgAcc<T> h[4][4];
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) bcg_clear(h[ti][tj]);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    BcgAcc<T> ax[4], aq[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bcg_clear(ax[t]), bcg_clear(aq[t]);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk)
+      if (kk < 4 * nt) {
+        const T p = bcg_load(P, n, nc, r0 + ci, 4 * kk + kq), t = bcg_load(Tm, n, nc, r0 + ci, 4 * kk + kq);
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (tj < nt) {
+            bcg_mma(ax[tj], p, e1[(4 * kk + kq) * 64 + 16 * tj + ci]);
+            bcg_mma(aq[tj], t, e2[(4 * kk + kq) * 64 + 16 * tj + ci]);
+          }
+      }
+    T qn[4][4];
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t row = r0 + kq + 4 * reg;
+        const int col = 16 * tj + ci;
+        qn[tj][reg] = vzero(T());
+        if (tj < nt && row < n && col < nc) {
+          X[row * ldx + col] = vadd(X[row * ldx + col], bcg_get(ax[tj], reg));
+          qn[tj][reg] = vsub(Q[row * nc + col], bcg_get(aq[tj], reg));
+          Q[row * nc + col] = qn[tj][reg];
+        }
+      }
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (ti < nt && tj < nt) bcg_mma(h[ti][tj], vconj(qn[ti][reg]), qn[tj][reg]);
+  }
+  bcg_block_partial(h, nt, e1, partial);
+}
+
+// Step 6 in one pass: Q <- Q E1 and P <- W E1 + P E2 in place (E1 = I[:, piv] inv(S[:, piv]), E2 = S^H).  A wave reads its
+// 16-row strip of Q, W and P once, as operands, before it writes any of it; W E1 is never stored.
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_qp(int64_t n, int nc, T *__restrict__ Q, const T *__restrict__ W,
+                                                T *__restrict__ P, const T *__restrict__ E1, const T *__restrict__ E2) {
+  extern __shared__ double bcg_lds_raw[];
+  T *e1 = (T *)bcg_lds_raw, *e2 = e1 + 64 * 64;
+  bcg_stage(E1, E2, e1, e2);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    T q[16], w[16], p[16];
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      q[kk] = w[kk] = p[kk] = vzero(T());
+      if (kk < 4 * nt) {
+        q[kk] = bcg_load((const T *)Q, n, nc, r0 + ci, 4 * kk + kq);
+        w[kk] = bcg_load(W, n, nc, r0 + ci, 4 * kk + kq);
+        p[kk] = bcg_load((const T *)P, n, nc, r0 + ci, 4 * kk + kq);
+      }
+    }
+    BcgAcc<T> aq[4], ap[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bcg_clear(aq[t]), bcg_clear(ap[t]);
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk)
+      if (kk < 4 * nt) {
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (tj < nt) {
+            const T b1 = e1[(4 * kk + kq) * 64 + 16 * tj + ci], b2 = e2[(4 * kk + kq) * 64 + 16 * tj + ci];
+            bcg_mma(aq[tj], q[kk], b1);
+            bcg_mma(ap[tj], w[kk], b1);
+            bcg_mma(ap[tj], p[kk], b2);
+          }
+      }
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t row = r0 + kq + 4 * reg;
+        const int col = 16 * tj + ci;
+        if (tj < nt && row < n && col < nc) {
+          Q[row * nc + col] = bcg_get(aq[tj], reg);
+          P[row * nc + col] = bcg_get(ap[tj], reg);
+        }
+      }
+  }
+}
+
+// The start's scalars from the kCgBlocks partials of |b_j|^2 (k_cg_dot): beta_j, and which columns enter the block.  A zero
+// column is done (x = 0, flag 0), a column whose |b|^2 is not finite is excluded (x = 0, flag 1); both 0 iterations.
+template <class T>
+__global__ void __launch_bounds__(1024) k_bcg_beta(const T *__restrict__ partial, int nc, BcgState<T> S) {
+  __shared__ T sm[16 * 64];
+  const T tot = cg_sum_partials(partial, nc, sm);
+  if (threadIdx.x < nc) {
+    const int c = threadIdx.x;
+    const double b2 = vreal(tot);
+    const bool in = b2 != 0.0 && isfinite(b2);
+    S.bnorm[c] = in ? sqrt(b2) : 0.0;
+    S.active[c] = in ? 1 : 0;
+    S.flag[c] = (b2 == 0.0 || in) ? 0 : 1;
+    S.iter[c] = 0;
+    S.relres[c] = __builtin_huge_val();
+  }
+  if (threadIdx.x == 0) S.ctl[0] = 1, S.ctl[1] = S.ctl[2] = 0, S.ctl[3] = nc;
+}
+
+// R[:, c] = R[:, c] / beta_c for a column of the block, an exact zero otherwise (selected, not multiplied: a NaN stays out)
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_norm(int64_t n, int nc, T *__restrict__ R, const double *__restrict__ beta,
+                                                  const int *__restrict__ active) {
+  const int64_t total = n * nc;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(e % nc);
+    const T v = R[e];
+    R[e] = active[c] ? vdivr(v, beta[c]) : vzero(T());
+  }
+}
+
+struct BcgTeam {
+  __device__ int rank() const { return threadIdx.x; }
+  __device__ int size() const { return blockDim.x; }
+  __device__ void sync() const { __syncthreads(); }
+};
+
+// One workgroup of 256 threads on the summed Gram S.G of step k (1-based), with blockcg_small.hpp's arithmetic on two
+// 64 x 64 working matrices in LDS:
+//   mode 1: start: G = R^H Z -> pivoted Cholesky S, rank r; E1 = I[:, piv] inv(S[:, piv]), E2 = 0, C = S
+//   mode 2: Sigma = P^H A P -> unpivoted Cholesky, alpha = Sigma^-1; E1 = alpha C diag(beta), E2 = alpha
+//   mode 3: H = Q^H Q -> relres_j = sqrt(c_j^H H c_j); all <= rtol: flag 0, k iterations; k == maxit: flag 0 / 2
+//   mode 4: G = Q^H W -> pivoted Cholesky S, rank r'; E1 = I[:, piv] inv(S[:, piv]), E2 = S^H, C = S C, r = r'
+// A breakdown (the Cholesky's, or r' = 0) ends the tile: every column of the block that was not <= rtol at its last test
+// gets flag 1, all get the completed steps as iterations, and E1 = E2 = 0 so that the step's remaining passes change nothing.
+// A tile that is over (ctl[0] == 0) is left alone.
+template <class T>
+__global__ void __launch_bounds__(256) k_bcg_small(int mode, int k, int s, BcgState<T> S) {
+  extern __shared__ double bcg_lds_raw[];
+  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64;
+  double *d = (double *)(W2 + 64 * 64);
+  int *piv = (int *)(d + 64), *taken = piv + 64;
+  const BcgTeam tm;
+  if (S.ctl[0] == 0) return;
+  const int m = (mode == 1) ? s : S.ctl[3];
+  __syncthreads();  // (everybody has read ctl before thread 0 may change it)
+  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) W1[e] = (e / 64 < m && e % 64 < m) ? S.G[e] : vzero(T());
+  __syncthreads();
+  bcg::hermitize(W1, W2, m, tm);
+  auto clear_coefficients = [&] {
+    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.E1[e] = S.E2[e] = vzero(T());
+    __syncthreads();
+  };
+  auto stop = [&](bool broke, int done) {  // flags and iterations of the block's columns; the tile is over
+    if (threadIdx.x < s && S.active[threadIdx.x]) {
+      const bool conv = S.relres[threadIdx.x] <= S.rtol;
+      S.flag[threadIdx.x] = conv ? 0 : (broke ? 1 : 2);
+      S.iter[threadIdx.x] = done;
+    }
+    if (threadIdx.x == 0) S.ctl[0] = 0;
+  };
+  auto stage = [&](const T *from, T *to) {  // a 64 x 64 matrix of the state into LDS: no inner loop reads HBM
+    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) to[e] = from[e];
+    __syncthreads();
+  };
+  if (mode == 3) {
+    stage(S.C, W2);
+    bcg::quad_forms(W1, W2, m, s, S.G, S.relres, tm);
+    bool all = true;
+    for (int c = 0; c < s; ++c) all = all && (!S.active[c] || S.relres[c] <= S.rtol);
+    if (all || k >= S.maxit) stop(false, k);
+    return;
+  }
+  clear_coefficients();
+  const bcg::Chol f = bcg::chol(W1, m, S.deftol, mode != 2, W2, piv, d, taken, tm);
+  if (f.bad || (mode != 2 && f.r == 0)) {
+    if (mode == 1 && !f.bad) {  // every column zero or excluded: nothing to do
+      if (threadIdx.x == 0) S.ctl[0] = 0;
+    } else {
+      stop(true, mode == 4 ? k : (mode == 2 ? k - 1 : 0));
+    }
+    return;
+  }
+  const int r = f.r;
+  bcg::tri_inv(W2, piv, r, W1, tm);  // W1 = inv(S[:, piv])
+  if (mode == 2) {
+    for (int c = threadIdx.x; c < 64; c += blockDim.x) d[c] = (c < s && S.active[c]) ? S.bnorm[c] : 0.0;
+    bcg::matmul(W1, W1, true, r, r, r, (const double *)nullptr, W2, tm);  // alpha = Ti Ti^H
+    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.E2[e] = (e / 64 < r && e % 64 < r) ? W2[e] : vzero(T());
+    stage(S.C, W1);
+    bcg::matmul(W2, W1, false, r, r, s, d, S.E1, tm);
+    if (threadIdx.x == 0) S.ctl[2] = r;
+    return;
+  }
+  bcg::select_rows(W1, piv, r, m, r, S.E1, tm);
+  if (mode == 1) {
+    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.C[e] = (e / 64 < r && e % 64 < s) ? W2[e] : vzero(T());
+    if (threadIdx.x == 0) S.ctl[1] = S.ctl[2] = S.ctl[3] = r;
+    return;
+  }
+  bcg::adjoint(W2, r, m, S.E2, tm);
+  stage(S.C, W1);
+  bcg::matmul(W2, W1, false, r, m, s, (const double *)nullptr, S.G, tm);  // S C
+  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.C[e] = (e / 64 < r && e % 64 < s) ? S.G[e] : vzero(T());
+  if (threadIdx.x == 0) S.ctl[3] = r;
 }
 
 }  // namespace hifamd

@@ -556,9 +556,10 @@ class HIF:
         it, fl = st[0::2].copy(), st[1::2].copy()
         return (x, int(it[0]), int(fl[0])) if vec else (x, it, fl)
 
-    def _krylov(self, name, b, *lead, rtol, maxit, full_rank):
+    def _krylov(self, name, b, *lead, rtol, maxit, full_rank, mid=(), tail=()):
         """The batched solver hifamd_<name>_batch (host array) or hifamd_<name>_batch_dev (CUDA tensor) on all columns of
-        b; lead are the solver's arguments ahead of rtol.  Returns (x, flags, iters); ints for a vector."""
+        b; lead are the solver's arguments ahead of rtol, mid those between rtol and maxit, tail those behind iters.
+        Returns (x, flags, iters); ints for a vector."""
         vec = (b.ndim == 1)
         if _is_torch(b):
             import torch
@@ -572,7 +573,7 @@ class HIF:
             fn, io = getattr(lib(), "hifamd_%s_batch" % name), (_p(B), B.shape[1], _p(X), X.shape[1])
         fl = np.zeros(B.shape[1], dtype=np.int32)
         it = np.zeros(B.shape[1], dtype=np.int32)
-        _check(fn(self._h, *io, B.shape[1], *lead, float(rtol), int(maxit), -1 if full_rank else 0, _p(fl), _p(it)))
+        _check(fn(self._h, *io, B.shape[1], *lead, float(rtol), *mid, int(maxit), -1 if full_rank else 0, _p(fl), _p(it), *tail))
         if vec:
             return X.reshape(-1), int(fl[0]), int(it[0])
         return X, fl, it
@@ -662,6 +663,20 @@ class HIF:
         [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix and is_hermitian().
         Returns (x, flags, iters); ints for a vector.  flags: 0 converged, 1 breakdown, 2 reached maxit."""
         return self._krylov("pcg", b, rtol=rtol, maxit=maxit, full_rank=full_rank)
+
+    def bcg(self, b, block=64, rtol=1e-6, maxit=500, deftol=1e-12, full_rank=False):
+        """Breakdown-free block CG (x0 = 0) for a Hermitian positive-definite pair (A, M) (hifamd_bcg_batch / _dev): the
+        columns of b ([n] or [n][nrhs], host array or CUDA tensor) are cut into tiles of `block` <= 64, and the columns of a
+        tile share one block Krylov space; dependent, duplicate and zero columns shrink the block (a pivoted Cholesky that
+        drops pivots <= deftol) instead of breaking it down.  Needs set_matrix and is_hermitian().  Returns
+        (x, flags, iters, ranks); ints for a vector, ranks always an array: per tile its rank after the start and during
+        its last step.  flags: 0 converged, 1 breakdown or a non-finite column, 2 reached maxit; iters: the steps of the
+        column's tile.  A column's result depends on the columns it shares a tile with."""
+        ntile = -(-(1 if b.ndim == 1 else int(b.shape[1])) // max(int(block), 1))
+        ranks = np.zeros(2 * max(ntile, 1), dtype=np.int32)
+        x, fl, it = self._krylov("bcg", b, int(block), rtol=rtol, maxit=maxit, full_rank=full_rank, mid=(float(deftol),),
+                                 tail=(_p(ranks),))
+        return x, fl, it, ranks
 
     def sqmr(self, b, rtol=1e-6, maxit=500, full_rank=False):
         """Symmetric QMR (Freund / Nachtigal, x0 = 0) for a Hermitian pair (A, M) that may be indefinite, all columns of b

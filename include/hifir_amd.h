@@ -433,6 +433,40 @@ HifAmdStatus hifamd_pcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, 
 HifAmdStatus hifamd_pcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs,
                                   double rtol, int maxit, int64_t rank, int *flags, int *iters);
 
+/* ---- breakdown-free block CG for a Hermitian positive-definite pair (A, M) -------------------- */
+/* Block CG with x0 = 0 (Dubrulle's BCGrQ, preconditioned): the batch is cut into tiles of `block` <= 64 columns, and the
+ * columns of a tile share ONE block Krylov space -- every column is minimised over the directions generated by all of them,
+ * where hifamd_pcg_batch runs 64 independent spaces in lock step.  The block residual is kept factored, R = Q C with
+ * Q^H M^{-1} Q = I, and rank loss (dependent, duplicate or zero columns, directions that converge before the others)
+ * shrinks the block through a pivoted Cholesky instead of breaking down:
+ *   start: beta_j = ||b_j||; R = B diag(1 / beta); Z = M^{-1} R; G = R^H Z = S^H S, the upper Cholesky factor by the
+ *     largest remaining diagonal (ties: the lowest index), stopped when that diagonal is <= deftol * max diag G: rank r,
+ *     S is r x s; E = I[:, piv] inv(S[:, piv]); Q = R E; P = Z E; C = S
+ *   per step: T = A P; alpha = (P^H T)^{-1} by an unpivoted Cholesky; X += P alpha C diag(beta); Q -= T alpha;
+ *     relres_j = sqrt(c_j^H (Q^H Q) c_j) = ||r_j|| / ||b_j||; stop when every column is <= rtol; W = M^{-1} Q;
+ *     G = Q^H W = S^H S (pivoted as above, rank r'); Q <- Q E; P <- W E + P S^H; C <- S C; r = r'
+ * A STEP is one batched M^{-1} apply plus one SpMM on the block, the unit of the PCG iteration count; on top of these
+ * it costs two Gram products and two row-local [n][block] x [block][block] products on the f64 matrix cores and three
+ * one-workgroup kernels on the small matrices.  Everything stays in HBM (four work vectors Q, W, P, T per tile); the host
+ * reads back one integer per step.  Sums run in a fixed order: the same tile with the same inputs gives the same bits,
+ * but -- unlike every other driver here -- a column's result DOES depend on the columns it shares a tile with.
+ * Needs hifamd_set_matrix and a Hermitian M^{-1}, and treats the filters as hifamd_pcg_batch does: a constant-mode
+ * filter on HIFAMD_S is refused with HIFAMD_BAD_PREC, with a basis filter the iteration runs projected (R = P B,
+ * beta = ||P b||, every apply filtered).  maxit < 1, rtol <= 0, block outside [1, 64] or deftol outside (0, 1):
+ * HIFAMD_MISMATCHED_SIZES.  deftol: 1e-12 sits two decades above the rounding of a 64-column Gram.  rank: 0 numerical
+ * rank, -1 full.  Per column: flags[c] = 0 converged / 1 breakdown / 2 reached maxit; iters[c] = the steps of its tile,
+ * the same for all its columns.  A zero column: x = 0, flag 0, 0 iterations.  A column whose ||b||^2 is not finite is
+ * excluded: x = 0, flag 1, 0 iterations; it enters the block as an exact zero and does not touch its neighbours.  A
+ * breakdown (P^H A P not positive definite: a pivot <= 0 or not finite; a Gram with a non-finite entry or a leftover
+ * diagonal below -deftol * max diag; r' = 0 with columns still unconverged) ends the tile: every column that was not
+ * <= rtol at its last test gets flag 1, iters = completed steps.  ranks (may be NULL): int[2 * ceil(nrhs / block)], per
+ * tile its rank after the start and during its last step.  flags and iters may be NULL.  Host pointers; the _dev variant
+ * takes device pointers for B, X (flags, iters, ranks stay host arrays) and returns when the solve is done. */
+HifAmdStatus hifamd_bcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int block,
+                              double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks);
+HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
+                                  double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks);
+
 /* ---- right-preconditioned BiCGSTAB for a general (non-Hermitian) pair (A, M), batched --------- */
 /* BiCGSTAB with x0 = 0 and shadow residual r^ = b for nrhs columns in lock step: r = b, rho = (r^, r), p = r; per
  * iteration y = M^{-1} p, v = A y, alpha = rho / (r^, v), x += alpha y, r -= alpha v, test; y = M^{-1} r, t = A y,
