@@ -344,7 +344,9 @@ class HIF:
         dev = lib().hifamd_device(self._h)
         if dev >= 0 and T.device.index != dev:
             raise HifAmdError(2, f"{what}: tensor lives on cuda:{T.device.index}, the hierarchy on cuda:{dev}")
-        if _np_dtype_of(T) != self.dtype:
+        # (`is None` first: numpy reads a comparison with None as one with its default dtype, float64, so on a real handle
+        # `None != self.dtype` is False and a float32 tensor would pass, to be read as float64 past its end)
+        if _np_dtype_of(T) is None or _np_dtype_of(T) != self.dtype:
             raise HifAmdError(2, f"{what}: dtype {T.dtype} does not match the hierarchy's {self.dtype}")
         if T.dim() != 2 or T.shape[0] != self.nrows() or T.shape[1] < 1:
             raise HifAmdError(2, f"{what}: expected an [nrows][nrhs] block, got {tuple(T.shape)}")

@@ -404,6 +404,57 @@ def test_tensor_arguments_are_validated():
         M.solve_mrhs(np.zeros((n, 2)), X=np.zeros((2, n)).T)  # not C-contiguous
 
 
+class _DeviceTensorStandIn:
+    """What HIF._dev_block asks of a CUDA tensor, without a GPU: on the handle's device, [n][nrhs], unit column stride, of the
+    given torch dtype.  Its address must never be asked for: a tensor that is refused does not reach the C ABI."""
+    __module__ = "torch.standin"
+    is_cuda = True
+
+    def __init__(self, n, nrhs, dtype, device_index):
+        import types
+
+        self.shape, self.dtype, self.ndim = (n, nrhs), dtype, 2
+        self.device = types.SimpleNamespace(index=device_index)
+
+    def dim(self):
+        return 2
+
+    def stride(self, k):
+        return (self.shape[1], 1)[k]
+
+    def reshape(self, *shape):
+        return self
+
+    def data_ptr(self):
+        raise AssertionError("a tensor that had to be refused reached the C ABI")
+
+
+@pytest.mark.parametrize("cplx", [False, True], ids=["real-handle", "complex-handle"])
+def test_device_tensors_of_another_dtype_are_refused(cplx):
+    """A device tensor whose dtype is not the handle's is refused with MISMATCHED_SIZES by every CUDA-tensor branch, whatever
+    the dtype: the kernels would read a float32 block as float64, past its end.  (numpy compares None -- what the wrapper
+    maps every torch dtype but float64 and complex128 to -- as float64: on a real handle `None != dtype` is False.)"""
+    torch = pytest.importorskip("torch")
+    M = hifir_amd.HIF(dtype=np.complex128 if cplx else np.float64)
+    n = 25
+    own = torch.complex128 if cplx else torch.float64
+    other = [torch.float32, torch.float16, torch.bfloat16, torch.complex64, torch.int64, torch.float64 if cplx else torch.complex128]
+    M.nrows = lambda: n  # (the shape test behind the dtype test would refuse too: it must not be what refuses)
+    dev = hifir_amd.lib().hifamd_device(M._h)
+    good = _DeviceTensorStandIn(n, 4, own, dev)
+    assert M._dev_block(good, "B") is good  # the stand-in passes as a block of the handle's own type
+    for dt in other:
+        T = _DeviceTensorStandIn(n, 4, dt, dev)
+        for call in (lambda: M.solve_mrhs(T), lambda: M.solve_mrhs(T, good), lambda: M.solve_mrhs(good, T), lambda: M.solve(T),
+                     lambda: M.mmultiply(T), lambda: M.spmv(T), lambda: M.spmv(good, T), lambda: M.nsp_filter(T),
+                     lambda: M.hifir(T, 2), lambda: M.residual(T, good), lambda: M.residual(good, T), lambda: M.gmres(T),
+                     lambda: M.gmres_ir(T), lambda: M.pcg(T), lambda: M.bcg(T), lambda: M.sqmr(T), lambda: M.bicgstab(T),
+                     lambda: M.idrs(T), lambda: M.time_apply(T, good), lambda: M.time_apply(good, T)):
+            with pytest.raises(hifir_amd.HifAmdError) as e:
+                call()
+            assert e.value.code == 2 and "dtype" in e.value.msg, dt
+
+
 @pytest.mark.parametrize("san", ["address,undefined", "thread"])
 def test_import_path_under_sanitizers(tmp_path, san):
     """The host half of hifamd_load / add_level / set_dense / finalize (import.hpp + host.hpp, the code engine.hip
