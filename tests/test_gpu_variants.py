@@ -25,8 +25,12 @@ by source / dependent-row class in two tiers with outside entries (util.py; test
 which classes arrive), and the band_wgs=1 rows chain several components onto every workgroup (the kernels' loop over a
 workgroup's components, which a default plan enters only with more than 8,192 components in a band).
 
-Not reached here: the grid cap of the per-wave Schur product (k_spmm_tile with more than 16,384 blocks, i.e. more than a
-million rows in one coupling block) stays with test_gpu_fullsize.py.
+Not reached here: the grid cap of the per-wave Schur product (k_spmm_tile with more than 16,384 blocks, i.e. more than
+262,144 rows in one coupling block) stays with test_gpu_fullsize.py.  Every tiled coupling block of this table comes from
+util.shared_coupling (exactly four column groups per 16-row block) and every other one from sp.random (about 18 nonzeros per
+row, at most 4,500 rows): blocks of 0 ... 68 groups with padded last groups, rows of 0 ... 200 nonzeros and a wave's second
+row in k_spmm_epi are test_gpu_schur_edges.py's subject, which also holds the bits claimed by the narrow_tiles=0 and
+narrow_spmm=0 rows on those shapes.
 
 test_every_switch_has_a_row (CPU) keeps the table honest: every HIFIR_AMD_* name the engine reads is either in a row or
 in NOT_VARIANTS with a reason, and is listed in the README's knob paragraph."""
