@@ -3100,7 +3100,7 @@ class Engine : public EngineBase {
   }
 
   // ---- what the lock-step Krylov solvers share -------------------------------------------------------
-  // The [n][64] work vectors of all of them: a tile asks for the first k (GMRES 2, PCG and block CG 4, BiCGSTAB 5, symmetric QMR 7,
+  // The [n][64] work vectors of all of them: a tile asks for the first k (block GCR 1, GMRES 2, PCG and block CG 4, BiCGSTAB 5, symmetric QMR 7,
   // IDR(s) 2 s + 4), each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
   // That holds because no solver runs inside another one's tile: the null-space search calls gmres_dev between its own
   // local blocks, flexible GMRES calls the refinement (ir_r, ir_xk) and the projected PCG / QMR call apply_nsp
@@ -3646,6 +3646,129 @@ class Engine : public EngineBase {
                 int64_t rank, int *flags, int *iters, int *ranks) {
     staged(B, ldb, X, ldx, nrhs, false, [&] { bcg_check(block, deftol, maxit, rtol); },
            [&](const D *b, D *x) { bcg_dev(b, nrhs, x, nrhs, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
+  }
+
+  // ---- restarted block GCR for a general pair (A, M): block CG's shared space without its conditions ------------
+  // Block GMRES(m) with right preconditioning in exact arithmetic, flexible by construction.  Per cycle the true residual
+  // R = B - A X (resid_dev, the handle's residual precision) is tested, normalized and factored, relative residual = Rh C
+  // with Rh^H Rh = I (pivoted Cholesky, rank r); per step Z = M^{-1} Rh, W = A Z, both orthogonalized against the cycle's
+  // stored blocks (C_i = Q_i^H W all from the same W), W = Q_j S1 (pivoted, rank q), P_j = Z E, D = Q_j^H Rh,
+  // X += P_j D C diag(beta), Rh -= Q_j D, rel_j = sqrt(c_j^H Rh^H Rh c_j); the cycle ends on all rel <= rtol, maxit or its
+  // last step, otherwise Rh is re-factored (rank r').  A flag 0 is only ever decided on a true residual at a cycle's start.
+  // Q and P live in gm_Q / gm_Z (`restart` slots of [n][nc]); solve_dev and spmv_dev write Z and W straight into slot j and
+  // k_bgcr_rmul turns them into P_j and Q_j in place.  Rh (and the cycle-start residual it is made from, in place) is
+  // kr_vec[0].  Per step: one batched apply, one SpMM, the stacked Gram (k_bgcr_gram), the fused projection (k_bgcr_proj), a
+  // Gram (k_bcg_gram), the update (k_bcg_xq), two in-place products (k_bgcr_rmul), three one-workgroup kernels and ONE
+  // read-back; per cycle start one more.  Flags 0 converged / 1 stagnated, bad Gram or excluded / 2 reached maxit.
+  void bgcr_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, int restart, double rtol, double deftol, int maxit,
+                 int64_t rank, int *flags, int *iters, int *ranks) {
+    const int64_t n = lv[0]->n, slot = n * nc;
+    const size_t vec = (size_t)n * nc * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
+    const size_t part = std::max((size_t)kBcgBlocks * mat, (size_t)kCgBlocks * 64 * sizeof(D));
+    krylov_vectors(1, vec);
+    if (gm_Q.bytes < vec * (size_t)restart) gm_Q.alloc(vec * (size_t)restart);
+    if (gm_Z.bytes < vec * (size_t)restart) gm_Z.alloc(vec * (size_t)restart);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    D *Rh = kr_vec[0].as<D>(), *Qs = gm_Q.as<D>(), *Ps = gm_Z.as<D>(), *pt = ir_part.as<D>();
+    const size_t lds_pass = 2 * mat, lds_small = 2 * mat + 64 * sizeof(double) + 128 * sizeof(int);
+    const size_t lds_proj = (size_t)kBgcrGroup<D> * mat;
+    if (!bgcr_lds_raised) {
+      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_xq<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
+      HIP_OK(hipFuncSetAttribute((const void *)k_bgcr_proj<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_proj));
+      HIP_OK(hipFuncSetAttribute((const void *)k_bgcr_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
+      bgcr_lds_raised = true;
+    }
+    StreamWait wait{stream};
+    BgcrState<D> S;
+    double *ints = nullptr;  // (a [64] double slot that holds live | aux as integers)
+    krylov_state(S, {{&S.C, 64}, {&S.E1, 64}, {&S.E2, 64}, {&S.G, 64}, {&S.Cs, 64 * restart}},
+                 {&S.bnorm, &S.relres, &S.rho, &S.tres, &S.mu, &ints}, rtol, maxit);
+    S.deftol = deftol;
+    S.live = (int *)ints;
+    S.aux = S.live + 64;
+    auto gram = [&](const D *a, const D *b) {  // S.G = a^H b
+      hipLaunchKernelGGL((k_bcg_gram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
+    };
+    auto small = [&](int mode, int steps, bool flag) {
+      hipLaunchKernelGGL((k_bgcr_small<D>), dim3(1), dim3(256), lds_small, stream, mode, steps, flag ? 1 : 0, nc, S);
+    };
+    auto rmul = [&](D *x1, D *x2) {  // x1 <- x1 E1 (and x2)
+      hipLaunchKernelGGL((k_bgcr_rmul<D>), dim3(kBcgBlocks), dim3(256), mat, stream, n, nc, x1, x2, (const D *)S.E1);
+    };
+    auto state = [&] {  // ctl[0]: 0 the tile is over, 1 inside a cycle, 2 the cycle has ended
+      const int go = krylov_active(S);
+      HIP_OK(hipGetLastError());
+      return go;
+    };
+    vec_op(1, n, nc, Rh, nc, dB, ldb, nullptr, 0);  // R = b
+    hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, (const D *)Rh, (int64_t)nc, (const D *)nullptr, pt);
+    hipLaunchKernelGGL((k_bcg_beta<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, (BcgState<D>)S);
+    vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
+    int steps = 0, go = 1;
+    for (int cycle = 0; go != 0; ++cycle) {
+      if (cycle > 0) resid_dev(dB, ldb, (const D *)dX, ldx, Rh, nc, nc, resid_mode);  // the true residual
+      hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, (const D *)Rh, (int64_t)nc,
+                         (const D *)nullptr, pt);
+      hipLaunchKernelGGL((k_bgcr_rho<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, cycle, steps, S);
+      hipLaunchKernelGGL((k_bcg_norm<D>), dim3(vec_grid(n * nc)), dim3(256), 0, stream, n, nc, Rh, (const double *)S.rho,
+                         (const int *)S.live);
+      gram(Rh, Rh);
+      small(1, steps, cycle == 0);
+      rmul(Rh, nullptr);  // Rh = Rn E
+      if ((go = state()) != 1) break;
+      for (int j = 0; j < restart && go == 1; ++j) {
+        D *Pj = Ps + (int64_t)j * slot, *Qj = Qs + (int64_t)j * slot;
+        solve_dev((const D *)Rh, nc, Pj, nc, nc, rank, nullptr);  // Z = M^{-1} Rh, into the slot
+        spmv_dev((const D *)Pj, nc, Qj, nc, nc, nullptr);         // W = A Z
+        ++steps;
+        if (j > 0) {
+          // (row blocks per stack entry: fewer as the stack grows, never more partial matrices than kBcgBlocks)
+          const int nb = std::max(1, kBcgBlocks / j);
+          hipLaunchKernelGGL((k_bgcr_gram<D>), dim3(j, nb), dim3(256), 0, stream, n, nc, (const D *)Qs, slot, (const D *)Qj, pt);
+          hipLaunchKernelGGL((k_bgcr_sum<D>), dim3(16, j), dim3(256), 0, stream, (const D *)pt, nb, nc, S.Cs);
+        }
+        hipLaunchKernelGGL((k_bgcr_proj<D>), dim3(kBcgBlocks), dim3(256), lds_proj, stream, n, nc, j, (const D *)Qs,
+                           (const D *)Ps, slot, (const D *)S.Cs, Qj, Pj, pt);
+        hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
+        small(2, steps, false);  // W^H W -> rank q, E1
+        rmul(Qj, Pj);            // Q_j = W E, P_j = Z E
+        gram(Qj, Rh);
+        small(3, steps, false);  // D -> E1 = D C diag(beta), E2 = D
+        hipLaunchKernelGGL((k_bcg_xq<D>), dim3(kBcgBlocks), dim3(256), lds_pass, stream, n, nc, dX, ldx, Rh, (const D *)Pj,
+                           (const D *)Qj, (const D *)S.E1, (const D *)S.E2, pt);
+        hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
+        small(4, steps, j == restart - 1);  // rel, the end of the cycle, or the next factor of Rh
+        if ((go = state()) == 1) rmul(Rh, nullptr);
+      }
+    }
+    krylov_result(S, nc, flags, iters);
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+  }
+  bool bgcr_lds_raised = false;
+
+  void bgcr_check(int block, int restart, double deftol, int maxit, double rtol) {
+    krylov_check("block GCR", maxit, rtol);
+    if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
+    if (restart < 1 || restart > HIFAMD_BGCR_MAX_RESTART)
+      throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= restart <= HIFAMD_BGCR_MAX_RESTART");
+    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < deftol < 1");
+  }
+  void bgcr_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int block, int restart, double rtol, double deftol,
+                int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { bgcr_check(block, restart, deftol, maxit, rtol); },
+                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) {
+                   bgcr_tile(b, ldb, x, ldx, nc, restart, rtol, deftol, maxit, rank, fl, it,
+                             ranks ? ranks + 2 * ((b - dB) / block) : nullptr);
+                 },
+                 block >= 1 && block <= 64 ? block : 64);
+  }
+  void bgcr_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int block, int restart, double rtol, double deftol,
+                 int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
+    staged(B, ldb, X, ldx, nrhs, false, [&] { bgcr_check(block, restart, deftol, maxit, rtol); },
+           [&](const D *b, D *x) { bgcr_dev(b, nrhs, x, nrhs, nrhs, block, restart, rtol, deftol, maxit, rank, flags, iters, ranks); });
   }
 
   // ---- right-preconditioned BiCGSTAB, batched over columns ----------------------------------------
@@ -4747,6 +4870,26 @@ HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void
                                   double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
   API_BEGIN
   visit(h, [&](auto &E) { E.bcg_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
+  API_END
+}
+
+HifAmdStatus hifamd_bgcr_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int block,
+                               int restart, double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters,
+                               int *ranks) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.bgcr_host(E.val(B), ldb, E.val(X), ldx, nrhs, block, restart, rtol, deftol, maxit, rank, flags, iters, ranks);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_bgcr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
+                                   int restart, double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters,
+                                   int *ranks) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.bgcr_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, block, restart, rtol, deftol, maxit, rank, flags, iters, ranks);
+  });
   API_END
 }
 

@@ -35,6 +35,8 @@
 //                    k_bs_tr and, for P^H x, k_nsp_coef / k_nsp_finish)
 //   k_bcg_gram / k_bcg_sum / k_bcg_xq / k_bcg_qp / k_bcg_small / k_bcg_beta / k_bcg_norm   device-resident block CG: Grams and
 //                    row-local products on the f64 matrix cores, the small matrices in one workgroup (blockcg_small.hpp)
+//   k_bgcr_gram / k_bgcr_sum / k_bgcr_proj / k_bgcr_rmul / k_bgcr_rho / k_bgcr_small   device-resident restarted block GCR: the
+//                    stacked Gram, the fused block Gram-Schmidt pass, in-place right-multiplication, decisions (blockgcr_small.hpp)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -45,6 +47,7 @@
 
 #include "band_lds.hpp"
 #include "blockcg_small.hpp"
+#include "blockgcr_small.hpp"
 
 namespace hifamd {
 
@@ -5736,9 +5739,9 @@ __device__ __forceinline__ T bcg_load(const T *__restrict__ x, int64_t n, int nc
 }
 
 // Adds the 4 x 4 accumulator tiles of the four waves of a block in wave order and writes the nt x nt tiles in use to
-// partial[blockIdx.x] ([64][64]).  lds: 64 x 64 values, free to use from the barrier this function starts with.
+// out ([64][64]).  lds: 64 x 64 values, free to use from the barrier this function starts with.
 template <class T>
-__device__ __forceinline__ void bcg_block_partial(BcgAcc<T> (&acc)[4][4], int nt, T *lds, T *__restrict__ partial) {
+__device__ __forceinline__ void bcg_block_partial_at(BcgAcc<T> (&acc)[4][4], int nt, T *lds, T *__restrict__ out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
   for (int w = 1; w < 4; ++w) {
     __syncthreads();
@@ -5767,7 +5770,6 @@ __device__ __forceinline__ void bcg_block_partial(BcgAcc<T> (&acc)[4][4], int nt
     }
   }
   if (wave != 0) return;
-  T *__restrict__ out = partial + (int64_t)blockIdx.x * 64 * 64;
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
@@ -5776,6 +5778,11 @@ __device__ __forceinline__ void bcg_block_partial(BcgAcc<T> (&acc)[4][4], int nt
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) out[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[ti][tj], reg);
       }
+}
+// (the same to partial[blockIdx.x] of a one-dimensional grid)
+template <class T>
+__device__ __forceinline__ void bcg_block_partial(BcgAcc<T> (&acc)[4][4], int nt, T *lds, T *__restrict__ partial) {
+  bcg_block_partial_at(acc, nt, lds, partial + (int64_t)blockIdx.x * 64 * 64);
 }
 
 // partial[blockIdx.x] = the block's share of X^H Y: wave w of block b owns the row groups g = 4 b + w + k * 4 gridDim.x
@@ -6058,6 +6065,240 @@ __global__ void __launch_bounds__(256) k_bcg_small(int mode, int k, int s, BcgSt
   bcg::matmul(W2, W1, false, r, m, s, (const double *)nullptr, S.G, tm);  // S C
   for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.C[e] = (e / 64 < r && e % 64 < s) ? S.G[e] : vzero(T());
   if (threadIdx.x == 0) S.ctl[3] = r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident restarted block GCR for a general pair (A, M) (block GMRES(m) with right preconditioning in exact
+// arithmetic), one tile of nc <= 64 columns (Engine::bgcr_tile).  The direction blocks Q_i = A P_i of a cycle are kept
+// orthonormal in a stack ([slot] elements apart); the residual is kept factored, relative residual = Rh C with Rh^H Rh = I.
+// On top of block CG's kernels (k_bcg_gram, k_bcg_sum, k_bcg_xq, k_bcg_beta, k_bcg_norm, the lane maps above):
+//   k_bgcr_gram   C_i = Q_i^H W for every stored i < j in ONE launch (k_bgcr_sum adds the partials in block order)
+//   k_bgcr_proj   W -= sum Q_i C_i, Z -= sum P_i C_i and the partials of the new W^H W in one pass over the rows
+//   k_bgcr_rmul   one or two blocks times the same 64 x 64 matrix, in place
+//   k_bgcr_rho / k_bgcr_small   one workgroup: every decision and the small matrices (blockgcr_small.hpp, shared with the host)
+// A complex handle runs the same kernels on its real planes, as block CG does.  Sums run in a fixed order, no atomics.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+struct BgcrState : BcgState<T> {
+  // ctl: [0] 0 the tile is over / 1 inside a cycle / 2 the cycle has ended, [1] rank after the first cycle's start,
+  // [2] rank during the last step, [3] current rank; relres: the recurrence's rel_j
+  T *Cs;                     // [restart][64][64]  the coefficient matrices C_i of a step
+  double *rho, *tres, *mu;   // [64]  ||r|| and ||r|| / ||b|| at the cycle's start; mu[0]: the last cycle's largest tres
+  int *live, *aux;           // [64]  block columns with a nonzero residual; aux[0]: rank of the step's direction block
+  __host__ __device__ bgcr::Small<T> small() const {
+    return bgcr::Small<T>{this->C, this->E1, this->E2, this->G, this->bnorm, rho, tres, this->relres, mu, this->iter,
+                          this->flag, this->active, live, this->ctl, aux, this->rtol, this->deftol, this->maxit};
+  }
+};
+
+__device__ __forceinline__ void bcg_put(BcgAcc<double> &c, int reg, double v) { c.re[reg] = v; }
+__device__ __forceinline__ void bcg_put(BcgAcc<cplx> &c, int reg, cplx v) { c.re[reg] = v.x, c.im[reg] = v.y; }
+
+// The coefficient matrices of a stack that k_bgcr_proj holds in LDS together: 128 KB of the 160 KB (4 real, 2 complex)
+template <class T>
+constexpr int kBgcrGroup = (int)(131072 / (64 * 64 * sizeof(T)));
+
+// partial[i][blockIdx.y] = block (i = blockIdx.x, blockIdx.y)'s share of Q_i^H W, Q_i = Qs + i * slot.  The stack index
+// runs fastest over the grid, so the workgroups that are resident together read the same rows of W; the row groups of a
+// block are dealt as in k_bcg_gram, over gridDim.y blocks per stack entry.
+template <class T>
+__global__ void __launch_bounds__(256) k_bgcr_gram(int64_t n, int nc, const T *__restrict__ Qs, int64_t slot,
+                                                   const T *__restrict__ W,
+                                                   T *__restrict__ partial /* [gridDim.x][gridDim.y][64][64] */) {
+  __shared__ T lds[64 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  const T *__restrict__ X = Qs + (int64_t)blockIdx.x * slot;
+  BcgAcc<T> acc[4][4];
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) bcg_clear(acc[ti][tj]);
+  const int64_t stride = (int64_t)gridDim.y * 4;
+  for (int64_t g = (int64_t)blockIdx.y * 4 + wave; 4 * g < n; g += 2 * stride) {
+    T a[2][4], b[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        a[u][t] = vconj(bcg_load(X, n, nc, 4 * (g + u * stride) + kq, 16 * t + ci));
+        b[u][t] = bcg_load(W, n, nc, 4 * (g + u * stride) + kq, 16 * t + ci);
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (ti < nt && tj < nt) bcg_mma(acc[ti][tj], a[u][ti], b[u][tj]);
+  }
+  bcg_block_partial_at(acc, nt, lds, partial + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * 64 * 64);
+}
+
+// Cs[i] = the nb partials of stack entry i = blockIdx.y in block order (bcg::sum_partials, as k_bcg_sum)
+template <class T>
+__global__ void __launch_bounds__(256) k_bgcr_sum(const T *__restrict__ partial, int nb, int m, T *__restrict__ Cs) {
+  bcg::sum_partials(partial + (int64_t)blockIdx.y * nb * 64 * 64, nb, m, Cs + (int64_t)blockIdx.y * 64 * 64, BcgGridTeam{});
+}
+
+// Block classical Gram-Schmidt of step j in one pass over the rows: W -= sum_{i < j} Q_i C_i, Z -= sum_{i < j} P_i C_i (the
+// C_i all from the W before any update) and the block's share of the new W^H W.  A wave owns 16-row strips of W and Z and
+// keeps both in accumulator registers while the strips of Q_i and P_i stream through as A operands; the -C_i are staged in
+// LDS kBgcrGroup at a time (a stack deeper than one group re-stages per round of strips, from L2).  The updated W strip is,
+// register by register, the operand of the Gram instruction, as in k_bcg_xq.  j == 0: the Gram alone, nothing is written.
+// The four waves of a block walk their rounds together (the barriers of the staging), a strip past the last row loads zeros.
+template <class T>
+__global__ void __launch_bounds__(256) k_bgcr_proj(int64_t n, int nc, int j, const T *__restrict__ Qs,
+                                                   const T *__restrict__ Ps, int64_t slot, const T *__restrict__ Cs,
+                                                   T *__restrict__ W, T *__restrict__ Z,
+                                                   T *__restrict__ partial /* [gridDim.x][64][64] */) {
+  extern __shared__ double bcg_lds_raw[];
+  T *cl = (T *)bcg_lds_raw;
+  constexpr int GRP = kBgcrGroup<T>;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  BcgAcc<T> h[4][4];
+#pragma unroll
+  for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) bcg_clear(h[ti][tj]);
+  int staged = -1;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st0 = (int64_t)blockIdx.x * 4; 16 * st0 < n; st0 += stride) {
+    const int64_t r0 = 16 * (st0 + wave);
+    BcgAcc<T> aw[4], az[4];
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        bcg_put(aw[tj], reg, bcg_load((const T *)W, n, nc, r0 + kq + 4 * reg, 16 * tj + ci));
+        bcg_put(az[tj], reg, j > 0 ? bcg_load((const T *)Z, n, nc, r0 + kq + 4 * reg, 16 * tj + ci) : vzero(T()));
+      }
+    for (int g0 = 0; g0 < j; g0 += GRP) {
+      const int cnt = (j - g0 < GRP) ? j - g0 : GRP;
+      if (staged != g0) {
+        __syncthreads();  // (every wave is done with the group before)
+        for (int e = threadIdx.x; e < cnt * 64 * 64; e += blockDim.x) cl[e] = vsub(vzero(T()), Cs[(int64_t)g0 * 64 * 64 + e]);
+        __syncthreads();
+        staged = g0;
+      }
+      for (int u = 0; u < cnt; ++u) {
+        const T *__restrict__ Qi = Qs + (int64_t)(g0 + u) * slot, *__restrict__ Pi = Ps + (int64_t)(g0 + u) * slot;
+        const T *c = cl + u * 64 * 64;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+          if (kk < 4 * nt) {
+            const T q = bcg_load(Qi, n, nc, r0 + ci, 4 * kk + kq), p = bcg_load(Pi, n, nc, r0 + ci, 4 * kk + kq);
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj)
+              if (tj < nt) {
+                const T b = c[(4 * kk + kq) * 64 + 16 * tj + ci];
+                bcg_mma(aw[tj], q, b);
+                bcg_mma(az[tj], p, b);
+              }
+          }
+      }
+    }
+    T wn[4][4];
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t row = r0 + kq + 4 * reg;
+        const int col = 16 * tj + ci;
+        wn[tj][reg] = vzero(T());
+        if (tj < nt && row < n && col < nc) {
+          wn[tj][reg] = bcg_get(aw[tj], reg);
+          if (j > 0) {
+            W[row * nc + col] = wn[tj][reg];
+            Z[row * nc + col] = bcg_get(az[tj], reg);
+          }
+        }
+      }
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+          if (ti < nt && tj < nt) bcg_mma(h[ti][tj], vconj(wn[ti][reg]), wn[tj][reg]);
+  }
+  bcg_block_partial(h, nt, cl, partial);
+}
+
+// X1 <- X1 E and, where X2 is not null, X2 <- X2 E in place, E (64 x 64, zero outside its block) staged in LDS.  A wave
+// reads its 16-row strip of a block once, as operands, before it writes any of it.
+template <class T>
+__global__ void __launch_bounds__(256) k_bgcr_rmul(int64_t n, int nc, T *X1, T *X2, const T *__restrict__ E) {
+  extern __shared__ double bcg_lds_raw[];
+  T *e1 = (T *)bcg_lds_raw;
+  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) e1[e] = E[e];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (nc + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    for (int which = 0; which < 2; ++which) {
+      T *X = which ? X2 : X1;
+      if (!X) continue;
+      T x[16];
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) x[kk] = kk < 4 * nt ? bcg_load((const T *)X, n, nc, r0 + ci, 4 * kk + kq) : vzero(T());
+      BcgAcc<T> ax[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) bcg_clear(ax[t]);
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk)
+        if (kk < 4 * nt) {
+#pragma unroll
+          for (int tj = 0; tj < 4; ++tj)
+            if (tj < nt) bcg_mma(ax[tj], x[kk], e1[(4 * kk + kq) * 64 + 16 * tj + ci]);
+        }
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int64_t row = r0 + kq + 4 * reg;
+          const int col = 16 * tj + ci;
+          if (tj < nt && row < n && col < nc) X[row * nc + col] = bcg_get(ax[tj], reg);
+        }
+    }
+  }
+}
+
+// A cycle's start from the kCgBlocks partials of |r_j|^2 of the true residual (k_cg_dot): rho, rho / beta and the three
+// tests that can end the tile (bgcr::cycle_start).  One workgroup of 1024 threads.
+template <class T>
+__global__ void __launch_bounds__(1024) k_bgcr_rho(const T *__restrict__ partial, int nc, int cycle, int steps, BgcrState<T> S) {
+  __shared__ T sm[16 * 64];
+  const T tot = cg_sum_partials(partial, nc, sm);
+  if (S.ctl[0] == 0) return;
+  __syncthreads();
+  if (threadIdx.x < nc) S.rho[threadIdx.x] = vreal(tot);
+  __syncthreads();
+  bgcr::cycle_start(S.small(), nc, cycle, steps, BcgTeam{});
+}
+
+// One workgroup of 256 threads on the summed Gram S.G, with blockgcr_small.hpp's modes on two 64 x 64 working matrices in LDS:
+//   mode 1: cycle start: G = Rn^H Rn -> rank r, E1 (Rh = Rn E1), C        (flag: the tile's first cycle)
+//   mode 2: G = W^H W -> rank q, E1 (Q_j = W E1, P_j = Z E1)
+//   mode 3: G = Q_j^H Rh = D -> E1 = D C diag(beta), E2 = D
+//   mode 4: G = Rh^H Rh -> rel_j, the end of the cycle, or rank r', E1 (Rh <- Rh E1), C <- S C   (flag: the cycle's last step)
+// steps: the tile's completed steps.  A tile that is over, or a cycle that has ended, is left alone.
+template <class T>
+__global__ void __launch_bounds__(256) k_bgcr_small(int mode, int steps, int flag, int s, BgcrState<T> S) {
+  extern __shared__ double bcg_lds_raw[];
+  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64;
+  double *d = (double *)(W2 + 64 * 64);
+  int *piv = (int *)(d + 64), *taken = piv + 64;
+  const bgcr::Work<T> W{W1, W2, d, piv, taken};
+  const bgcr::Small<T> Sm = S.small();
+  const BcgTeam tm;
+  if (mode == 1) bgcr::cycle_factor(Sm, W, s, flag != 0, steps, tm);
+  if (mode == 2) bgcr::step_basis(Sm, W, s, steps, tm);
+  if (mode == 3) bgcr::step_coeff(Sm, W, s, tm);
+  if (mode == 4) bgcr::step_test(Sm, W, s, steps, flag != 0, tm);
 }
 
 }  // namespace hifamd

@@ -680,6 +680,22 @@ class HIF:
                                  tail=(_p(ranks),))
         return x, fl, it, ranks
 
+    def bgcr(self, b, block=64, restart=10, rtol=1e-6, maxit=500, deftol=1e-12, full_rank=False):
+        """Restarted block GCR (x0 = 0; block GMRES(restart) with right preconditioning in exact arithmetic) for a general
+        pair (A, M) (hifamd_bgcr_batch / _dev): the columns of b ([n] or [n][nrhs], host array or CUDA tensor) are cut into
+        tiles of `block` <= 64, and the columns of a tile share one block Krylov space, as in bcg -- but nothing is asked of
+        the hierarchy.  The residual is kept factored and rank-revealed (a pivoted Cholesky that drops pivots <= deftol), and
+        every flag 0 is decided on a true residual b - A x at the start of a cycle of at most `restart` <= 64 steps.  Needs
+        set_matrix.  Returns (x, flags, iters, ranks); ints for a vector, ranks always an array: per tile its rank after the
+        start of its first cycle and during its last step.  flags: 0 converged, 1 stagnated, a bad Gram or a non-finite
+        column, 2 reached maxit; iters: the steps (one apply plus one SpMM each) of the column's tile.  A column's result
+        depends on the columns it shares a tile with."""
+        ntile = -(-(1 if b.ndim == 1 else int(b.shape[1])) // max(int(block), 1))
+        ranks = np.zeros(2 * max(ntile, 1), dtype=np.int32)
+        x, fl, it = self._krylov("bgcr", b, int(block), int(restart), rtol=rtol, maxit=maxit, full_rank=full_rank,
+                                 mid=(float(deftol),), tail=(_p(ranks),))
+        return x, fl, it, ranks
+
     def sqmr(self, b, rtol=1e-6, maxit=500, full_rank=False):
         """Symmetric QMR (Freund / Nachtigal, x0 = 0) for a Hermitian pair (A, M) that may be indefinite, all columns of b
         ([n] or [n][nrhs], host array or CUDA tensor) in lock step on the device.  Needs set_matrix and is_hermitian().

@@ -467,6 +467,54 @@ HifAmdStatus hifamd_bcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, 
 HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
                                   double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks);
 
+/* ---- restarted block GCR for a general pair (A, M): a shared block space without conditions ---- */
+/* Restarted block GCR with x0 = 0: in exact arithmetic block GMRES(restart) with right preconditioning, flexible by
+ * construction.  The batch is cut into tiles of `block` <= 64 columns, and the columns of a tile share ONE block Krylov
+ * space, as in hifamd_bcg_batch -- but nothing is asked of the hierarchy: no Hermitian M^{-1}, no definite A.  The
+ * residual is kept factored and rank-revealed, relative residual = Rh C with Rh^H Rh = I:
+ *   beta_j = ||b_j||; X = 0; steps = 0; mu_prev = inf
+ *   cycle c = 0, 1, ...:
+ *     R = B - A X in the handle's residual precision (c = 0: R = B); rho_j = ||R_j||; t_j = rho_j / beta_j
+ *     all t_j <= rtol: flags 0, end.  steps == maxit: flag 0 / 2 by t_j, end.
+ *     mu = max_j t_j; c > 0 and not mu < mu_prev: flag 0 / 1 (stagnated) by t_j, end.  mu_prev = mu
+ *     Rn = R diag(1 / rho); G = Rn^H Rn = S^H S, the upper Cholesky factor by the largest remaining diagonal (ties: the
+ *       lowest index), stopped when that diagonal is <= deftol * max diag G: rank r, S is r x s;
+ *       Rh = Rn I[:, piv] inv(S[:, piv]); C = S diag(rho / beta).  r == 0 or a bad Gram: flag 0 / 1 by t_j, end.
+ *     for j = 0 .. restart - 1:
+ *       Z = M^{-1} Rh; W = A Z; steps += 1
+ *       C_i = Q_i^H W for every stored i < j (all from the same W); W -= sum Q_i C_i; Z -= sum P_i C_i
+ *       W^H W = S1^H S1 (pivoted as above, rank q; q == 0 ends the cycle); E = I[:, piv] inv(S1[:, piv]);
+ *       Q_j = W E; P_j = Z E   (A P_j = Q_j, Q_j^H Q_i = delta_ij I)
+ *       D = Q_j^H Rh; X += P_j D C diag(beta); Rh -= Q_j D; H = Rh^H Rh; rel_j = sqrt(max(0, c_j^H H c_j))
+ *       all rel_j <= rtol, steps == maxit or j == restart - 1: the cycle ends, before H is factored
+ *       H = S^H S (pivoted, rank r'; r' == 0 ends the cycle); Rh <- Rh I[:, piv] inv(S[:, piv]); C <- S C; r = r'
+ * A STEP is one batched M^{-1} apply plus one SpMM on the block, the unit of every other driver here: maxit caps steps and
+ * iters[c] is the step count of the column's tile.  EVERY FLAG 0 IS DECIDED ON A TRUE RESIDUAL b - A x formed at a
+ * cycle's start; the recurrence's rel_j only ends a cycle early, and what a pivoted Cholesky drops is therefore looked at
+ * again at the next cycle's start: a drop cannot make a column pass.  A converged column stays in the block and leaves
+ * through the rank, as in block CG.  A column's bits depend on the columns it shares a tile with; the same tile with the
+ * same inputs gives the same bits (fixed summation orders, no atomics); tiles do not see each other.  The filters are
+ * treated as hifamd_bicgstab_batch treats them: every M^{-1} apply is filtered, nothing else, and a constant-mode filter
+ * is allowed.  On top of the apply and the SpMM a step costs the stacked Gram against the cycle's blocks, one fused
+ * projection pass, two more Grams, the update pass and two in-place [n][block] x [block][block] products on the f64
+ * matrix cores, three one-workgroup kernels, and one integer read back; a cycle's start costs a residual, a Gram and a
+ * second read-back.  Memory: 2 * restart + 1 blocks of [n][block] on the device plus restart + 4 matrices of 64 x 64.
+ * Refusals as hifamd_bicgstab_batch, then block outside [1, 64], restart outside [1, HIFAMD_BGCR_MAX_RESTART] or deftol
+ * outside (0, 1): HIFAMD_MISMATCHED_SIZES.  rank: 0 numerical rank, -1 full.  flags[c] = 0 converged / 1 stagnated, a bad
+ * Gram (a non-finite entry, a leftover diagonal below -deftol * max diag) or excluded / 2 reached maxit.  A zero column:
+ * x = 0, flag 0, 0 steps.  A column whose ||b||^2 is not finite is excluded as in hifamd_bcg_batch: x = 0, flag 1, 0 steps;
+ * it enters the block as an exact zero and does not touch its neighbours.  ranks (may be NULL):
+ * int[2 * ceil(nrhs / block)], per tile its rank after the start of its first cycle and the rank of Rh during its last
+ * step.  flags and iters may be NULL.  Host pointers; the _dev variant takes device pointers for B, X (flags, iters, ranks
+ * stay host arrays) and returns when the solve is done. */
+#define HIFAMD_BGCR_MAX_RESTART 64
+HifAmdStatus hifamd_bgcr_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, int64_t ldx, int64_t nrhs, int block,
+                               int restart, double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters,
+                               int *ranks);
+HifAmdStatus hifamd_bgcr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
+                                   int restart, double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters,
+                                   int *ranks);
+
 /* ---- right-preconditioned BiCGSTAB for a general (non-Hermitian) pair (A, M), batched --------- */
 /* BiCGSTAB with x0 = 0 and shadow residual r^ = b for nrhs columns in lock step: r = b, rho = (r^, r), p = r; per
  * iteration y = M^{-1} p, v = A y, alpha = rho / (r^, v), x += alpha y, r -= alpha v, test; y = M^{-1} r, t = A y,

@@ -327,6 +327,24 @@ class HIF {
     return std::make_tuple(std::move(X), std::move(flags), std::move(iters), std::move(ranks));
   }
 
+  // ---- restarted block GCR for a general pair (A, M) on the device (hifamd_bgcr_batch) ----
+  // As bcg, with nothing asked of the hierarchy: the columns of every tile of `block` <= 64 share one block Krylov space,
+  // restarted every `restart` <= HIFAMD_BGCR_MAX_RESTART steps; every flag 0 is decided on a true residual.
+  // -> (X, flags, iters, ranks): per column flag 0 converged, 1 stagnated / bad Gram / excluded, 2 reached maxit and the
+  // steps of its tile; per tile its rank after the start of its first cycle and during its last step.
+  template <class Matrix, class ArrayType>
+  std::tuple<ArrayType, std::vector<int>, std::vector<int>, std::vector<int>> bgcr(
+      const Matrix &A, const ArrayType &B, const int nrhs, const int block, const int restart, const double rtol,
+      const int maxit, const double deftol = 1e-12, const bool full_rank = false) {
+    ensure_matrix(A);
+    if (nrhs < 1 || block < 1) throw std::runtime_error("hifir_amd: bgcr needs nrhs >= 1 and block >= 1");
+    ArrayType X(B.size());
+    std::vector<int> flags(nrhs, 0), iters(nrhs, 0), ranks(2 * ((nrhs + block - 1) / block), 0);
+    detail::check(hifamd_bgcr_batch(_h, B.data(), nrhs, X.data(), nrhs, nrhs, block, restart, rtol, deftol, maxit,
+                                    full_rank ? -1 : 0, flags.data(), iters.data(), ranks.data()));
+    return std::make_tuple(std::move(X), std::move(flags), std::move(iters), std::move(ranks));
+  }
+
   // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
   // Needs an is_symm hierarchy: is_hermitian(); neither A nor M has to be definite.  iters counts iterations (one apply
   // plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
