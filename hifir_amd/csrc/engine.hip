@@ -22,6 +22,7 @@
 #include "host.hpp"
 #include "import.hpp"
 #include "kernels.hip.hpp"
+#include "options.hpp"
 
 namespace hifamd {
 
@@ -52,10 +53,7 @@ struct DevT<zdouble> {
   typedef cplx type;
 };
 
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
+static_assert(kMaxWgRows == HIFAMD_TAIL_MAX, "a thin band's rows must fit the LDS flags of k_trsv_band's sequential workgroup");
 
 // -------------------------------------------------------------------------------------------
 // Transfers never touch the legacy default stream: while ANOTHER host thread captures a graph on its
@@ -451,16 +449,12 @@ class Engine : public EngineBase {
   // read-only device array of this one (matrices, inverses, permutations) and owns only a second work
   // arena and stream; odd tiles run there, even tiles here, joined by events.  Built on first use.
   bool is_twin = false;
-  int use_twin = 1;   // number of EXTRA lanes (HIFIR_AMD_TWIN: 0 = tiles strictly one after the other)
   std::vector<std::unique_ptr<Engine<T>>> twins;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
   // S7 of the child's rows beside the level's second solve (enqueue_level): a side stream and one fork / join event per level
   hipStream_t side_stream = nullptr;
   std::vector<hipEvent_t> ev_side_fork, ev_side_join;
-  // HIFIR_AMD_LIST_EARLY=1 (round 4, measured, OFF): 3.66 -> 3.77 ms on the 1M default hierarchy -- the five fork / join pairs of
-  // the captured graph cost more than the 0.12 ms of list kernels they hide
-  int list_early = 0;
   std::vector<std::unique_ptr<DevLevel>> lv;
   DevDense dn;
   DevCsr A;
@@ -488,44 +482,16 @@ class Engine : public EngineBase {
     cur_census[(size_t)family] += n;
     if (cur_level >= 1) cur_census[(size_t)(KF_COUNT + family)] += n;
   }
-  bool use_graph = true;
-  int min_logR = 6;
-  int gemm_waves = 16;   // split-K width of the block-inverse GEMM
-  bool spmm_tiles = true;       // E / F products on the matrix cores where rows share columns (HIFIR_AMD_SPMM_TILES=0: off)
-  double spmm_tile_reuse = 2.0; // ... when a 16-row block has at least this many nonzeros per distinct column
-  bool fuse_gather = true;  // S1 fused into the L solve (HIFIR_AMD_FUSE_S1=0: separate k_gather_scale launches)
-  // The hierarchy's tail as ONE dense operator: from the first level of at most tail_rows rows downwards (the small
-  // levels and the dense block behind them are a chain of ~15 dependent launches per solve for a few thousand rows),
-  // G = M_tail^{-1}, formed at finalize by running the device's own apply on the identity, one product per solve.
-  // Only where the effective rank of the dense block equals its numerical rank (the operator bakes that rank in; the graph
-  // cache keys on the effective rank too).  HIFIR_AMD_TAIL_ROWS=0: off.
-  int64_t tail_rows = 4096;
-  int64_t tail_level = -1, tail_n = 0;
+  EngineOptions opt;  // the creation-time options (options.hpp)
+  double spmm_tile_reuse = 2.0;  // opt.spmm_tiles ... when a 16-row block has at least this many nonzeros per distinct column
+  int64_t tail_level = -1, tail_n = 0;  // the tail operator (opt.tail_rows)
   DevBuf tailG;
   double tail_probe_err = 0.0, tail_max_abs = 0.0;  // build_tail_operator: G c against the recursion on a probe, max |G|
   int tail_rejected = 0;                            // 1: not finite, 2: growth, 3: probe, 4: an error while building
-  double tail_probe_tol = 1e-11, tail_max_growth = 1e8;  // HIFIR_AMD_TAIL_PROBE_TOL / HIFIR_AMD_TAIL_GROWTH
   double finalize_seconds = 0.0, capture_ms = 0.0;  // set-up cost: hifamd_finalize, the last hipGraph capture + instantiate
   double bytes_inverses = 0.0, bytes_top = 0.0, bytes_tail = 0.0;  // resident explicit operators (HBM)
-  bool fuse_out = true;    // S7 fused into the last band of the final U solve (HIFIR_AMD_FUSE_S7=0: k_scatter_scale over all rows)
-  int spmm_tiles_z = 1;     // HIFIR_AMD_SPMM_TILES_Z=0: complex coupling blocks keep the row-gather products
-  int spmm_rb = 1;          // HIFIR_AMD_SPMM_RB: 16-row tiles per block of the tiled Schur products (1; 2 measured slower: fewer, longer chains)
-  int spmm_split_blocks = 4096;  // HIFIR_AMD_SPMM_SPLIT_BLOCKS: fewer blocks than this -> one block per workgroup (k_spmm_tile4)
-  bool spmm_split = true;  // tiled Schur products: one 16-row block per workgroup (k_spmm_tile4); HIFIR_AMD_SPMM_SPLIT=0: per wave
-  int carry_wgs = 512;   // workgroups a band's launch may add for the carried prefix of the next band (HIFIR_AMD_CARRY_WGS)
-  bool fuse_f = true;    // S5 fused into the second L solve where the plan allows (HIFIR_AMD_FUSE_F=0: separate k_spmm_epi launch)
-  int top_gemm = 4;      // top / tail operator product: 4 k_top_gemm (64-row tiles, panel through LDS, K splits); 1 k_strip_gemm_d<4>,
-                         // 2 k_strip_gemm4_d<2>, 3 k_strip_gemm4_d<4> (HIFIR_AMD_TOP_GEMM)
   DevBuf gemm_part;      // partial tiles of the K splits of k_top_gemm
   DevBuf gemm_cnt;       // ... and one arrival counter per 64-row tile (the last split to arrive adds them: no k_top_reduce launch)
-  // HIFIR_AMD_TOP_LAST=1 (round 4, measured, OFF): the K splits summed inside k_top_gemm by the last split to arrive -- nine
-  // launches fewer, same bits, but the agent-scope release / acquire fences write back and invalidate a whole L2 per
-  // workgroup: k_top_gemm 40 -> 147 us, the apply 3.67 -> 4.61 ms
-  int top_last_arriver = 0;
-  // Complex handles have both operators on request only (hifamd_set_complex_operators, before the first level): bit 0 the
-  // tail operator, bit 1 the combined tops.  Their products run through k_top_gemm_z / k_top_reduce_z whatever the
-  // switches of the real product kernels say.  Real handles: always 0 (they have both operators anyway).
-  int zop_flags = 0;
   void set_complex_operators(int flags) {
     if (flags < 0 || flags > 3) throw Error(HIFAMD_MISMATCHED_SIZES, "complex operator flags must be 0 ... 3 (HIFAMD_ZOP_TAIL | HIFAMD_ZOP_TOP)");
     if (sizeof(T) == sizeof(double)) {
@@ -534,44 +500,13 @@ class Engine : public EngineBase {
     }
     if (finalized || !host.levels.empty())
       throw Error(HIFAMD_BAD_PREC, "complex operators are a planner option: set them before the first hifamd_add_level");
-    zop_flags = flags;
-    band_opt.top_max = (flags & 2) ? zop_top_max : 0;
+    opt.zop_flags = flags;
+    opt.band.top_max = (flags & 2) ? opt.zop_top_max : 0;
   }
-  int64_t zop_top_max = 0;  // what top_max is for a real handle in the environment this handle was created under
-  int cd_dbg = 0;        // development aid (HIFIR_AMD_CD_DBG): phases of k_band_cd switched off for timing experiments
-  // ... and bit 2048 (kDbgCtPlain), which switches nothing off: k_band_ct's phase 1 gathers a tile batch in front of its own
+  // opt.cd_dbg: ... and bit 2048 (kDbgCtPlain), which switches nothing off: k_band_ct's phase 1 gathers a tile batch in front of its own
   // products, as it did before its requests ran ahead -- the same sums in the same order, the same bits; the tests' second opinion
   static constexpr int kDbgCtPlain = 2048;
-  // Column-sliced component bands (kernels.hip.hpp k_band_cs): a component band of at most cs_max_wgs workgroups is cut
-  // into 16-column slices (the heaviest component of a narrow band then runs on four compute units); a batch of fewer
-  // than 49 columns runs EVERY component band sliced and launches only the slices it has.  HIFIR_AMD_CS=0: off.
-  int cs_mode = 1;
-  // Two launches for a component band whose slowest wave would walk many entries: the entries of ALL its rows that refer
-  // to rows outside their component go to a chip-wide prefix pass (every wave of the chip takes rows, perfectly balanced),
-  // and the band kernel is left with right-hand sides -> inverse product -> stores.  One launch more (~ 8 us) against the
-  // serial walk of the band's longest chunk at ~ 120 ns per entry.  HIFIR_AMD_CD_SPLIT_MIN: entries of the
-  // longest chunk from which a band is split (0 = never); HIFIR_AMD_CD_SPLIT_WGS: only bands of at most this many components
-  int cd_split_min = 0, cd_split_wgs = 600;
-  int narrow_spmm = 1;   // HIFIR_AMD_NARROW_SPMM=0: batches of <= 32 columns keep the 64-lane Schur product kernel
-  int cs_sparse = 0;     // HIFIR_AMD_CS_SPARSE=1: sparse-own bands (level 0) in column slices at full width too
-  int device_inverses = 1;  // HIFIR_AMD_DEVICE_INVERSES=0: the block inverses of finalize are formed by the host threads and uploaded
-  int cs_max_wgs = 0;    // HIFIR_AMD_CS_MAX_WGS (full batches: measured equal to k_band_cd at every band width)
-  int ct_wide_wgs = 128; // HIFIR_AMD_CT_WIDE: a component band with more workgroups than this takes two column tiles per workgroup
-  int ct_wide4_wgs = 1 << 30;  // HIFIR_AMD_CT_WIDE4: ... and with more than this all four (one workgroup per component)
-  int us_mode = 1;  // HIFIR_AMD_US=0: sparse-own U bands keep every row of a component in LDS (k_band_cd)
-  int ls_mode = 1;  // HIFIR_AMD_LS=0: sparse-own L bands keep every row of a component in LDS (k_band_cd; the same bits)
-  int ls_chunk = 0;  // HIFIR_AMD_LS_CHUNK=32/48/64: rows of k_band_ls's source chunk (0: the largest that fits 80 KB of LDS)
-  int narrow_tiles = 1;  // HIFIR_AMD_NARROW_TILES=0: the tiled Schur products always multiply all four column tiles
-  int skip_rows = 3;  // HIFIR_AMD_SKIP_ROWS: bit 0 L rows / bit 1 U rows a level's first solve does not store (build_row_flags); 0: every row
-  int ct_mode_real = 1;  // HIFIR_AMD_CT_REAL=0: real handles keep the entry walk while HIFIR_AMD_CT_Z stays as set (tests)
-  int ct_mode_z = 0;     // HIFIR_AMD_CT_Z=1: complex component bands on coefficient tiles too (k_band_ct_z; measured SLOWER than the
-                         // entry walk at every width on BASELINE config 5: 7.17 vs 7.00 ms at 16, 17.9 vs 16.1 ms at 64 columns)
-  int ct_mode = 1;       // HIFIR_AMD_CT=0: dense-own component bands walk their entries one by one (k_band_cd / k_band_cs) instead of
-                         // multiplying 16 x 4 coefficient tiles on the matrix cores (k_band_ct)
   int act_cols = 64;     // columns of the 64-column arena that the tile being enqueued actually uses (enqueue_apply)
-  int xcd_remap = 1;     // HIFIR_AMD_XCD=0: workgroups numbered as the hardware deals them (one device-wide word, set by the last finalize)
-  int band_pipe = 1;     // 1: k_trsv_band_p (next row's head behind the last gathers), 0: k_trsv_band at R = 64 too
-  BandOptions band_opt;  // how triangles are cut into bands (host.hpp)
   DevBuf errflag;        // sticky error word: a bounded spin of k_trsv_band expired
 #ifdef HIFAMD_PROBE
   DevBuf probe;          // development probe (make PROBE=1): wave timestamps of k_trsv_band, dumped at destruction
@@ -615,83 +550,12 @@ class Engine : public EngineBase {
   DevBuf nsp_Q, nsp_cpart, nsp_C;
   DevBuf gm_Q, gm_Z, gm_alpha;  // GMRES: Krylov basis, per-column coefficients (its work vectors: kr_vec)
   int64_t ir_cols = 0;
-  // how resid_dev forms r = b - A x: 0 working precision (k_crs_spmm), 1 compensated (k_crs_resid_dd); from the
-  // environment at creation (import.hpp resid_mode_from_env), hifamd_set_residual_precision later
-  int resid_mode = 0;
 
-  explicit Engine(int dev) : device(dev) {
-    // Import and host-side analysis (CCS -> CSR, level schedules, dense QRCP) need no GPU; the
-    // device is bound in finalize(), and every compute entry point requires a finalized handle.
-    use_graph = env_int("HIFIR_AMD_NO_GRAPH", 0) == 0;
-    min_logR = std::min(6, std::max(0, env_int("HIFIR_AMD_MIN_LOGR", 6)));
-    gemm_waves = env_int("HIFIR_AMD_GEMM_WAVES", 16);
-    band_pipe = env_int("HIFIR_AMD_BAND_PIPE", 1);
-    cd_dbg = env_int("HIFIR_AMD_CD_DBG", 0);
-    cs_mode = env_int("HIFIR_AMD_CS", 1);
-    cs_max_wgs = env_int("HIFIR_AMD_CS_MAX_WGS", 0);
-    ct_mode = env_int("HIFIR_AMD_CT", 1);
-    ct_mode_z = env_int("HIFIR_AMD_CT_Z", 0);
-    ct_mode_real = env_int("HIFIR_AMD_CT_REAL", 1);
-    skip_rows = env_int("HIFIR_AMD_SKIP_ROWS", 3);
-    narrow_tiles = env_int("HIFIR_AMD_NARROW_TILES", 1);
-    us_mode = env_int("HIFIR_AMD_US", 1);
-    ls_mode = env_int("HIFIR_AMD_LS", 1);
-    ls_chunk = env_int("HIFIR_AMD_LS_CHUNK", 0);
-    top_last_arriver = env_int("HIFIR_AMD_TOP_LAST", 0);
-    list_early = env_int("HIFIR_AMD_LIST_EARLY", 0);
-    spmm_rb = env_int("HIFIR_AMD_SPMM_RB", 1) == 2 ? 2 : 1;
-    spmm_tiles_z = env_int("HIFIR_AMD_SPMM_TILES_Z", 1);
-    spmm_split_blocks = env_int("HIFIR_AMD_SPMM_SPLIT_BLOCKS", 4096);
-    ct_wide_wgs = env_int("HIFIR_AMD_CT_WIDE", 128);
-    ct_wide4_wgs = env_int("HIFIR_AMD_CT_WIDE4", 1 << 30);
-    cs_sparse = env_int("HIFIR_AMD_CS_SPARSE", 0);
-    device_inverses = env_int("HIFIR_AMD_DEVICE_INVERSES", 1);
-    narrow_spmm = env_int("HIFIR_AMD_NARROW_SPMM", 1);
-    cd_split_min = env_int("HIFIR_AMD_CD_SPLIT_MIN", 0);
-    cd_split_wgs = env_int("HIFIR_AMD_CD_SPLIT_WGS", 600);
-    top_gemm = env_int("HIFIR_AMD_TOP_GEMM", 4);
-    fuse_f = env_int("HIFIR_AMD_FUSE_F", 1) != 0;
-    carry_wgs = std::max(1, env_int("HIFIR_AMD_CARRY_WGS", 512));
-    spmm_split = env_int("HIFIR_AMD_SPMM_SPLIT", 1) != 0;
-    fuse_out = env_int("HIFIR_AMD_FUSE_S7", 1) != 0;
-    tail_rows = env_int("HIFIR_AMD_TAIL_ROWS", 4096);
-    if (const char *e = getenv("HIFIR_AMD_TAIL_PROBE_TOL")) tail_probe_tol = atof(e);
-    if (const char *e = getenv("HIFIR_AMD_TAIL_GROWTH")) tail_max_growth = atof(e);
-    fuse_gather = env_int("HIFIR_AMD_FUSE_S1", 1) != 0;
-    spmm_tiles = env_int("HIFIR_AMD_SPMM_TILES", 1) != 0;
-    use_twin = env_int("HIFIR_AMD_TWIN", 1);
-    resid_mode = resid_mode_from_env();
-    xcd_remap = env_int("HIFIR_AMD_XCD", 1);
-    band_opt.thin_rows = env_int("HIFIR_AMD_THIN_ROWS", 96);
-    band_opt.band_depth = env_int("HIFIR_AMD_BAND_DEPTH", 32);
-    band_opt.max_wgs = env_int("HIFIR_AMD_BAND_WGS", 1024);
-    band_opt.max_comp_weight = env_int("HIFIR_AMD_BAND_WEIGHT", 1024);
-    band_opt.max_wg_rows = HIFAMD_TAIL_MAX;
-    band_opt.dense_block = env_int("HIFIR_AMD_DENSE_BLOCK", 2048);  // 0: exact sequential thin bands
-    // carried prefixes (host.hpp finish_band_plan): real data only -- measured on the complex 1M-row case (one
-    // workgroup per compute unit, rows of 1 KB) they lose at every threshold (18.8 ms without, 19.7 ... 20.6 ms with)
-    band_opt.fuse = env_int("HIFIR_AMD_BAND_FUSE", sizeof(T) == sizeof(double) ? 1 : 0) != 0;
-    band_opt.fuse_reorder = band_opt.dense_block > 0;                  // exact mode keeps the reference's order
-    band_opt.fuse_max_wgs = env_int("HIFIR_AMD_BAND_FUSE_WGS", 512);
-    band_opt.cd_fuse_max_wgs = env_int("HIFIR_AMD_CD_FUSE_WGS", 600);  // (4.26 -> 4.18 ms: the 1,216-workgroup last U band of level 1 gathers its own old sources)
-    // component-dense bands (host.hpp plan_bands_cd): real data, fast mode; HIFIR_AMD_CD_ROWS=0 keeps the depth-cut bands
-    band_opt.cd_rows = (sizeof(T) == sizeof(double) && band_opt.dense_block > 0) ? env_int("HIFIR_AMD_CD_ROWS", 128) : 0;
-    // complex handles: the same plan with 1 KB rows (k_band_cd_z keeps a component as two real planes: 96 rows = 96 KB);
-    // no sparse-own components, no combined top (both real-only)
-    if (sizeof(T) != sizeof(double) && band_opt.dense_block > 0) band_opt.cd_rows = std::min(144, env_int("HIFIR_AMD_CD_ROWS_Z", 96));
-    band_opt.cd_max_nnz = env_int("HIFIR_AMD_CD_NNZ", 4000);  // (a band lasts as long as its heaviest component: 4.53 -> 4.44 ms)
-    band_opt.cd_sparse_rows = std::min(240, env_int("HIFIR_AMD_CD_SPARSE_ROWS", 192));  // 0: thin triangles keep the flag bands
-    band_opt.top_max = env_int("HIFIR_AMD_TOP_ROWS", 4096);      // combined top operator (host.hpp choose_top); 0 = off
-    band_opt.top_few_wgs = env_int("HIFIR_AMD_TOP_WGS", 96);
-    // complex handles: no combined top unless the handle asks for it (set_complex_operators); sparse-own components for shallow thin triangles since round 4 (HIFIR_AMD_CD_SPARSE_ROWS_Z=0:
-    // those triangles keep the round-1 flag bands)
-    zop_top_max = band_opt.top_max;
-    if (sizeof(T) != sizeof(double))
-      band_opt.top_max = 0, band_opt.cd_sparse_rows = std::min(240, env_int("HIFIR_AMD_CD_SPARSE_ROWS_Z", 192)),
-      band_opt.cd_max_nnz = env_int("HIFIR_AMD_CD_NNZ_Z", 0);
-    band_opt.cd_sparse_min_rows = env_int("HIFIR_AMD_CD_SPARSE_MIN_ROWS", 4096);
-    if (band_opt.cd_rows > 240) band_opt.cd_rows = 240;  // (local row ids are bytes; 120 KB of the CU's 160 KB LDS)
-  }
+  // Import and host-side analysis (CCS -> CSR, level schedules, dense QRCP) need no GPU; the
+  // device is bound in finalize(), and every compute entry point requires a finalized handle.
+  // The handle's engine gets what EngineOptions::from_env read when the handle was created; the adjoint engine and the
+  // twin lanes, built on first use long after, get their handle's `opt` and never look at the environment.
+  Engine(int dev, const EngineOptions &o) : device(dev), opt(o) {}
 
   void bind_device() {
     int cnt = 0;
@@ -707,7 +571,7 @@ class Engine : public EngineBase {
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
-    if (sizeof(T) != sizeof(double) && zop_flags) {
+    if (sizeof(T) != sizeof(double) && opt.zop_flags) {
       HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
       HIP_OK(hipFuncSetAttribute((const void *)k_top_gemm_z<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTopGemmLds));
     }
@@ -770,10 +634,10 @@ class Engine : public EngineBase {
     // (hifamd_load of a file that carries the analysis of its levels -- import.hpp load_analysis: adopted, not redone)
     const size_t li = host.levels.size();
     const auto t_an0 = std::chrono::steady_clock::now();
-    if (li < cached_analysis.size() && adopt_analysis(H, cached_analysis[li], band_opt))
+    if (li < cached_analysis.size() && adopt_analysis(H, cached_analysis[li], opt.band))
       ++levels_from_cache;
     else
-      analyze_level(H, band_opt, env_int("HIFIR_AMD_PLAN_DUMP", 0) != 0, li);
+      analyze_level(H, opt.band, env_int("HIFIR_AMD_PLAN_DUMP", 0) != 0, li);
     analysis_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_an0).count();
     seal_level(H);  // (what finalize must find again: import.hpp verify_level)
     host.levels.push_back(std::move(H));
@@ -794,35 +658,14 @@ class Engine : public EngineBase {
   // the adjoint of one imported level (see `adj` above)
   void add_level_adjoint(const HostLevel<T> &P) {
     HostLevel<T> H = adjoint_level(P);
-    analyze_level(H, band_opt, env_int("HIFIR_AMD_PLAN_DUMP", 0) != 0, host.levels.size());
+    analyze_level(H, opt.band, env_int("HIFIR_AMD_PLAN_DUMP", 0) != 0, host.levels.size());
     seal_level(H);
     host.levels.push_back(std::move(H));
   }
 
-  // The adjoint engine and the twin lanes are built on first use, long after the handle: they run with the options the
-  // handle read from the environment when it was created, not with what the environment holds when they are built.
-  void inherit_options(const Engine<T> &P) {
-    use_graph = P.use_graph, min_logR = P.min_logR, band_opt = P.band_opt, gemm_waves = P.gemm_waves;
-    fuse_gather = P.fuse_gather, spmm_tiles = P.spmm_tiles, top_gemm = P.top_gemm, fuse_f = P.fuse_f;
-    carry_wgs = P.carry_wgs, spmm_split = P.spmm_split, fuse_out = P.fuse_out, tail_rows = P.tail_rows;
-    cd_dbg = P.cd_dbg, cs_mode = P.cs_mode, cs_max_wgs = P.cs_max_wgs;
-    ct_mode = P.ct_mode, ct_mode_z = P.ct_mode_z, ct_mode_real = P.ct_mode_real;
-    skip_rows = P.skip_rows, narrow_tiles = P.narrow_tiles, us_mode = P.us_mode, ls_mode = P.ls_mode, ls_chunk = P.ls_chunk;
-    list_early = P.list_early, spmm_rb = P.spmm_rb, spmm_tiles_z = P.spmm_tiles_z, spmm_split_blocks = P.spmm_split_blocks;
-    ct_wide_wgs = P.ct_wide_wgs, ct_wide4_wgs = P.ct_wide4_wgs, cs_sparse = P.cs_sparse, narrow_spmm = P.narrow_spmm;
-    cd_split_min = P.cd_split_min, cd_split_wgs = P.cd_split_wgs;
-    // (these five were left to the environment of the moment until the variant tests built handles under a switch and
-    // solved transposed and in two lanes after it was gone)
-    band_pipe = P.band_pipe, top_last_arriver = P.top_last_arriver, use_twin = P.use_twin;
-    device_inverses = P.device_inverses, xcd_remap = P.xcd_remap;
-    tail_probe_tol = P.tail_probe_tol, tail_max_growth = P.tail_max_growth;
-    zop_flags = P.zop_flags, zop_top_max = P.zop_top_max;  // (band_opt, copied above, carries the top_max they chose)
-    resid_mode = P.resid_mode;
-  }
-
   // the residual mode of this engine and of every engine built from it so far (those built later inherit it)
   void set_resid_mode(int mode) {
-    resid_mode = mode;
+    opt.resid_mode = mode;
     for (auto &tw : twins) tw->set_resid_mode(mode);
     if (adj) adj->set_resid_mode(mode);
   }
@@ -831,11 +674,10 @@ class Engine : public EngineBase {
     if (adjoint) throw Error(HIFAMD_HIFIR_ERROR, "internal error: adjoint of the adjoint engine");
     if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
     if (!adj) {
-      std::unique_ptr<Engine<T>> E(new Engine<T>(device));
+      std::unique_ptr<Engine<T>> E(new Engine<T>(device, opt));
       E->adjoint = true;
       E->stream = stream;
       E->owns_stream = false;
-      E->inherit_options(*this);
       for (const auto &P : host.levels) E->add_level_adjoint(P);
       if (host.has_dense && host.dense.kind == 2) {  // LUP: ?getrs 'T' / ?gemv 'C' (LUP.hpp:150,187)
         E->host.dense.kind = 2;
@@ -875,10 +717,9 @@ class Engine : public EngineBase {
 
   Engine<T> &twin_engine(int k) {
     while ((int)twins.size() <= k) {
-      std::unique_ptr<Engine<T>> E(new Engine<T>(device));
+      std::unique_ptr<Engine<T>> E(new Engine<T>(device, opt));
       E->is_twin = true;
       E->adjoint = adjoint;
-      E->inherit_options(*this);
       E->max_nrhs = max_nrhs;
       E->Rmax = Rmax;
       E->host.has_dense = host.has_dense;
@@ -937,7 +778,6 @@ class Engine : public EngineBase {
         E->gemm_cnt.alloc(gemm_cnt.bytes);
         zero_dev(E->gemm_cnt.p, E->gemm_cnt.bytes);
       }
-      E->top_last_arriver = top_last_arriver;
       if (zt1.bytes) {
         E->zt1.alloc(zt1.bytes);
         E->zt2.alloc(zt2.bytes);
@@ -1056,7 +896,7 @@ class Engine : public EngineBase {
     for (int64_t sl = 0; sl < m; ++sl) uslot[(size_t)H.Ur.rowid[(size_t)sl]] = (int32_t)sl;
     std::vector<uint8_t> fL((size_t)m, 0), fU((size_t)m, 0);
     int64_t nred = 0, nskip = 0;
-    for (int64_t sl = 0; sl < m && (skip_rows & 1); ++sl) {
+    for (int64_t sl = 0; sl < m && (opt.skip_rows & 1); ++sl) {
       if (compL[(size_t)sl] < 0 || usedL[(size_t)sl] || H.Lr.ptr[(size_t)sl + 1] != H.Lr.ptr[(size_t)sl]) continue;
       const int32_t us = uslot[(size_t)H.Lr.rowid[(size_t)sl]];
       if (us < 0 || compU[(size_t)us] < 0) continue;  // (the U kernel that touches the row first must know where to look)
@@ -1064,7 +904,7 @@ class Engine : public EngineBase {
       fU[(size_t)us] |= 2;
       ++nred;
     }
-    for (int64_t sl = 0; sl < m && (skip_rows & 2); ++sl)
+    for (int64_t sl = 0; sl < m && (opt.skip_rows & 2); ++sl)
       if (compU[(size_t)sl] >= 0 && !usedU[(size_t)sl] && !ecol[(size_t)H.Ur.rowid[(size_t)sl]]) {
         fU[(size_t)sl] |= 1;
         ++nskip;
@@ -1086,7 +926,7 @@ class Engine : public EngineBase {
   // growth again in the other direction: a band that is flagged and grows under the new values is demoted as usual).
   void ship_block_inverses(BandPlan &P, const Csr<T> &A, int64_t total_elems, DevCsr &M) {
     M.upload(A, &P);
-    if (ct_mode && (sizeof(T) == sizeof(double) ? ct_mode_real : ct_mode_z) && band_opt.dense_block > 0 && !P.cd_sparse && !P.band_cd.empty()) {
+    if (opt.ct_mode && (sizeof(T) == sizeof(double) ? opt.ct_mode_real : opt.ct_mode_z) && opt.band.dense_block > 0 && !P.cd_sparse && !P.band_cd.empty()) {
       // dense-own component bands: the entries a component reads from older rows as 16 x 4 coefficient tiles (k_band_ct)
       CtTiles Tl;
       build_ct_tiles(P, A, Tl);
@@ -1104,10 +944,10 @@ class Engine : public EngineBase {
     M.tinv.alloc((size_t)total_elems * sizeof(double));
     const bool cplx = sizeof(T) != sizeof(double);
     auto elems_of = [&](size_t q) { return dense_block_elems(P.blk_slot1[q] - P.blk_slot0[q], cplx); };
-    int64_t biggest = dense_block_elems(std::max<int64_t>(band_opt.dense_block, 32), cplx);
+    int64_t biggest = dense_block_elems(std::max<int64_t>(opt.band.dense_block, 32), cplx);
     for (size_t q = 0; q < P.blk_slot0.size(); ++q) biggest = std::max(biggest, elems_of(q));
     const size_t cap = (size_t)biggest * sizeof(double);
-    if (!device_inverses && (!pin[0] || pin_cap < cap)) {
+    if (!opt.device_inverses && (!pin[0] || pin_cap < cap)) {
       for (int k = 0; k < 2; ++k) {
         if (pin[k]) (void)hipHostFree(pin[k]);
         HIP_OK(hipHostMalloc((void **)&pin[k], cap, hipHostMallocDefault));
@@ -1117,7 +957,7 @@ class Engine : public EngineBase {
     }
     std::vector<uint8_t> bad(P.blk_slot0.size(), 0);
     const size_t nblk = P.blk_slot0.size();
-    if (device_inverses && nblk) {
+    if (opt.device_inverses && nblk) {
       // on the device (kernels.hip.hpp k_block_inverse): the factors are there already, the operators never cross PCIe
       DevBuf d0, d1, doff, dg;
       std::vector<int64_t> off64(P.blk_inv_off.begin(), P.blk_inv_off.end());
@@ -1141,10 +981,10 @@ class Engine : public EngineBase {
       for (size_t q = 0; q < nblk; ++q) {
         double g;
         std::memcpy(&g, &gbits[q], 8);
-        if (!(g <= band_opt.dense_max_growth)) bad[q] = 1;
+        if (!(g <= opt.band.dense_max_growth)) bad[q] = 1;
       }
     }
-    for (size_t q0 = device_inverses ? nblk : 0; q0 < nblk;) {
+    for (size_t q0 = opt.device_inverses ? nblk : 0; q0 < nblk;) {
       size_t q1 = q0 + 1;
       int64_t batch = elems_of(q0);
       while (q1 < nblk && batch + elems_of(q1) <= biggest && P.blk_inv_off[q1] == P.blk_inv_off[q0] + batch) batch += elems_of(q1++);
@@ -1152,12 +992,12 @@ class Engine : public EngineBase {
       HIP_OK(hipEventSynchronize(pin_done[which]));  // the copy that last used this buffer has finished
       double *buf = pin[which];
       if (q1 - q0 == 1) {
-        if (!(build_dense_block(P, A, q0, buf) <= band_opt.dense_max_growth)) bad[q0] = 1;
+        if (!(build_dense_block(P, A, q0, buf) <= opt.band.dense_max_growth)) bad[q0] = 1;
       } else {
         parallel_for((int64_t)(q1 - q0), 1, [&](int64_t i0, int64_t i1) {
           for (int64_t i = i0; i < i1; ++i) {
             const size_t q = q0 + (size_t)i;
-            if (!(build_dense_block(P, A, q, buf + (P.blk_inv_off[q] - P.blk_inv_off[q0]), true) <= band_opt.dense_max_growth)) bad[q] = 1;
+            if (!(build_dense_block(P, A, q, buf + (P.blk_inv_off[q] - P.blk_inv_off[q0]), true) <= opt.band.dense_max_growth)) bad[q] = 1;
           }
         });
       }
@@ -1192,7 +1032,7 @@ class Engine : public EngineBase {
     max_nrhs = max_nrhs_;
     Rmax = 1;
     while (Rmax < max_nrhs && Rmax < 64) Rmax <<= 1;
-    Rmax = std::max<int64_t>(Rmax, 1LL << min_logR);
+    Rmax = std::max<int64_t>(Rmax, 1LL << opt.min_logR);
     // every array the kernels index with is re-validated right before it is shipped (import.hpp): a host copy that
     // is not what the conversion must have produced is refused here instead of hanging or mis-solving on the device
     // (development aid, HIFIR_AMD_FINALIZE_DUMP=1: seconds per piece of the set-up on stderr)
@@ -1207,7 +1047,7 @@ class Engine : public EngineBase {
       ft = t;
     };
     for (size_t l = 0; l < host.levels.size(); ++l) host_repairs += verify_level(host.levels[l], l, adjoint);
-    for (size_t l = 0; l < host.levels.size(); ++l) check_level_invariants(host.levels[l], l, adjoint, &band_opt);
+    for (size_t l = 0; l < host.levels.size(); ++l) check_level_invariants(host.levels[l], l, adjoint, &opt.band);
     tick("invariants (all levels)", 0);
     bind_device();
     tick("bind device", 0);
@@ -1222,7 +1062,7 @@ class Engine : public EngineBase {
       // sparse-own L bands: the one per-row order of the own entries that k_band_ls, k_band_cd and k_band_cs share (host.hpp
       // ls_reorder_own) -- before the lists are shipped, whatever HIFIR_AMD_LS says and whatever analyzed the level
       if constexpr (std::is_same<T, double>::value) {
-        if (band_opt.dense_block > 0 && H.Lp.cd_sparse) ls_reorder_own(H.Lp);
+        if (opt.band.dense_block > 0 && H.Lp.cd_sparse) ls_reorder_own(H.Lp);
       }
       ship_block_inverses(H.Lp, H.Lr, H.Ltinv_elems, L.L);
       ship_block_inverses(H.Up, H.Ur, H.Utinv_elems, L.U);
@@ -1233,7 +1073,7 @@ class Engine : public EngineBase {
         const int32_t r0U = H.Up.grp_slot_ptr[(size_t)H.Up.wg_grp_ptr[(size_t)H.Up.band_wg_ptr[(size_t)H.top_bandU]]];
         std::vector<T> G;
         const double growth = build_top_operator(H.Lr, H.Lp, r0L, H.Ur, H.Up, r0U, H.top_n, H.d, G);
-        if (growth <= band_opt.dense_max_growth) {
+        if (growth <= opt.band.dense_max_growth) {
           L.topG.upload(mfma_operand(G.data(), H.top_n, H.top_n, round_up32(H.top_n)), 4096);  // (k zero-padded to 32; k_top_gemm reads past the end)
           L.top_n = H.top_n;
           L.top_bandL = H.top_bandL;
@@ -1244,12 +1084,12 @@ class Engine : public EngineBase {
       tick("combined top operator", fl_);
       L.E.upload(H.Er, nullptr);
       L.F.upload(H.Fr, nullptr);
-      if (spmm_tiles && band_opt.dense_block > 0 && (sizeof(T) == sizeof(double) || spmm_tiles_z))  // fast mode
+      if (opt.spmm_tiles && opt.band.dense_block > 0 && (sizeof(T) == sizeof(double) || opt.spmm_tiles_z))  // fast mode
         for (int which = 0; which < 2; ++which) {
           const Csr<T> &Ah = which ? H.Fr : H.Er;
           DevCsr &Md = which ? L.F : L.E;
           if (Ah.nrows < 64 || Ah.col.size() < 8 * (size_t)Ah.nrows) continue;  // (sparse rows share too little)
-          SpmmTiles Tl = build_spmm_tiles(Ah, spmm_rb);
+          SpmmTiles Tl = build_spmm_tiles(Ah, opt.spmm_rb);
           if (Tl.reuse < spmm_tile_reuse) continue;
           Md.tl_rb = Tl.rb;
           Md.tl_gptr.upload(Tl.blk_gptr);
@@ -1261,7 +1101,7 @@ class Engine : public EngineBase {
       // S5 fused into the second L solve (host.hpp build_cd_streams_fused): thin F rows only -- rows that share columns
       // are better served by the tiled product
       if constexpr (std::is_same<T, double>::value) {
-        if (fuse_f && fuse_gather && band_pipe && Rmax == 64 && band_opt.dense_block > 0 && H.F_ncols > 0 && H.m > 0 &&
+        if (opt.fuse_f && opt.fuse_gather && opt.band_pipe && Rmax == 64 && opt.band.dense_block > 0 && H.F_ncols > 0 && H.m > 0 &&
             L.top_n == 0 && L.F.tl_nblk == 0 && cd_f_fusable(H.Lp)) {
           CdFusedStreams<T> S;
           if (build_cd_streams_fused(H.Lp, H.Lr, H.Fr, H.n + H.m, S)) {
@@ -1279,7 +1119,7 @@ class Engine : public EngineBase {
         // knows how -- enqueue_level asks s7_kernel_ok() whether this launch's last U band runs through it
         const BandPlan &Up = H.Up;
         const int64_t nbU = Up.nbands();
-        if (fuse_out && Rmax == 64 && H.m > 0 && nbU > 0 && !Up.band_cd.empty() && Up.band_cd[(size_t)nbU - 1] &&
+        if (opt.fuse_out && Rmax == 64 && H.m > 0 && nbU > 0 && !Up.band_cd.empty() && Up.band_cd[(size_t)nbU - 1] &&
             !(L.top_n > 0 && L.top_bandU == nbU - 1) && (int64_t)H.q.size() == H.n) {
           std::vector<uint8_t> covered((size_t)H.n, 0);
           const int32_t s0 = Up.grp_slot_ptr[(size_t)Up.wg_grp_ptr[(size_t)Up.band_wg_ptr[(size_t)nbU - 1]]];
@@ -1297,8 +1137,8 @@ class Engine : public EngineBase {
         }
       }
       if constexpr (std::is_same<T, double>::value) {
-        if (skip_rows && band_opt.dense_block > 0) build_row_flags(H, L);
-        if (us_mode && band_opt.dense_block > 0 && L.U.cd_sparse && Rmax == 64) {
+        if (opt.skip_rows && opt.band.dense_block > 0) build_row_flags(H, L);
+        if (opt.us_mode && opt.band.dense_block > 0 && L.U.cd_sparse && Rmax == 64) {
           UsPlan<T> Up2;
           build_us_plan(H.Up, H.Ur, Up2);
           if (Up2.any) check_us_plan(H.Up, H.Ur, Up2);
@@ -1312,9 +1152,9 @@ class Engine : public EngineBase {
         }
       }
       if constexpr (std::is_same<T, double>::value) {
-        if (ls_mode && band_opt.dense_block > 0 && L.L.cd_sparse && Rmax == 64) {
+        if (opt.ls_mode && opt.band.dense_block > 0 && L.L.cd_sparse && Rmax == 64) {
           LsPlan<T> Lp2;
-          build_ls_plan(H.Lp, H.Lr, L.L.f_fused ? &H.Fr : nullptr, H.n + H.m, ls_chunk, Lp2);
+          build_ls_plan(H.Lp, H.Lr, L.L.f_fused ? &H.Fr : nullptr, H.n + H.m, opt.ls_chunk, Lp2);
           if (Lp2.any) check_ls_plan(H.Lp, H.Lr, Lp2, 2 * H.n);  // (the arena: w, v behind it)
           if (Lp2.any) {
             DevCsr &M = L.L;
@@ -1403,20 +1243,20 @@ class Engine : public EngineBase {
     }
 #endif
     if (sizeof(T) != sizeof(double)) {
-      const size_t rows = (size_t)std::max<int64_t>(band_opt.dense_block + 32, host.has_dense ? host.dense.n + 32 : 0);
+      const size_t rows = (size_t)std::max<int64_t>(opt.band.dense_block + 32, host.has_dense ? host.dense.n + 32 : 0);
       zt1.alloc(rows * (size_t)Rmax * 2 * sizeof(double));
       zt2.alloc(rows * (size_t)Rmax * 2 * sizeof(double));
     }
     {
-      const int remap = xcd_remap;
+      const int remap = opt.xcd_remap;
       HIP_OK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_xcd_remap), &remap, sizeof(int), 0, hipMemcpyHostToDevice, xfer_stream()));
       HIP_OK(hipStreamSynchronize(xfer_stream()));
     }
     if (top_rows_max > 0) gemm_part.alloc((size_t)kTopGemmSplits * (size_t)((top_rows_max + 63) / 64 * 64) * 64 * sizeof(T));  // (complex: partial tiles of 128 doubles a row)
     gemm_cnt.alloc(kTopGemmTilesMax * sizeof(unsigned));  // (tops and tails have at most top_max / tail_rows <= 64 x this many rows)
     zero_dev(gemm_cnt.p, gemm_cnt.bytes);
-    if (band_opt.dense_block > 0) {  // +32 rows: the MFMA kernel reads whole 32-k operand sets (masked)
-      blk_tmp.alloc((size_t)(std::max<int64_t>(band_opt.dense_block, top_rows_max) + 32) * Rmax * sizeof(T));
+    if (opt.band.dense_block > 0) {  // +32 rows: the MFMA kernel reads whole 32-k operand sets (masked)
+      blk_tmp.alloc((size_t)(std::max<int64_t>(opt.band.dense_block, top_rows_max) + 32) * Rmax * sizeof(T));
       zero_dev(blk_tmp.p, blk_tmp.bytes);
     }
     HIP_OK(hipStreamSynchronize(stream));  // (transfers were synchronous on the transfer stream)
@@ -1451,11 +1291,11 @@ class Engine : public EngineBase {
 
   void build_tail_operator() {
     // (complex handles: on request only -- hifamd_set_complex_operators, HIFAMD_ZOP_TAIL)
-    if (!std::is_same<T, double>::value && !(zop_flags & 1)) return;
-    if (tail_rows <= 0 || band_opt.dense_block <= 0 || Rmax != 64 || lv.size() < 2) return;
+    if (!std::is_same<T, double>::value && !(opt.zop_flags & 1)) return;
+    if (opt.tail_rows <= 0 || opt.band.dense_block <= 0 || Rmax != 64 || lv.size() < 2) return;
     size_t l0 = 0;
     for (size_t l = 1; l < lv.size(); ++l)
-      if (lv[l]->n <= tail_rows) {
+      if (lv[l]->n <= opt.tail_rows) {
         l0 = l;
         break;
       }
@@ -1496,7 +1336,7 @@ class Engine : public EngineBase {
     double gmax = 0.0;
     for (const T &g : G) gmax = std::max(gmax, (double)std::abs(g));
     tail_max_abs = gmax;
-    if (gmax > tail_max_growth) {
+    if (gmax > opt.tail_max_growth) {
       tail_rejected = 2;
       return;
     }
@@ -1530,7 +1370,7 @@ class Engine : public EngineBase {
         den = std::max(den, (double)std::abs(hO[i]));
       }
       tail_probe_err = den > 0.0 ? num / den : num;
-      if (!(tail_probe_err <= tail_probe_tol)) {
+      if (!(tail_probe_err <= opt.tail_probe_tol)) {
         tailG.release();
         tail_rejected = 3;
         return;
@@ -1605,7 +1445,7 @@ class Engine : public EngineBase {
   int pick_logR(int64_t nrhs) const {
     int64_t R = 1;
     while (R < nrhs && R < 64) R <<= 1;
-    return std::max(log2i(R), min_logR);
+    return std::max(log2i(R), opt.min_logR);
   }
   static unsigned grid_for(int64_t rows, int logR, int threads = 256) {
     const int64_t G = 64 >> logR, rows_per_block = (threads / 64) * G;
@@ -1649,9 +1489,9 @@ class Engine : public EngineBase {
       // unless the previous band's launch carried it
       int pre = band_has_prefix(M, b) ? 1 : 0;
       // a component band split into a chip-wide prefix pass over ALL outside sources + the band kernel without its walk
-      const bool cd_two = cd_split_min > 0 && logR == 6 && act_cols > 48 && !M.band_cd.empty() && M.band_cd[b] && !M.band_dense[b] &&
-                          !M.cd_sparse && !(LOWER && with_f) && b < M.band_chunk_max.size() && M.band_chunk_max[b] >= cd_split_min &&
-                          g1 - g0 <= cd_split_wgs && sizeof(T) == sizeof(double);
+      const bool cd_two = opt.cd_split_min > 0 && logR == 6 && act_cols > 48 && !M.band_cd.empty() && M.band_cd[b] && !M.band_dense[b] &&
+                          !M.cd_sparse && !(LOWER && with_f) && b < M.band_chunk_max.size() && M.band_chunk_max[b] >= opt.cd_split_min &&
+                          g1 - g0 <= opt.cd_split_wgs && sizeof(T) == sizeof(double);
       if (cd_two) {
         const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
         const bool touched = fused && have_carried;  // [ptr, split) was folded in (first touch included) by the previous launch
@@ -1682,14 +1522,14 @@ class Engine : public EngineBase {
         continue;
       }
       const bool cdb = !M.band_cd.empty() && M.band_cd[b] && logR == 6;
-      if ((logR == 6 && band_pipe) || cdb) {  // the overlapped pipeline (trsv_band_r64); HIFIR_AMD_BAND_PIPE=0: the first version
+      if ((logR == 6 && opt.band_pipe) || cdb) {  // the overlapped pipeline (trsv_band_r64); HIFIR_AMD_BAND_PIPE=0: the first version
         // extra workgroups for the carried prefix of the NEXT band (they run on the units this band leaves idle)
         int32_t ps0 = 0, ps1 = 0;
         unsigned extra = 0;
         if (b + 1 < nb && !M.band_fused.empty() && M.band_fused[b + 1]) {
           ps0 = M.band_slot_ptr[b + 1];
           ps1 = M.band_slot_ptr[b + 2];
-          extra = (unsigned)std::min<int64_t>(carry_wgs, std::max<int64_t>(1, ((int64_t)ps1 - ps0 + 15) / 16));
+          extra = (unsigned)std::min<int64_t>(opt.carry_wgs, std::max<int64_t>(1, ((int64_t)ps1 - ps0 + 15) / 16));
           carried = true;
         }
         if (cdb) {
@@ -1764,7 +1604,7 @@ class Engine : public EngineBase {
       kper = (int)((lda + 63) / 64 * 64);
     }
     auto kern = nct == 1 ? k_top_gemm<1> : (nct == 2 ? k_top_gemm<2> : (nct == 3 ? k_top_gemm<3> : k_top_gemm<4>));
-    const bool fused_sum = top_last_arriver && nks > 1 && tiles <= kTopGemmTilesMax && gemm_cnt.p;
+    const bool fused_sum = opt.top_last_arriver && nks > 1 && tiles <= kTopGemmTilesMax && gemm_cnt.p;
     tally(KF_TOP_GEMM);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nks), dim3(1024), kTopGemmLds, st, nt, nt, kper, G, lda, X, rowmap,
                        Out, gemm_part.as<double>(), pad, fused_sum ? gemm_cnt.as<unsigned>() : (unsigned *)nullptr);
@@ -1809,7 +1649,7 @@ class Engine : public EngineBase {
   // right-hand side; then v_T = G t_T on the matrix cores (G = U_TT^{-1} D_T^{-1} L_TT^{-1}, rows scattered by L's row ids)
   void launch_top(hipStream_t st, const DevLevel &L, int logR, int64_t &count, const FL &fl) {
     if constexpr (!std::is_same<T, double>::value)
-      if (!(zop_flags & 2)) throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle that did not ask for it");
+      if (!(opt.zop_flags & 2)) throw Error(HIFAMD_HIFIR_ERROR, "internal error: combined top operator on a complex handle that did not ask for it");
     const DevCsr &M = L.L;
     const size_t b = (size_t)L.top_bandL;
     const int64_t s0 = M.band_slot_ptr[b], s1 = M.band_slot_ptr[b + 1];
@@ -1822,17 +1662,17 @@ class Engine : public EngineBase {
     if constexpr (std::is_same<T, double>::value) {
       const int nt = (int)L.top_n;
       const int ktop = (int)round_up32(nt);
-      if (top_gemm >= 4) {
+      if (opt.top_gemm >= 4) {
         launch_top_gemm(st, nt, L.topG.as<double>(), (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0,
                         L.v.as<double>(), count);
         return;
       }
       ++count;
-      tally(top_gemm == 1 ? KF_STRIP_GEMM : KF_STRIP_GEMM4);
-      if (top_gemm == 1)
+      tally(opt.top_gemm == 1 ? KF_STRIP_GEMM : KF_STRIP_GEMM4);
+      if (opt.top_gemm == 1)
         hipLaunchKernelGGL(k_strip_gemm_d<4>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, ktop, L.topG.as<double>(), ktop,
                            (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0, L.v.as<double>());
-      else if (top_gemm == 2)
+      else if (opt.top_gemm == 2)
         hipLaunchKernelGGL(k_strip_gemm4_d<2>, dim3((unsigned)((nt + 15) / 16)), dim3(1024), 0, st, nt, ktop, L.topG.as<double>(), ktop,
                            (const double *)blk_tmp.as<double>(), M.rowid.as<int32_t>() + s0, L.v.as<double>());
       else
@@ -1846,14 +1686,14 @@ class Engine : public EngineBase {
   // rows the LDS layout of a component band kernel is built for (band_lds.hpp); dense-own plans: rounded up to a multiple
   // of 32 -- the inverse product reads whole operand sets
   int32_t cd_lds_rows(bool sparse) const {
-    return (int32_t)(sparse ? band_opt.cd_sparse_rows : ((band_opt.cd_rows + 31) & ~(int64_t)31));
+    return (int32_t)(sparse ? opt.band.cd_sparse_rows : ((opt.band.cd_rows + 31) & ~(int64_t)31));
   }
   // v_tail = G c_tail (build_tail_operator); the product reads up to 31 rows behind c_tail: they lie inside the level's
   // arena (v follows w) and meet zero columns of the operand
   bool launch_tail(hipStream_t st, const D *cin, D *zout, int64_t &count) {
     if constexpr (std::is_same<T, double>::value) {
       const int nt = (int)tail_n, kt = (int)round_up32(tail_n);
-      if (top_gemm >= 4) {  // (reads exactly the tail_n rows of c_tail: nothing behind them)
+      if (opt.top_gemm >= 4) {  // (reads exactly the tail_n rows of c_tail: nothing behind them)
         launch_top_gemm(st, nt, tailG.as<double>(), (const double *)cin, nullptr, (double *)zout, count);
         return true;
       }
@@ -1905,24 +1745,24 @@ class Engine : public EngineBase {
       // column slices (k_band_cs): narrow batches always, full batches where the band is narrow
       const int nsl = std::min(4, (act_cols + 15) / 16);
       const bool fits = (int64_t)(g1 - g0) * nsl + 4 * (int64_t)extra < (1LL << 30);
-      if (ct_mode && M.ct_on && !M.cd_sparse && !with_f && fits) {  // coefficient tiles on the matrix cores, every batch width
+      if (opt.ct_mode && M.ct_on && !M.cd_sparse && !with_f && fits) {  // coefficient tiles on the matrix cores, every batch width
         // a wide band takes two column tiles per workgroup (a coefficient tile is fetched for 32 columns at once); a narrow
         // one a workgroup per 16-column slice: its heaviest component then runs on four compute units
         const int ncols = (act_cols + 15) / 16;  // column tiles in use
-        const int nct = (ncols == 4 && g1 - g0 > ct_wide4_wgs) ? 4 : ((ncols >= 2 && g1 - g0 > ct_wide_wgs) ? 2 : 1);
+        const int nct = (ncols == 4 && g1 - g0 > opt.ct_wide4_wgs) ? 4 : ((ncols >= 2 && g1 - g0 > opt.ct_wide_wgs) ? 2 : 1);
         const int nslc = (ncols + nct - 1) / nct;
         return {nct == 4 ? KF_BAND_CT4 : (nct == 2 ? KF_BAND_CT2 : KF_BAND_CT1), (unsigned)(((g1 - g0 + 7) / 8) * 8 * nslc) + 4 * extra, 256,
                 BandCtLds(lds_rows, nct).bytes(), lds_rows, nslc, nct};
       }
-      if (!LOWER && us_mode && M.cd_sparse && nsl == 4 && !pre && !extra && !with_f && band < M.us_band_ok.size() && M.us_band_ok[band] &&
-          !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {  // black rows in LDS, sinks streamed: two workgroups per unit
+      if (!LOWER && opt.us_mode && M.cd_sparse && nsl == 4 && !pre && !extra && !with_f && band < M.us_band_ok.size() && M.us_band_ok[band] &&
+          !(opt.cs_mode && (g1 - g0 <= opt.cs_max_wgs || opt.cs_sparse))) {  // black rows in LDS, sinks streamed: two workgroups per unit
         const int32_t own_cap2 = (M.us_band_own[band] + 63) & ~63;
         const int32_t lds_black = std::max(1, M.us_band_nbk[band]);
         const size_t lds2 = BandUsLds(lds_black, own_cap2).bytes();
         if (lds2 <= kBandLdsMax) return {KF_BAND_US, n, 1024, lds2, lds_black, 1, 1, own_cap2};
       }
-      if (LOWER && ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
-          (!with_f || M.ls_fused) && !(cd_dbg & ~kDbgCtPlain) && !no_walk && !(cs_mode && (g1 - g0 <= cs_max_wgs || cs_sparse))) {
+      if (LOWER && opt.ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
+          (!with_f || M.ls_fused) && !(opt.cd_dbg & ~kDbgCtPlain) && !no_walk && !(opt.cs_mode && (g1 - g0 <= opt.cs_max_wgs || opt.cs_sparse))) {
         // dependent rows in LDS, sources through a chunk: two workgroups per unit
         const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]);
         const int32_t own_cap2 = std::max(64, (M.ls_band_own[band] + 63) & ~63), rptr_cap = (M.ls_band_rptr[band] + 3) & ~3;
@@ -1930,7 +1770,7 @@ class Engine : public EngineBase {
         const size_t lds2 = ls_lds_bytes(lds_dep, 16 * cw, own_cap2, rptr_cap);
         if (ls_kernel(cw, nch) && lds2 <= kLsLdsMax) return {KF_BAND_LS, n, 1024, lds2, lds_dep, 1, 1, own_cap2, rptr_cap, cw, nch};
       }
-      if (cs_mode && (nsl < 4 || g1 - g0 <= cs_max_wgs || (cs_sparse && M.cd_sparse)) && fits)
+      if (opt.cs_mode && (nsl < 4 || g1 - g0 <= opt.cs_max_wgs || (opt.cs_sparse && M.cd_sparse)) && fits)
         return {M.cd_sparse ? KF_BAND_CS_SPARSE : KF_BAND_CS, n * (unsigned)nsl + 4 * extra, 256,
                 BandCsLds(lds_rows, M.cd_sparse, M.own_cap).bytes(), lds_rows, nsl};
       return {M.cd_sparse ? KF_BAND_CD_SPARSE : KF_BAND_CD, n + extra, 1024, lds, lds_rows};
@@ -1939,15 +1779,15 @@ class Engine : public EngineBase {
       if (extra) throw Error(HIFAMD_HIFIR_ERROR, "internal error: carried prefix on a complex handle");
       const int nslz = std::min(4, (act_cols + 15) / 16);
       const int32_t lds_rows = cd_lds_rows(M.cd_sparse);
-      if (ct_mode && M.ct_on && !M.cd_sparse)  // coefficient tiles (round 4): 16-column slices at every batch width
+      if (opt.ct_mode && M.ct_on && !M.cd_sparse)  // coefficient tiles (round 4): 16-column slices at every batch width
         return {KF_BAND_CT_Z, n * (unsigned)nslz, 256, BandCtzLds(lds_rows).bytes(), lds_rows, nslz};
       if (M.cd_sparse) {  // sparse-own components (round 4): 16-column slices at every batch width
         const BandCszLds lay(lds_rows, true, M.own_cap);  // (lay.rows: even)
         return {KF_BAND_CS_Z, n * (unsigned)nslz, 256, lay.bytes(), lay.rows, nslz, 1, M.own_cap};
       }
-      if (cs_mode && nslz < 4 && (int64_t)(g1 - g0) * nslz < (1LL << 30))  // a narrow batch: only the slices it has
+      if (opt.cs_mode && nslz < 4 && (int64_t)(g1 - g0) * nslz < (1LL << 30))  // a narrow batch: only the slices it has
         return {KF_BAND_CS_Z, n * (unsigned)nslz, 256, BandCszLds(lds_rows, false, 0).bytes(), lds_rows, nslz};
-      const int32_t rows = (int32_t)band_opt.cd_rows;  // (two planes of 64 columns: not rounded)
+      const int32_t rows = (int32_t)opt.band.cd_rows;  // (two planes of 64 columns: not rounded)
       return {KF_BAND_CD_Z, n, 1024, BandCdzLds(rows).bytes(), rows};
     }
   }
@@ -1966,7 +1806,7 @@ class Engine : public EngineBase {
   std::vector<std::pair<const void *, size_t>> band_lds_table() const {
     std::vector<std::pair<const void *, size_t>> t;
     auto add = [&t](auto kernel, size_t bytes) { t.emplace_back((const void *)kernel, std::min(bytes, kBandLdsMax)); };
-    if (band_opt.cd_rows <= 0) return t;
+    if (opt.band.cd_rows <= 0) return t;
     const int32_t rd = cd_lds_rows(false), rs = cd_lds_rows(true);
     if constexpr (std::is_same<T, double>::value) {
       const size_t ct1 = BandCtLds(rd, 1).bytes(), ct2 = BandCtLds(rd, 2).bytes(), ct4 = BandCtLds(rd, 4).bytes();
@@ -1985,7 +1825,7 @@ class Engine : public EngineBase {
       add(k_band_ct_z<true>, BandCtzLds(rd).bytes()), add(k_band_ct_z<false>, BandCtzLds(rd).bytes());
       const size_t csd = BandCszLds(rd, false, 0).bytes(), css = BandCszLds(rs, true, kCdOwnCap).bytes();
       add(k_band_cs_z<true, false>, csd), add(k_band_cs_z<false, false>, csd), add(k_band_cs_z<true, true>, css), add(k_band_cs_z<false, true>, css);
-      const size_t cdz = BandCdzLds((int32_t)band_opt.cd_rows).bytes();
+      const size_t cdz = BandCdzLds((int32_t)opt.band.cd_rows).bytes();
       add(k_band_cd_z<true>, cdz), add(k_band_cd_z<false>, cdz);
     }
     return t;
@@ -1997,7 +1837,7 @@ class Engine : public EngineBase {
     const BandChoice c = choose_band<LOWER>(M, g0, g1, pre, extra, with_f, band, no_walk);
     const dim3 grid(c.grid), block(c.block);
     const int first_u = pre ? 0 : 1;  // (the packed streams already start at split[] for a carried band, at ptr[] otherwise)
-    const int dbg = cd_dbg | (no_walk ? 1 : 0);
+    const int dbg = opt.cd_dbg | (no_walk ? 1 : 0);
     const int32_t n_band = g1 - g0;
     tally(c.family);
     if constexpr (std::is_same<T, double>::value) {
@@ -2009,7 +1849,7 @@ class Engine : public EngineBase {
       case KF_BAND_CT1:
       case KF_BAND_CT2:
       case KF_BAND_CT4: {
-        const bool ct_ahead = !(cd_dbg & kDbgCtPlain);
+        const bool ct_ahead = !(opt.cd_dbg & kDbgCtPlain);
         auto kct = ct_ahead ? (c.nct == 4 ? k_band_ct<LOWER, 4, true> : (c.nct == 2 ? k_band_ct<LOWER, 2, true> : k_band_ct<LOWER, 1, true>))
                             : (c.nct == 4 ? k_band_ct<LOWER, 4, false> : (c.nct == 2 ? k_band_ct<LOWER, 2, false> : k_band_ct<LOWER, 1, false>));
         hipLaunchKernelGGL(kct, grid, block, c.lds, st, g0,
@@ -2157,9 +1997,9 @@ class Engine : public EngineBase {
     const unsigned pairs = (unsigned)(((nb + 15) / 16 + 1) / 2);
     const dim3 grid(pairs, ((1u << logR) + 15) / 16);
     tally(KF_TRI_GEMM);
-    if (gemm_waves >= 16)
+    if (opt.gemm_waves >= 16)
       hipLaunchKernelGGL(k_tri_gemm_d<16>, grid, dim3(1024), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
-    else if (gemm_waves >= 8)
+    else if (opt.gemm_waves >= 8)
       hipLaunchKernelGGL(k_tri_gemm_d<8>, grid, dim3(512), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
     else
       hipLaunchKernelGGL(k_tri_gemm_d<4>, grid, dim3(256), 0, st, nb, Aops, lda, X, logR, rowmap, Out, dscale, Out2);
@@ -2212,8 +2052,8 @@ class Engine : public EngineBase {
     if constexpr (std::is_same<T, double>::value) {
       // one block per workgroup, its groups dealt to the four waves: where the per-wave kernel would leave the chip short
       // of waves (with more blocks the product runs at the fabric's gather bandwidth either way: 95 vs 100 us, 101 vs 123 us)
-      const int nct = narrow_tiles ? std::min(4, (act_cols + 15) / 16) : 4;  // column tiles of the batch
-      if (A.tl_nblk > 0 && A.tl_nblk < spmm_split_blocks && logR == 6 && spmm_split) {
+      const int nct = opt.narrow_tiles ? std::min(4, (act_cols + 15) / 16) : 4;  // column tiles of the batch
+      if (A.tl_nblk > 0 && A.tl_nblk < opt.spmm_split_blocks && logR == 6 && opt.spmm_split) {
         auto k4 = A.tl_rb == 2 ? (nct == 1 ? k_spmm_tile4<2, 1> : nct == 2 ? k_spmm_tile4<2, 2> : nct == 3 ? k_spmm_tile4<2, 3> : k_spmm_tile4<2, 4>)
                                : (nct == 1 ? k_spmm_tile4<1, 1> : nct == 2 ? k_spmm_tile4<1, 2> : nct == 3 ? k_spmm_tile4<1, 3> : k_spmm_tile4<1, 4>);
         tally(A.tl_rb == 2 ? KF_SPMM_TILE4_RB2 : KF_SPMM_TILE4_RB1);
@@ -2245,7 +2085,7 @@ class Engine : public EngineBase {
       }
     }
     // a narrow batch in the 64-column arena: 64 / R rows per wave (R = 16 or 32 lanes per row)
-    if (logR == 6 && narrow_spmm && act_cols <= 32) {
+    if (logR == 6 && opt.narrow_spmm && act_cols <= 32) {
       const int lr = act_cols <= 16 ? 4 : 5;
       tally(KF_SPMM_EPI_NARROW);
       hipLaunchKernelGGL((k_spmm_epi_narrow<D>), dim3(grid_for(nrows, lr)), dim3(256), 0, st, nrows, A.ptr.as<int32_t>(),
@@ -2288,11 +2128,11 @@ class Engine : public EngineBase {
     D *w = L.w.as<D>(), *v = L.v.as<D>();
     const bool last = (l + 1 == lv.size());
     // S1 (:359, :402) fused into the L solve that follows it (kernels FirstL): the R = 64 band pipeline only
-    const bool fuse_s1 = fuse_gather && logR == 6 && band_pipe && m > 0;
+    const bool fuse_s1 = opt.fuse_gather && logR == 6 && opt.band_pipe && m > 0;
     cur_level = (int)l;
     const FL fl{bin, ldb, nrhs, L.p.as<int32_t>(), L.s.as<double>()};
     const bool fuse_f_lv = fuse_s1 && L.L.f_fused;  // S5 fused as well (level with thin F rows, all-component L plan)
-    const bool fuse_s7_lv = fuse_out && logR == 6 && m > 0 && L.s7_n >= 0 && s7_kernel_ok(L);
+    const bool fuse_s7_lv = opt.fuse_out && logR == 6 && m > 0 && L.s7_n >= 0 && s7_kernel_ok(L);
     int64_t early_rows = 0;  // rows of the S7 list already sent out on the side stream
     int64_t c0 = count;
     if (m && !fuse_s1) {  // S1  :359
@@ -2323,7 +2163,7 @@ class Engine : public EngineBase {
       cur_level = (int)l;
       // S7 of the child's rows (:411) needs nothing of this level's second solve: it leaves now, on the side stream, beside
       // S5 / S6 (whose component bands are latency-bound and leave the memory system room); joined at the end of the level
-      if (fuse_s7_lv && list_early && L.s7_child > 0) {
+      if (fuse_s7_lv && opt.list_early && L.s7_child > 0) {
         c0 = count;
         side_fork(st, l);
         launch_s7_list(side_stream, L, v, 0, L.s7_child, yout, ldy, nrhs);
@@ -2584,7 +2424,7 @@ class Engine : public EngineBase {
     if (kind == 1) ensure_prod_buffers();
     hipStream_t st = user ? user : stream;
     const int ntiles = (int)((nrhs + 63) / 64);
-    const int nl = std::min(ntiles, 1 + std::max(0, use_twin));  // lanes: this engine + its twins
+    const int nl = std::min(ntiles, 1 + std::max(0, opt.use_twin));  // lanes: this engine + its twins
     if (nl > 1 && !is_twin) {  // tile t runs on lane t % nl, all lanes in flight
       if (!ev_fork) HIP_OK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
       HIP_OK(hipEventRecord(ev_fork, st));
@@ -2823,7 +2663,7 @@ class Engine : public EngineBase {
 
   void launch_part(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int64_t rank, hipStream_t st, int kind,
                    int tfirst, int tstride) {
-    if (!use_graph) {
+    if (!opt.use_graph) {
       last_launches = enqueue_apply(st, dB, ldb, dX, ldx, nrhs, rank, kind, nullptr, tfirst, tstride);
       last_map = cur_map;
       last_census = cur_census;
@@ -2957,7 +2797,7 @@ class Engine : public EngineBase {
                     hipStream_t user) {
     residual_check(dB, ldb, dX, ldx, dR, ldr, nrhs);
     HIP_OK(hipSetDevice(device));
-    resid_dev(dB, ldb, dX, ldx, dR, ldr, nrhs, mode < 0 ? resid_mode : mode, user);
+    resid_dev(dB, ldb, dX, ldx, dR, ldr, nrhs, mode < 0 ? opt.resid_mode : mode, user);
   }
   DevBuf stage_r;
   void residual_host(const T *B, int64_t ldb, const T *X, int64_t ldx, T *R, int64_t ldr, int64_t nrhs, int mode) {
@@ -2972,7 +2812,7 @@ class Engine : public EngineBase {
     HIP_OK(hipMemcpy2DAsync(stage_b.p, row, B, ldb * sizeof(T), row, n, hipMemcpyHostToDevice, stream));
     HIP_OK(hipMemcpy2DAsync(stage_x.p, row, X, ldx * sizeof(T), row, n, hipMemcpyHostToDevice, stream));
     resid_dev((const D *)stage_b.as<D>(), nrhs, (const D *)stage_x.as<D>(), nrhs, stage_r.as<D>(), nrhs, nrhs,
-              mode < 0 ? resid_mode : mode);
+              mode < 0 ? opt.resid_mode : mode);
     HIP_OK(hipMemcpy2DAsync(R, ldr * sizeof(T), stage_r.p, row, row, n, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
   }
@@ -3026,7 +2866,7 @@ class Engine : public EngineBase {
       for (int i = 0; i < nirs; ++i) {
         vec_op(1, n, nrhs, xk, nrhs, dX, ldx, nullptr, 0);
         if (i)
-          resid_dev(dB, ldb, xk, nrhs, r, nrhs, nrhs, resid_mode);
+          resid_dev(dB, ldb, xk, nrhs, r, nrhs, nrhs, opt.resid_mode);
         else
           vec_op(1, n, nrhs, r, nrhs, dB, ldb, nullptr, 0);
         // M.solve(x, _r): the reference solves into _r and then x = _r + _xk (:102-103)
@@ -3067,7 +2907,7 @@ class Engine : public EngineBase {
       nactive = 0;
       for (char a : active) nactive += a;
       if (!nactive) break;
-      resid_dev(dB, ldb, dX, ldx, r, nrhs, nrhs, resid_mode);  // r = b - A x
+      resid_dev(dB, ldb, dX, ldx, r, nrhs, nrhs, opt.resid_mode);  // r = b - A x
       col_norms(r, nrhs, n, nrhs, rnorm);
       for (int64_t c = 0; c < nrhs; ++c) {
         if (!active[(size_t)c]) continue;
@@ -3287,7 +3127,7 @@ class Engine : public EngineBase {
     const int max_outer = (maxit + restart - 1) / restart;  // :43
     for (int outer = 0; outer < max_outer && gm_ctl_host[2] > 0; ++outer) {
       if (outer) {
-        resid_dev(dB, ldb, (const D *)dX, ldx, v, nc, nc, resid_mode);  // v = b - A x  (:48-50)
+        resid_dev(dB, ldb, (const D *)dX, ldx, v, nc, nc, opt.resid_mode);  // v = b - A x  (:48-50)
         gm_step(n, nc, v, nullptr, nullptr, S);
       }  // (outer == 0: the partial sums of |b|^2 are still in place)
       gm_finish(nc, 2, 0, 0, S);                        // beta, y[0], active mask  (:53-54)
@@ -3707,7 +3547,7 @@ class Engine : public EngineBase {
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
     int steps = 0, go = 1;
     for (int cycle = 0; go != 0; ++cycle) {
-      if (cycle > 0) resid_dev(dB, ldb, (const D *)dX, ldx, Rh, nc, nc, resid_mode);  // the true residual
+      if (cycle > 0) resid_dev(dB, ldb, (const D *)dX, ldx, Rh, nc, nc, opt.resid_mode);  // the true residual
       hipLaunchKernelGGL((k_cg_dot<D>), dim3(kCgBlocks), dim3(256), 0, stream, n, nc, (const D *)Rh, (int64_t)nc,
                          (const D *)nullptr, pt);
       hipLaunchKernelGGL((k_bgcr_rho<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, cycle, steps, S);
@@ -4097,10 +3937,10 @@ class Engine : public EngineBase {
   void save(std::FILE *f, int flags = 0) const {
     if (adjoint || is_twin) throw Error(HIFAMD_HIFIR_ERROR, "internal engines are not saved");
     save_hierarchy(f, host);
-    if (flags & HIFAMD_SAVE_ANALYSIS) save_analysis(f, host, band_opt);
+    if (flags & HIFAMD_SAVE_ANALYSIS) save_analysis(f, host, opt.band);
   }
   void load(std::FILE *f) {
-    if (env_int("HIFIR_AMD_LOAD_ANALYSIS", 1)) load_analysis<T>(f, band_opt, cached_analysis);
+    if (env_int("HIFIR_AMD_LOAD_ANALYSIS", 1)) load_analysis<T>(f, opt.band, cached_analysis);
     try {
       load_hierarchy<T>(f, *this);
     } catch (...) {
@@ -4233,11 +4073,11 @@ class Engine : public EngineBase {
       }
     }
     const double v[] = {finalize_seconds, capture_ms,     bytes_inverses,  bytes_top,     bytes_tail,           (double)tail_n,
-                        (double)tail_level, tail_probe_err, tail_max_abs, (double)tail_rejected, tail_probe_tol, tail_max_growth,
+                        (double)tail_level, tail_probe_err, tail_max_abs, (double)tail_rejected, opt.tail_probe_tol, opt.tail_max_growth,
                         (double)levels_from_cache, analysis_seconds, arena, (double)Rmax, tiles, factors, (double)max_nrhs,
                         skip_w, skip_v, (double)host_repairs,
                         (double)(nsp_Q.bytes + (adj ? adj->nsp_Q.bytes : 0)), ls_src, ls_dep, ls_c,
-                        cd_comps, cd_shared, ls_nch, (double)zop_flags};
+                        cd_comps, cd_shared, ls_nch, (double)opt.zop_flags};
     const int nv = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < cap && i < nv; ++i) o[i] = v[i];
     return nv;
@@ -4416,9 +4256,9 @@ HifAmdStatus hifamd_create(HifAmdValueType vt, int device, HifAmdHdl *out) {
   try {
     EngineBase *e = nullptr;
     if (vt == HIFAMD_D)
-      e = new Engine<double>(device);
+      e = new Engine<double>(device, EngineOptions::from_env(false));
     else if (vt == HIFAMD_Z)
-      e = new Engine<zdouble>(device);
+      e = new Engine<zdouble>(device, EngineOptions::from_env(true));
     else
       throw Error(HIFAMD_BAD_PREC, "unknown value type");
     HifAmdPrec *h = new HifAmdPrec{(int)vt, e};
@@ -4807,7 +4647,7 @@ HifAmdStatus hifamd_set_residual_precision(HifAmdHdl h, int mode) {
 
 int hifamd_residual_precision(HifAmdHdl h) {
   if (!h || !h->eng) return -1;
-  return visit(h, [](auto &E) { return E.resid_mode; });
+  return visit(h, [](auto &E) { return E.opt.resid_mode; });
 }
 
 HifAmdStatus hifamd_residual_batch(HifAmdHdl h, HifAmdOp op, const void *B, int64_t ldb, const void *X, int64_t ldx, void *R,

@@ -299,7 +299,7 @@ struct BandPlan {
 constexpr int kCdDescWords = 28;  // 112 bytes per component descriptor (BandPlan::cd_desc)
 constexpr int kCdOwnCap = 4096;   // own nonzeros of a sparse component that k_band_cd keeps in LDS
 
-struct BandOptions {
+struct BandOptions {  // (the values a handle ships with are in options.hpp; these are what host programs default-construct)
   int64_t thin_rows = 96;    // a wavefront this narrow belongs to a thin run
   int64_t band_depth = 32;   // at most this many wavefronts per band outside thin runs
   int64_t max_comp_weight = 1024;  // ... and a band stops growing before one component gets heavier

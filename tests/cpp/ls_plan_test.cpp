@@ -9,13 +9,10 @@
 //   * prints, per qualifying L band, the table of rows / sources / dependent rows / own entries / depth levels.
 // Built and run by tests/test_ls_plan_host.py (g++ -ffp-contract=off, -fsanitize=address,undefined; no GPU).
 #include "import.hpp"
+#include "options.hpp"  // env_int; the planner options below stay this program's own list
 #include <random>
 using namespace hifamd;
 
-static int env_int(const char *name, int dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
 static int g_bad = 0;
 static long g_bands = 0, g_comps = 0, g_multi_chunk = 0;
 #define EXPECT(c, what)                                              \

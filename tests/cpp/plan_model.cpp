@@ -7,13 +7,9 @@
 //   g++ -O2 -std=c++17 -pthread -I hifir_amd/csrc tests/cpp/plan_model.cpp -o /tmp/plan_model
 //   /tmp/plan_model hier.hifamd > plan.jsonl
 #include "import.hpp"
+#include "options.hpp"  // env_int; the planner options below stay this program's own list
 #include <set>
 using namespace hifamd;
-
-static int env_int(const char *name, int dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
 
 struct Sink {
   BandOptions opt;

@@ -566,7 +566,7 @@ def test_band_wgs_rows_share_workgroups(v, hier):
 # ---- the table guard (CPU) ----------------------------------------------------------------------------------------------
 def test_every_switch_has_a_row():
     read = set()
-    for f in ("engine.hip", "host.hpp"):
+    for f in ("engine.hip", "host.hpp", "options.hpp"):
         with open(os.path.join(ROOT, "hifir_amd", "csrc", f)) as fh:
             read |= set(re.findall(PFX + r"([A-Z0-9_]+)", fh.read()))
     table = switches_in_table()
