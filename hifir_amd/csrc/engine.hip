@@ -506,6 +506,9 @@ class Engine : public EngineBase {
   // opt.cd_dbg: ... and bit 2048 (kDbgCtPlain), which switches nothing off: k_band_ct's phase 1 gathers a tile batch in front of its own
   // products, as it did before its requests ran ahead -- the same sums in the same order, the same bits; the tests' second opinion
   static constexpr int kDbgCtPlain = 2048;
+  // ... and bit 4096 (kDbgSpmmPlain), which switches nothing off either: k_spmm_tile / k_spmm_tile4 run the group loop and the epilogue of
+  // before their requests ran ahead (the second template instance) -- the same sums in the same order, the same bits
+  static constexpr int kDbgSpmmPlain = 4096;
   int act_cols = 64;     // columns of the 64-column arena that the tile being enqueued actually uses (enqueue_apply)
   DevBuf errflag;        // sticky error word: a bounded spin of k_trsv_band expired
 #ifdef HIFAMD_PROBE
@@ -1762,7 +1765,7 @@ class Engine : public EngineBase {
         if (lds2 <= kBandLdsMax) return {KF_BAND_US, n, 1024, lds2, lds_black, 1, 1, own_cap2};
       }
       if (LOWER && opt.ls_mode && M.cd_sparse && nsl == 4 && !pre && !extra && band < M.ls_band_ok.size() && M.ls_band_ok[band] &&
-          (!with_f || M.ls_fused) && !(opt.cd_dbg & ~kDbgCtPlain) && !no_walk && !(opt.cs_mode && (g1 - g0 <= opt.cs_max_wgs || opt.cs_sparse))) {
+          (!with_f || M.ls_fused) && !(opt.cd_dbg & ~(kDbgCtPlain | kDbgSpmmPlain)) && !no_walk && !(opt.cs_mode && (g1 - g0 <= opt.cs_max_wgs || opt.cs_sparse))) {
         // dependent rows in LDS, sources through a chunk: two workgroups per unit
         const int cw = M.ls_band_cw[band], nch = std::max(2, M.ls_band_nch[band]);
         const int32_t own_cap2 = std::max(64, (M.ls_band_own[band] + 63) & ~63), rptr_cap = (M.ls_band_rptr[band] + 3) & ~3;
@@ -2047,15 +2050,31 @@ class Engine : public EngineBase {
 
   // S3 / S5: out = s[p] b[p] - A x.  R = 64, fast mode, real data, rows that share columns: on the matrix cores
   // (k_spmm_tile); otherwise the row-gather kernel in the reference's summation order (k_spmm_epi)
+  // the instance of the tiled products: row tiles per block, column tiles of the batch, requests running ahead or the former loop
+  typedef void (*SpmmTileKernel)(int64_t, int64_t, const int32_t *, const int32_t *, const double *, const double *, IoPtr<const double>,
+                                 int64_t, int, const int32_t *, const double *, int64_t, double *);
+  template <bool AHEAD>
+  static SpmmTileKernel spmm_tile_kernel_of(int rb, int nct) {
+    return rb == 2 ? (nct == 1 ? k_spmm_tile<2, 1, AHEAD> : nct == 2 ? k_spmm_tile<2, 2, AHEAD> : nct == 3 ? k_spmm_tile<2, 3, AHEAD> : k_spmm_tile<2, 4, AHEAD>)
+                   : (nct == 1 ? k_spmm_tile<1, 1, AHEAD> : nct == 2 ? k_spmm_tile<1, 2, AHEAD> : nct == 3 ? k_spmm_tile<1, 3, AHEAD> : k_spmm_tile<1, 4, AHEAD>);
+  }
+  template <bool AHEAD>
+  static SpmmTileKernel spmm_tile4_kernel_of(int rb, int nct) {
+    return rb == 2 ? (nct == 1 ? k_spmm_tile4<2, 1, AHEAD> : nct == 2 ? k_spmm_tile4<2, 2, AHEAD> : nct == 3 ? k_spmm_tile4<2, 3, AHEAD> : k_spmm_tile4<2, 4, AHEAD>)
+                   : (nct == 1 ? k_spmm_tile4<1, 1, AHEAD> : nct == 2 ? k_spmm_tile4<1, 2, AHEAD> : nct == 3 ? k_spmm_tile4<1, 3, AHEAD> : k_spmm_tile4<1, 4, AHEAD>);
+  }
+  static SpmmTileKernel spmm_tile_kernel(int rb, int nct, bool ahead) { return ahead ? spmm_tile_kernel_of<true>(rb, nct) : spmm_tile_kernel_of<false>(rb, nct); }
+  static SpmmTileKernel spmm_tile4_kernel(int rb, int nct, bool ahead) { return ahead ? spmm_tile4_kernel_of<true>(rb, nct) : spmm_tile4_kernel_of<false>(rb, nct); }
+
   void launch_spmm(hipStream_t st, const DevCsr &A, int64_t nrows, const D *x, InP bin, int64_t ldb, int nrhs,
                    const DevLevel &L, int64_t roff, D *out, int logR) {
     if constexpr (std::is_same<T, double>::value) {
       // one block per workgroup, its groups dealt to the four waves: where the per-wave kernel would leave the chip short
       // of waves (with more blocks the product runs at the fabric's gather bandwidth either way: 95 vs 100 us, 101 vs 123 us)
       const int nct = opt.narrow_tiles ? std::min(4, (act_cols + 15) / 16) : 4;  // column tiles of the batch
+      const bool ahead = !(opt.cd_dbg & kDbgSpmmPlain);
       if (A.tl_nblk > 0 && A.tl_nblk < opt.spmm_split_blocks && logR == 6 && opt.spmm_split) {
-        auto k4 = A.tl_rb == 2 ? (nct == 1 ? k_spmm_tile4<2, 1> : nct == 2 ? k_spmm_tile4<2, 2> : nct == 3 ? k_spmm_tile4<2, 3> : k_spmm_tile4<2, 4>)
-                               : (nct == 1 ? k_spmm_tile4<1, 1> : nct == 2 ? k_spmm_tile4<1, 2> : nct == 3 ? k_spmm_tile4<1, 3> : k_spmm_tile4<1, 4>);
+        auto k4 = spmm_tile4_kernel(A.tl_rb, nct, ahead);
         tally(A.tl_rb == 2 ? KF_SPMM_TILE4_RB2 : KF_SPMM_TILE4_RB1);
         hipLaunchKernelGGL(k4, dim3((unsigned)A.tl_nblk), dim3(256), 0, st, nrows, A.tl_nblk, A.tl_gptr.as<int32_t>(),
                            A.tl_ucol.as<int32_t>(), A.tl_coef.as<double>(), (const double *)x, bin, ldb, nrhs, L.p.as<int32_t>(),
@@ -2064,8 +2083,7 @@ class Engine : public EngineBase {
       }
       if (A.tl_nblk > 0 && logR == 6) {
         const unsigned grid = (unsigned)std::min<int64_t>((A.tl_nblk + 3) / 4, 256 * 16);
-        auto k1 = A.tl_rb == 2 ? (nct == 1 ? k_spmm_tile<2, 1> : nct == 2 ? k_spmm_tile<2, 2> : nct == 3 ? k_spmm_tile<2, 3> : k_spmm_tile<2, 4>)
-                               : (nct == 1 ? k_spmm_tile<1, 1> : nct == 2 ? k_spmm_tile<1, 2> : nct == 3 ? k_spmm_tile<1, 3> : k_spmm_tile<1, 4>);
+        auto k1 = spmm_tile_kernel(A.tl_rb, nct, ahead);
         tally(A.tl_rb == 2 ? KF_SPMM_TILE_RB2 : KF_SPMM_TILE_RB1);
         hipLaunchKernelGGL(k1, dim3(grid), dim3(256), 0, st, nrows, A.tl_nblk, A.tl_gptr.as<int32_t>(),
                            A.tl_ucol.as<int32_t>(), A.tl_coef.as<double>(), (const double *)x, bin, ldb, nrhs, L.p.as<int32_t>(),

@@ -1174,8 +1174,76 @@ __global__ void __launch_bounds__(256) k_spmm_epi_narrow(int64_t nrows, const in
 // 16-column tiles (lane l fetches x[ucol[4g + (l >> 4)]][16 ct + (l & 15)]), four MFMAs.  Two groups in flight.
 // Every distinct source row of a block is fetched once, not once per nonzero.  R = 64, real data, fast mode.
 // ---------------------------------------------------------------------------------------------
-template <int RB, int NCT>
-__global__ void __launch_bounds__(256) k_spmm_tile(int64_t nrows, int64_t nblk, const int32_t *__restrict__ blk_gptr,
+//
+// The group loop of k_spmm_tile / k_spmm_tile4 with its requests running ahead (AHEAD; the former loop and epilogue are the
+// second instance, bit 4096 of the development switch, engine.hip kDbgSpmmPlain -- the same products in the same order).
+// A wave's groups k = 0 .. ng - 1 (HIFAMD_TL_GID(k): the group's number, clamped to the wave's last group; ng is
+// wave-uniform) are multiplied in batches of BU, the sequence form of k_band_ct's phase 1: at the top of the step that
+// multiplies batch b the ids of batch b + 1 and the gathers and coefficient tiles of batch b are in flight, in that order;
+// the step requests the ids of batch b + 2, then -- the wait for the ids of b + 1 leaves batch b's operands in flight --
+// the operands of batch b + 1, and only then multiplies batch b: that wait leaves everything the step requested in flight.
+// Every load is unconditional; a group past the wave's last reads that group again and its coefficient is replaced by
+// zero where it is multiplied (a batch wholly past the end is never multiplied).  Two register sets of each kind rotate by
+// name over a loop of two steps with one exit, at its top; the remainder is multiplied behind the loop, with no requests.
+// BU groups per batch: 4 for the per-wave kernel on 16-row blocks (168 registers, three waves per SIMD as before), 2 on
+// 32-row blocks and for k_spmm_tile4 (116 registers, four waves per SIMD as before; 3 and 4 measured slower).
+// The second bound of __launch_bounds__ (two workgroups per compute unit) keeps the accumulators in vector registers: with
+// 512 registers allowed the matrix instructions take theirs in AGPRs and the loop copies every one in and out per trip.
+template <int RB>
+struct SpmmAhead {
+  static constexpr int BU = RB == 1 ? 4 : 2;  // k_spmm_tile
+  static constexpr int BU4 = 2;               // k_spmm_tile4
+  static constexpr int WGS = 2;               // workgroups per compute unit the register allocation leaves room for
+};
+typedef __attribute__((address_space(1))) double tl_gdouble;
+typedef __attribute__((address_space(1))) int32_t tl_gint32;
+#define HIFAMD_TLA_IDS(ii, kb_) \
+  _Pragma("unroll") for (int u = 0; u < BU; ++u) ii[u] = (uint32_t)ucol_g[4 * (int64_t)HIFAMD_TL_GID((kb_) + u) + kq];
+#define HIFAMD_TLA_OPS(gg, cf, ii, kb_)                                                            \
+  {                                                                                                \
+    _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                               \
+      _Pragma("unroll") for (int rb = 0; rb < RB; ++rb)                                            \
+        cf[u][rb] = coef_g[64 * (RB * (int64_t)HIFAMD_TL_GID((kb_) + u) + rb) + lane];             \
+    }                                                                                              \
+    __builtin_amdgcn_sched_barrier(0); /* (the tiles need no ids: they go out in front of the wait for them) */ \
+    _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                               \
+      _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) gg[u][ct] = x_g[((uint64_t)ii[u] << 6) + (uint32_t)(16 * ct + jc)]; \
+    }                                                                                              \
+  }
+#define HIFAMD_TLA_MUL(gg, cf, kb_)                                                                \
+  _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                                 \
+    _Pragma("unroll") for (int rb = 0; rb < RB; ++rb) {                                            \
+      const double c_ = ((kb_) + u < ng) ? cf[u][rb] : 0.0;                                        \
+      _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct)                                           \
+        acc[rb][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(c_, gg[u][ct], acc[rb][ct], 0, 0, 0);   \
+    }                                                                                              \
+  }
+// ifree: the id set whose gathers are out; inext: the ids of the batch behind the one being multiplied
+#define HIFAMD_TLA_STEP(ifree, inext, gcur, ccur, gnew, cnew, kb_)                                 \
+  {                                                                                                \
+    HIFAMD_TLA_IDS(ifree, (kb_) + 2 * BU)                                                          \
+    __builtin_amdgcn_sched_barrier(0); /* (the ids lead: the next step's wait for them is counted) */ \
+    HIFAMD_TLA_OPS(gnew, cnew, inext, (kb_) + BU)                                                  \
+    __builtin_amdgcn_sched_barrier(0); /* (the requests stay in front of the products) */          \
+    HIFAMD_TLA_MUL(gcur, ccur, kb_)                                                                \
+    HIFAMD_TLA_PIN_ACC                                                                             \
+  }
+// (the accumulators are touched behind each step's products, as in k_band_ct: without it the next step's id requests land
+// behind products of this one, and the instances take four registers more -- k_spmm_tile<1,4> 172, one wave per SIMD less)
+#define HIFAMD_TLA_PIN_ACC                                                                         \
+  _Pragma("unroll") for (int rb = 0; rb < RB; ++rb) {                                              \
+    _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) asm volatile("" : "+v"(acc[rb][ct]));       \
+  }
+// the epilogue's operands of row tile rb_: scales and right-hand sides of its four rows (rows and columns clamped)
+#define HIFAMD_TLA_RHS(rb_)                                                                        \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                  \
+    sc[rb_][r] = s_g[prow[rb_][r]];                                                                \
+    _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct)                                             \
+      bv_[rb_][r][ct] = bin_g[(int64_t)prow[rb_][r] * ldb + min(16 * ct + jc, nrhs - 1)];          \
+  }
+
+template <int RB, int NCT, bool AHEAD>
+__global__ void __launch_bounds__(256, AHEAD ? SpmmAhead<RB>::WGS : 1) k_spmm_tile(int64_t nrows, int64_t nblk, const int32_t *__restrict__ blk_gptr,
                                                    const int32_t *__restrict__ ucol, const double *__restrict__ coef,
                                                    const double *__restrict__ x, IoPtr<const double> bin_, int64_t ldb,
                                                    int nrhs, const int32_t *__restrict__ p, const double *__restrict__ s,
@@ -1196,9 +1264,69 @@ __global__ void __launch_bounds__(256) k_spmm_tile(int64_t nrows, int64_t nblk, 
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) acc[rb][ct] = v4f64{0.0, 0.0, 0.0, 0.0};
-    // Software pipeline over the groups, all loads unconditional (indices clamped to the block's last group, whose
-    // coefficient is then zeroed): source-row indices run 7 groups ahead, coefficient + B fragments 3 groups ahead of the
-    // MFMAs -- the compiler counts its waits exactly, nothing but the oldest group is ever waited for.
+    if constexpr (AHEAD) {
+      constexpr int BU = SpmmAhead<RB>::BU;
+      const tl_gdouble *x_g = (const tl_gdouble *)x, *coef_g = (const tl_gdouble *)coef, *bin_g = (const tl_gdouble *)bin;
+      const tl_gdouble *s_g = (const tl_gdouble *)s;
+      const tl_gint32 *ucol_g = (const tl_gint32 *)ucol, *p_g = (const tl_gint32 *)p;
+      // The epilogue's operands do not depend on the product: the rows' places in the level's input are requested when the
+      // block opens, their scales and right-hand sides behind the loop, in front of the last batch's products (rows and
+      // columns clamped, zero selected at the use) -- not 4 RB (1 + NCT) serial round trips behind the last product.
+      uint32_t prow[RB][4];
+      double sc[RB][4], bv_[RB][4][NCT];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t i = 16 * (RB * b + rb) + kq + 4 * r;
+          prow[rb][r] = (uint32_t)p_g[roff + (i < nrows ? i : nrows - 1)];
+        }
+      const int32_t ng = g1 - g0;
+      if (ng > 0) {
+#define HIFAMD_TL_GID(k) (g0 + min((k), ng - 1))
+        uint32_t ia[BU], ib[BU];  // (row ids are not negative: widened by zero, nothing waits for the load that early)
+        double ca[BU][RB], cb[BU][RB], ga[BU][NCT], gb[BU][NCT];
+        HIFAMD_TLA_IDS(ia, 0)
+        HIFAMD_TLA_IDS(ib, BU)
+        // (the second id set is touched here, or its request sinks into the loop's entry, behind batch 0's operands)
+#pragma unroll
+        for (int u = 0; u < BU; ++u) pin_here(ib[u]);
+        HIFAMD_TLA_OPS(ga, ca, ia, 0)
+        int32_t k = 0;
+        for (; k + BU < ng; k += 2 * BU) {  // (one exit, at the top; two batches per trip)
+          HIFAMD_TLA_STEP(ia, ib, ga, ca, gb, cb, k)
+          HIFAMD_TLA_STEP(ib, ia, gb, cb, ga, ca, k + BU)
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) { HIFAMD_TLA_RHS(rb) }
+        __builtin_amdgcn_sched_barrier(0);  // (these requests stand in front of the last batch's products)
+        if (k < ng) {  // the block's last batch: in registers or on its way
+          HIFAMD_TLA_MUL(ga, ca, k)
+        }
+#undef HIFAMD_TL_GID
+      } else {
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) { HIFAMD_TLA_RHS(rb) }
+      }
+      // epilogue: C layout col = l & 15, row = (l >> 4) + 4 * reg; only the stores depend on the row
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t i = 16 * (RB * b + rb) + kq + 4 * r;
+#pragma unroll
+          for (int ct = 0; ct < NCT; ++ct) {
+            const int c = 16 * ct + jc;
+            const double rhs = c < nrhs ? sc[rb][r] * bv_[rb][r][ct] : 0.0;
+            if (i < nrows) out[(i << 6) + c] = rhs - acc[rb][ct][r];
+          }
+        }
+      continue;
+    }
+    // The former software pipeline over the groups, all loads unconditional (indices clamped to the block's last group,
+    // whose coefficient is then zeroed): source-row indices 7 groups ahead, coefficient + B fragments 3 groups ahead of the
+    // MFMAs in the source; the compiler clusters them per trip of eight groups.
     if (g0 < g1) {
       const int32_t gl = g1 - 1;
       int32_t src[8];
@@ -1254,8 +1382,8 @@ __global__ void __launch_bounds__(256) k_spmm_tile(int64_t nrows, int64_t nblk, 
 // on average, 188 at most, 1,987 blocks of 16 rows -- fewer waves than the chip holds, and the launch lasts as long as
 // the longest chain): four waves per block cut every chain to a quarter and quadruple the gathers in flight.  Partial
 // tiles meet in LDS; wave w finishes column tile w of the block (fixed order: deterministic).
-template <int RB, int NCT>
-__global__ void __launch_bounds__(256) k_spmm_tile4(int64_t nrows, int64_t nblk, const int32_t *__restrict__ blk_gptr,
+template <int RB, int NCT, bool AHEAD>
+__global__ void __launch_bounds__(256, AHEAD ? SpmmAhead<RB>::WGS : 1) k_spmm_tile4(int64_t nrows, int64_t nblk, const int32_t *__restrict__ blk_gptr,
                                                     const int32_t *__restrict__ ucol, const double *__restrict__ coef,
                                                     const double *__restrict__ x, IoPtr<const double> bin_, int64_t ldb,
                                                     int nrhs, const int32_t *__restrict__ p, const double *__restrict__ s,
@@ -1276,7 +1404,58 @@ __global__ void __launch_bounds__(256) k_spmm_tile4(int64_t nrows, int64_t nblk,
   // this wave's groups: g0 + wave + 4 k, k = 0 .. ng - 1; same software pipeline as k_spmm_tile (loads unconditional,
   // indices clamped to the wave's last group, whose coefficient is then zeroed)
   const int32_t ng = (g1 - g0 > wave) ? (g1 - g0 - wave + 3) / 4 : 0;
-  if (ng > 0) {
+  const int c = 16 * wave + jc;
+  // AHEAD: the epilogue of column tile `wave` needs its rows' places in the level's input, their scales and right-hand sides,
+  // none of which depends on the product -- requested up front, rows and the column clamped, zero selected at the use
+  // -- the request order is places, the first two id sets, then (the wait for the places leaves the ids in flight) scales
+  // and right-hand sides, then batch 0's operands: the loop's first wait for operands covers them all
+  double sc[RB][4], bw[RB][4];
+  if constexpr (AHEAD) {
+    constexpr int BU = SpmmAhead<RB>::BU4;
+    const tl_gdouble *bin_g = (const tl_gdouble *)bin, *s_g = (const tl_gdouble *)s;
+    const tl_gdouble *x_g = (const tl_gdouble *)x, *coef_g = (const tl_gdouble *)coef;
+    const tl_gint32 *p_g = (const tl_gint32 *)p, *ucol_g = (const tl_gint32 *)ucol;
+#define HIFAMD_TL_GID(k) (g0 + wave + 4 * min((k), ng - 1))
+    uint32_t prow[RB][4];
+    uint32_t ia[BU], ib[BU];
+    double ca[BU][RB], cb[BU][RB], ga[BU][NCT], gb[BU][NCT];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t i = 16 * (RB * b + rb) + kq + 4 * r;
+        prow[rb][r] = (uint32_t)p_g[roff + (i < nrows ? i : nrows - 1)];
+      }
+    if (ng > 0) {
+      HIFAMD_TLA_IDS(ia, 0)
+      HIFAMD_TLA_IDS(ib, BU)
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sc[rb][r] = s_g[prow[rb][r]];
+        bw[rb][r] = bin_g[(int64_t)prow[rb][r] * ldb + min(c, nrhs - 1)];
+      }
+    __builtin_amdgcn_sched_barrier(0);
+    if (ng > 0) {
+      // (the second id set is touched here, or its request sinks into the loop's entry, behind batch 0's operands)
+#pragma unroll
+      for (int u = 0; u < BU; ++u) pin_here(ib[u]);
+      HIFAMD_TLA_OPS(ga, ca, ia, 0)
+      int32_t k = 0;
+      for (; k + BU < ng; k += 2 * BU) {  // (one exit, at the top; two batches per trip)
+        HIFAMD_TLA_STEP(ia, ib, ga, ca, gb, cb, k)
+        HIFAMD_TLA_STEP(ib, ia, gb, cb, ga, ca, k + BU)
+      }
+      if (k < ng) {  // the wave's last batch: in registers or on its way
+        HIFAMD_TLA_MUL(ga, ca, k)
+      }
+    }
+#undef HIFAMD_TL_GID
+  }
+  if (!AHEAD && ng > 0) {
     const int32_t kl = ng - 1;
     int32_t src[8];
     double av[4][RB], bv[4][NCT];
@@ -1307,7 +1486,6 @@ __global__ void __launch_bounds__(256) k_spmm_tile4(int64_t nrows, int64_t nblk,
 #undef HIFAMD_TL_SRC
 #undef HIFAMD_TL_LOAD
   }
-  const int c = 16 * wave + jc;
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
     if (rb) __syncthreads();  // (the previous row tile's partials have been read)
@@ -1321,7 +1499,11 @@ __global__ void __launch_bounds__(256) k_spmm_tile4(int64_t nrows, int64_t nblk,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t i = 16 * (RB * b + rb) + kq + 4 * r;
-      if (i < nrows) {
+      if constexpr (AHEAD) {  // (only the store depends on the row)
+        const double tot = ((red[0][wave][r][lane] + red[1][wave][r][lane]) + red[2][wave][r][lane]) + red[3][wave][r][lane];
+        const double rhs = c < nrhs ? sc[rb][r] * bw[rb][r] : 0.0;
+        if (i < nrows) out[(i << 6) + c] = rhs - tot;
+      } else if (i < nrows) {
         const double tot = ((red[0][wave][r][lane] + red[1][wave][r][lane]) + red[2][wave][r][lane]) + red[3][wave][r][lane];
         const int32_t srow = p[roff + i];
         const double rhs = c < nrhs ? s[srow] * bin[(int64_t)srow * ldb + c] : 0.0;
@@ -1330,6 +1512,13 @@ __global__ void __launch_bounds__(256) k_spmm_tile4(int64_t nrows, int64_t nblk,
     }
   }
 }
+
+#undef HIFAMD_TLA_IDS
+#undef HIFAMD_TLA_OPS
+#undef HIFAMD_TLA_MUL
+#undef HIFAMD_TLA_STEP
+#undef HIFAMD_TLA_RHS
+#undef HIFAMD_TLA_PIN_ACC
 
 // The tiled product for COMPLEX coupling blocks (round 4; host.hpp build_spmm_tiles(Csr<zdouble>)): one wave per 16-row
 // block and 16-column slice of the (complex) batch -- blockIdx.y = slice --; a group's coefficients are two real tiles

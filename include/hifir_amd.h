@@ -193,8 +193,9 @@ int hifamd_launch_map(HifAmdHdl h, int32_t *out, int cap);
  * out[f] = launches of family f on every level, out[N + f] = those of them on a level >= 1 (the tail operator counts for
  * the first level it replaces), f < N; hifamd_kernel_family_name(f) names the families in order ("band_ct1", "band_ct2",
  * ..., NULL from f = N on).  A family is what the dispatch distinguishes: a kernel, and where the planner or a
- * HIFIR_AMD_* switch chooses between instantiations, the instantiation (one exception: bit 2048 of HIFIR_AMD_CD_DBG picks the
- * other form of k_band_ct's tile loop, which makes the same sums in the same order -- both count as band_ct1 / 2 / 4).
+ * HIFIR_AMD_* switch chooses between instantiations, the instantiation (two exceptions: bit 2048 of HIFIR_AMD_CD_DBG picks the
+ * other form of k_band_ct's tile loop, which makes the same sums in the same order -- both count as band_ct1 / 2 / 4; bit
+ * 4096 picks the former group loop and epilogue of k_spmm_tile / k_spmm_tile4 -- both count as spmm_tile[4]_rb1 / 2).
  * Returns 2 N (writes min(cap, that)); 0 before
  * hifamd_finalize, -1 for a NULL handle. */
 int hifamd_kernel_census(HifAmdHdl h, int32_t *out, int cap);
