@@ -3506,6 +3506,145 @@ class Engine : public EngineBase {
            [&](const D *b, D *x) { bcg_dev(b, nrhs, x, nrhs, nrhs, block, rtol, deftol, maxit, rank, flags, iters, ranks); });
   }
 
+  // ---- LOBPCG: the nev smallest eigenpairs of a Hermitian pair (A, M), a block of k <= 16 candidates --------------
+  // Knyazev's locally optimal block PCG with a Rayleigh-Ritz step on the orthonormalized basis [X W P]:
+  //   start: X = X0 (or generated from seed), filtered under a basis filter; G = X^H X = S^H S (pivoted Cholesky, rank < k or
+  //          not finite: refused), X <- X E; AX = A X; X^H AX = V Theta V^H, X <- X V, AX <- AX V, lambda = Theta, P = AP = 0;
+  //   loop:  R = AX - X diag(lambda), res_j = ||r_j|| / ||A||_inf, conv_j = res_j <= tol; all j < nev converged or
+  //          steps == maxit: end.  W = M^{-1} R (converged columns exact zeros), AW = A W; GB = S^H S, GA = S^H AS on
+  //          S = [X W P]; D = diag(GB)^(-1/2), D GB D = T^H T (pivoted, stopped at deftol, rank r; r < k: breakdown),
+  //          E = D I[:, piv] inv(T[:, piv]); E^H GA E = V Theta V^H ascending; C = E V[:, :k], lambda = Theta[:k], Cp = C with its
+  //          first k rows zero; X, P <- S [C Cp], AX, AP <- AS [C Cp].
+  // Per step one batched apply, one SpMM, one Gram pass (k_lob_gram2), one row-local pass (k_lob_update), the residual pass
+  // (k_lob_resid, k_lob_lock), two one-workgroup kernels (k_lob_small) and ONE read-back, after the test.  The vectors are
+  // kr_vec[0..2] = S [n][3 k], AS [n][3 k], R [n][k]; the small matrices live beside the KrylovState (LobState).  flags
+  // 0 converged / 1 breakdown / 2 not converged at maxit, per column by its own last res_j.  info3: steps, rank of the basis
+  // in the last step, largest Jacobi sweep count.
+  void lobpcg_tile(const D *dX0, int64_t ldx0, uint64_t seed, int k, int nev, double tol, double deftol, int maxit, int64_t rank,
+                   D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3) {
+    const int64_t n = lv[0]->n;
+    const int s = 3 * k;
+    const size_t blk = (size_t)n * s * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
+    const size_t part = std::max(2 * (size_t)kBcgBlocks * mat, (size_t)kLobResBlocks * 16 * sizeof(double));
+    krylov_vectors(2, blk);
+    if (kr_vec[2].bytes < blk / 3) kr_vec[2].alloc(blk / 3);  // R is [n][k]
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    D *Sb = kr_vec[0].as<D>(), *ASb = kr_vec[1].as<D>(), *R = kr_vec[2].as<D>(), *pt = ir_part.as<D>();
+    const size_t lds_small = 2 * mat + 64 * sizeof(D) + 3 * 64 * sizeof(double) + (4 * 64 + 4) * sizeof(int);
+    if (!lob_lds_raised) {  // (68 KB; a complex handle's 133 KB)
+      HIP_OK(hipFuncSetAttribute((const void *)k_lob_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
+      lob_lds_raised = true;
+    }
+    StreamWait wait{stream};
+    LobState<D> S;
+    krylov_state(S, {{&S.GB, 64}, {&S.GA, 64}, {&S.CC, 64}, {&S.X1, 64}, {&S.X2, 64}, {&S.X3, 64}}, {&S.bnorm, &S.lam, &S.res}, tol,
+                 maxit);
+    S.deftol = deftol, S.anorm = A_norm_inf, S.k = k, S.nev = nev;
+    auto gram = [&] {  // S.GB = S^H S, S.GA = S^H AS
+      hipLaunchKernelGGL((k_lob_gram2<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, (const D *)Sb, (const D *)ASb, pt);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, s, S.GB);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)(pt + (size_t)kBcgBlocks * 64 * 64), kBcgBlocks,
+                         s, S.GA);
+    };
+    auto small = [&](int mode, int step) {
+      hipLaunchKernelGGL((k_lob_small<D>), dim3(1), dim3(256), lds_small, stream, mode, step, (const double *)pt, S);
+    };
+    auto update = [&] {
+      hipLaunchKernelGGL((k_lob_update<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, k, Sb, ASb, (const D *)S.CC);
+    };
+    auto refused = [&] {  // the start's verdict
+      HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+      check_device_error();
+      if (kr_pin[3] == 1) throw Error(HIFAMD_BAD_PREC, "LOBPCG: the start block is rank deficient");
+      if (kr_pin[3] == 2) throw Error(HIFAMD_BAD_PREC, "LOBPCG: the start block is not finite");
+      if (kr_pin[3] == 3)
+        throw Error(HIFAMD_BAD_PREC, "LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end");
+    };
+    HIP_OK(hipMemsetAsync(Sb, 0, blk, stream));
+    HIP_OK(hipMemsetAsync(ASb, 0, blk, stream));
+    if (dX0) {
+      vec_op(1, n, k, Sb, s, dX0, ldx0, nullptr, 0);
+    } else {
+      hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, k, seed, R);
+      vec_op(1, n, k, Sb, s, (const D *)R, k, nullptr, 0);
+    }
+    if (nsp_k > 0) apply_nsp(Sb, s, k, stream);  // on the complement of span(Q)
+    gram();
+    small(0, 0);
+    refused();
+    update();  // X <- X E
+    spmv_dev((const D *)Sb, s, ASb, s, k, nullptr);  // AX = A X
+    gram();
+    small(1, 0);
+    refused();
+    update();  // X <- X V, AX <- AX V, P = AP = 0
+    HIP_OK(hipGetLastError());
+    for (int step = 0;; ++step) {
+      hipLaunchKernelGGL((k_lob_resid<D>), dim3(kLobResBlocks), dim3(256), 0, stream, n, s, k, (const D *)Sb, (const D *)ASb,
+                         (const double *)S.lam, R, (double *)pt);
+      small(2, step);
+      if (krylov_active(S) == 0) break;
+      hipLaunchKernelGGL((k_lob_lock<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, R, (const int *)S.active);
+      solve_dev((const D *)R, k, Sb + k, s, k, rank, nullptr);  // W = M^{-1} R
+      spmv_dev((const D *)(Sb + k), s, ASb + k, s, k, nullptr);  // AW = A W
+      gram();
+      small(3, step);
+      update();
+      HIP_OK(hipGetLastError());
+    }
+    vec_op(1, n, k, dX, ldx, (const D *)Sb, s, nullptr, 0);
+    int its[64];
+    krylov_result(S, k, flags, its);
+    std::vector<double> out(128);
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(out.data(), S.lam, 128 * sizeof(double), hipMemcpyDeviceToHost, stream));  // lam | res
+    HIP_OK(hipStreamSynchronize(stream));
+    for (int c = 0; c < k; ++c) {
+      if (lambda) lambda[c] = out[(size_t)c];
+      if (res) res[c] = out[64 + (size_t)c];
+    }
+    if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
+  }
+  bool lob_lds_raised = false;
+
+  void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx) {
+    if (k < 1 || k > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= k <= 16");
+    if (nev < 1 || nev > k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= nev <= k");
+    if (!(tol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need tol > 0");
+    if (maxit < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need maxit >= 1");
+    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 0 < deftol < 1");
+    if ((has_x0 && ldx0 < k) || ldx < k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: row stride smaller than k");
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (k > std::max<int64_t>(Rmax, max_nrhs))
+      throw Error(HIFAMD_MISMATCHED_SIZES, "block wider than the max_nrhs given to hifamd_finalize");
+    if (!has_A) throw Error(HIFAMD_BAD_PREC, "LOBPCG needs the matrix (hifamd_set_matrix)");
+    hermitian_check("LOBPCG", "hifamd_nsp_find for null vectors", "a constant-mode null-space filter");
+  }
+  void lobpcg_dev(int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+                  int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info3) {
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, dX0 != nullptr, ldx);
+    if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    lobpcg_tile(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
+  }
+  void lobpcg_host(int64_t k, int64_t nev, const T *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+                   int64_t rank, double *lambda, T *X, int64_t ldx, double *res, int *flags, int *info3) {
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, X0 != nullptr, ldx);
+    if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * k * sizeof(T);
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
+    if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    lobpcg_tile(X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, (int)k, (int)nev, tol, deftol, maxit, rank, stage_x.as<D>(), k,
+                lambda, res, flags, info3);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
   // ---- restarted block GCR for a general pair (A, M): block CG's shared space without its conditions ------------
   // Block GMRES(m) with right preconditioning in exact arithmetic, flexible by construction.  Per cycle the true residual
   // R = B - A X (resid_dev, the handle's residual precision) is tested, normalized and factored, relative residual = Rh C
@@ -4747,6 +4886,26 @@ HifAmdStatus hifamd_bgcr_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, voi
   API_BEGIN
   visit(h, [&](auto &E) {
     E.bgcr_dev(E.dev(dB), ldb, E.dev(dX), ldx, nrhs, block, restart, rtol, deftol, maxit, rank, flags, iters, ranks);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_lobpcg(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, int64_t ldx0, uint64_t seed, double tol,
+                           double deftol, int maxit, int64_t rank, double *lambda, void *X, int64_t ldx, double *res, int *flags,
+                           int *info3) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.lobpcg_host(k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
+                               double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
+                               int *flags, int *info3) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.lobpcg_dev(k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
   });
   API_END
 }

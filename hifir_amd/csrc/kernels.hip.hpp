@@ -37,6 +37,8 @@
 //                    row-local products on the f64 matrix cores, the small matrices in one workgroup (blockcg_small.hpp)
 //   k_bgcr_gram / k_bgcr_sum / k_bgcr_proj / k_bgcr_rmul / k_bgcr_rho / k_bgcr_small   device-resident restarted block GCR: the
 //                    stacked Gram, the fused block Gram-Schmidt pass, in-place right-multiplication, decisions (blockgcr_small.hpp)
+//   k_lob_gram2 / k_lob_update / k_lob_resid / k_lob_lock / k_lob_small   device-resident LOBPCG: both Grams of the basis
+//                    [X W P] in one pass, the row-local update, the Rayleigh-Ritz step in one workgroup (lobpcg_small.hpp)
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -48,6 +50,7 @@
 #include "band_lds.hpp"
 #include "blockcg_small.hpp"
 #include "blockgcr_small.hpp"
+#include "lobpcg_small.hpp"
 
 namespace hifamd {
 
@@ -6488,6 +6491,222 @@ __global__ void __launch_bounds__(256) k_bgcr_small(int mode, int steps, int fla
   if (mode == 2) bgcr::step_basis(Sm, W, s, steps, tm);
   if (mode == 3) bgcr::step_coeff(Sm, W, s, tm);
   if (mode == 4) bgcr::step_test(Sm, W, s, steps, flag != 0, tm);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident LOBPCG for the smallest eigenpairs of a Hermitian pair (A, M) (Engine::lobpcg_tile): k <= 16 candidates,
+// the basis S = [X W P] and its image AS = [AX AW AP] as two [n][ld] blocks (ld = s = 3 k <= 48 columns, X at column 0, W at
+// k, P at 2 k), the residual R as [n][k].  Per step:
+//   k_lob_resid    R = AX - X diag(lambda) and the partials of |r_j|^2
+//   k_lob_lock     exact zeros in the columns of R that the test found converged (so that W = M^{-1} R is zero there)
+//   k_lob_gram2    partials of GB = S^H S and GA = S^H AS in one pass, upper block triangle, v_mfma_f64_16x16x4_f64
+//   k_lob_update   X, P <- S [C Cp] and AX, AP <- AS [C Cp] on the matrix cores, [C Cp] staged in LDS
+//   k_lob_small    one workgroup: the residual test, the Rayleigh-Ritz step (lobpcg_small.hpp, shared with the host), every
+//                  decision and flag
+// Lane maps, complex handles on real planes, fixed-order partials (k_bcg_sum adds the blocks): as block CG above.
+// ---------------------------------------------------------------------------------------------
+constexpr int kLobResBlocks = 1024;  // workgroups (and partials per column) of k_lob_resid
+
+template <class T>
+struct LobState : KrylovState {
+  // rtol holds tol; active: 1 for a column that the last test did not find converged; iter: the completed steps
+  // ctl: [0] 1 while the tile runs, [1] rank of the basis in the last step, [2] largest Jacobi sweep count,
+  //      [3] the start's verdict (lob::kStart*)
+  T *GB, *GA, *CC, *X1, *X2, *X3;  // [64][64] each: the summed Grams, [C Cp] of the next row pass, scratch of the small kernel
+  double *lam, *res;               // [64]  Ritz values; ||r_j|| / ||A||_inf of the last test
+  double deftol, anorm;
+  int k, nev;
+};
+
+// element (row, col) of an [n][ld] block whose first s columns are in use, an exact zero outside; the load is unconditional
+template <class T>
+__device__ __forceinline__ T lob_load(const T *__restrict__ x, int64_t n, int ld, int s, int64_t row, int col) {
+  const bool ok = row < n && col < s;
+  const T v = x[ok ? row * ld + col : 0];
+  return ok ? v : vzero(T());
+}
+
+// partial[0][blockIdx.x] and partial[1][blockIdx.x] ([64][64] each) = the block's share of S^H S and S^H AS, tiles (ti <= tj)
+// only.  Wave w of block b owns the row groups g = 4 b + w + k * 4 gridDim.x (rows 4 g .. 4 g + 3, one K step each); the
+// conjugated strip of S is loaded once and is the left operand of both products.
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_gram2(int64_t n, int ld, int s, const T *__restrict__ S, const T *__restrict__ AS,
+                                                   T *__restrict__ partial /* [2][gridDim.x][64][64] */) {
+  __shared__ T lds[12 * 4 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (s + 15) >> 4;
+  BcgAcc<T> acc[2][6];  // tile (ti, tj), ti <= tj < 3, at index 3 ti + tj - ti (ti + 1) / 2
+#pragma unroll
+  for (int w = 0; w < 2; ++w)
+#pragma unroll
+    for (int t = 0; t < 6; ++t) bcg_clear(acc[w][t]);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t g = (int64_t)blockIdx.x * 4 + wave; 4 * g < n; g += 2 * stride) {
+    T a[2][3], b[2][3], c[2][3];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        b[u][t] = lob_load(S, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+        c[u][t] = lob_load(AS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+        a[u][t] = vconj(b[u][t]);
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+        for (int tj = ti; tj < 3; ++tj)
+          if (tj < nt) {
+            bcg_mma(acc[0][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], b[u][tj]);
+            bcg_mma(acc[1][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], c[u][tj]);
+          }
+  }
+  // the four waves of the block in wave order
+  for (int w = 1; w < 4; ++w) {
+    __syncthreads();
+    if (wave == w) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) lds[((m * 6 + t) * 4 + reg) * 64 + lane] = bcg_get(acc[m][t], reg);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const T v = lds[((m * 6 + t) * 4 + reg) * 64 + lane];
+            if constexpr (std::is_same<T, cplx>::value)
+              acc[m][t].re[reg] += v.x, acc[m][t].im[reg] += v.y;
+            else
+              acc[m][t].re[reg] += v;
+          }
+    }
+  }
+  if (wave != 0) return;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    T *__restrict__ out = partial + ((int64_t)m * gridDim.x + blockIdx.x) * 64 * 64;
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+      for (int tj = ti; tj < 3; ++tj)
+        if (tj < nt) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+            out[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[m][3 * ti + tj - ti * (ti + 1) / 2], reg);
+        }
+  }
+}
+
+// X <- S C, P <- S Cp, AX <- AS C, AP <- AS Cp in place: CC [64][64] holds C in its columns 0 .. 15 and Cp in 16 .. 31 (rows
+// >= s and columns >= k of either are zero), staged in LDS once per workgroup.  A wave owns the 16-row strips
+// 4 b + w + j * 4 gridDim.x and reads its strip of S and of AS completely, as operands, before it writes any of it.
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_update(int64_t n, int ld, int s, int k, T *__restrict__ S, T *__restrict__ AS,
+                                                    const T *__restrict__ CC) {
+  __shared__ T cc[48 * 32];
+  for (int e = threadIdx.x; e < 48 * 32; e += blockDim.x) cc[e] = CC[(e >> 5) * 64 + (e & 31)];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (s + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    T x[12], ax[12];
+#pragma unroll
+    for (int kk = 0; kk < 12; ++kk) {
+      x[kk] = ax[kk] = vzero(T());
+      if (kk < 4 * nt) {
+        x[kk] = lob_load((const T *)S, n, ld, s, r0 + ci, 4 * kk + kq);
+        ax[kk] = lob_load((const T *)AS, n, ld, s, r0 + ci, 4 * kk + kq);
+      }
+    }
+    BcgAcc<T> as[2], aa[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) bcg_clear(as[t]), bcg_clear(aa[t]);
+#pragma unroll
+    for (int kk = 0; kk < 12; ++kk)
+      if (kk < 4 * nt) {
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) {
+          const T b = cc[(4 * kk + kq) * 32 + 16 * tj + ci];
+          bcg_mma(as[tj], x[kk], b);
+          bcg_mma(aa[tj], ax[kk], b);
+        }
+      }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t row = r0 + kq + 4 * reg;
+        if (row < n && ci < k) {
+          S[row * ld + 2 * k * tj + ci] = bcg_get(as[tj], reg);
+          AS[row * ld + 2 * k * tj + ci] = bcg_get(aa[tj], reg);
+        }
+      }
+  }
+}
+
+// R = AX - X diag(lambda) ([n][k]; X and AX are the first k columns of their [n][ld] blocks) and the block's share of
+// |r_j|^2: thread t owns column t & 15 of the rows 16 b + (t >> 4) + j * 16 gridDim.x in that order, the sixteen row
+// classes of a block are added in order: partial[blockIdx.x][16]
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_resid(int64_t n, int ld, int k, const T *__restrict__ S, const T *__restrict__ AS,
+                                                   const double *__restrict__ lam, T *__restrict__ R,
+                                                   double *__restrict__ partial /* [gridDim.x][16] */) {
+  __shared__ double sm[256];
+  const int c = threadIdx.x & 15, sub = threadIdx.x >> 4;
+  double acc = 0.0;
+  if (c < k) {
+    const double l = lam[c];
+    for (int64_t i = (int64_t)blockIdx.x * 16 + sub; i < n; i += (int64_t)gridDim.x * 16) {
+      const T r = vsub(AS[i * ld + c], vscale(l, S[i * ld + c]));
+      R[i * k + c] = r;
+      acc += vabs2(r);
+    }
+  }
+  sm[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    double tot = sm[threadIdx.x];
+    for (int u = 1; u < 16; ++u) tot += sm[16 * u + threadIdx.x];
+    partial[blockIdx.x * 16 + threadIdx.x] = tot;
+  }
+}
+
+// exact zeros in the columns of R ([n][k]) that the last test found converged (active[c] == 0); nothing else is written
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_lock(int64_t n, int k, T *__restrict__ R, const int *__restrict__ active) {
+  const int64_t total = n * k;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+    if (!active[e % k]) R[e] = vzero(T());
+}
+
+// One workgroup of 256 threads, with lobpcg_small.hpp's arithmetic and decisions on two 64 x 64 working matrices in LDS (three
+// more, of the state, in HBM).  step: the completed steps.
+//   mode 0: lob::start_factor  (X0^H X0 -> CC = [E 0], or the start's refusal)
+//   mode 1: lob::ritz_step at the start  (X^H A X = V Theta V^H -> CC = [V 0], lambda)
+//   mode 2: lob::residual_test on the kLobResBlocks partials of |r_j|^2
+//   mode 3: lob::ritz_step  (GB, GA -> CC = [C Cp], lambda, rank; or the breakdown)
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_small(int mode, int step, const double *__restrict__ partial, LobState<T> S) {
+  extern __shared__ double bcg_lds_raw[];
+  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64, *js = W2 + 64 * 64;
+  double *d = (double *)(js + 64), *dsc = d + 64, *jc = dsc + 64;
+  int *piv = (int *)(jc + 64), *taken = piv + 64, *perm = taken + 64, *mate = perm + 64, *count = mate + 64;
+  const lob::RitzScratch<T> W{W1, W2, S.X1, S.X2, S.X3, d, dsc, piv, taken, perm, lob::JacobiScratch<T>{mate, jc, js, count}};
+  const lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev};
+  const BcgTeam tm;
+  if (mode == 0) lob::start_factor(Sm, W, tm);
+  if (mode == 1 || mode == 3) lob::ritz_step(Sm, W, mode == 1, step, tm);
+  if (mode == 2) lob::residual_test(Sm, partial, kLobResBlocks, step, tm);
 }
 
 }  // namespace hifamd

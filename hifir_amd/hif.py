@@ -680,6 +680,43 @@ class HIF:
                                  tail=(_p(ranks),))
         return x, fl, it, ranks
 
+    def lobpcg(self, k=8, nev=None, X0=None, seed=0, tol=1e-8, maxit=200, deftol=1e-12, full_rank=False):
+        """LOBPCG for the nev smallest eigenpairs of the Hermitian matrix of set_matrix, preconditioned by the hierarchy
+        (hifamd_lobpcg / _dev): a block of k <= 16 candidates (nev <= k, default k; the others are guard columns), started
+        from X0 ([n][k], host array or CUDA tensor; its width is k) or from the generated block of `seed`.  A column is
+        converged when ||A x - lambda x||_2 <= tol ||A||_inf.  Needs set_matrix and is_hermitian(); with a basis filter
+        (set_nsp_basis) it returns the smallest eigenvalues on the complement of span(Q).  Returns
+        (lam, X, res, flags, steps): lam [k] ascending, X [n][k] orthonormal (a CUDA tensor where X0 is one), res [k] the last
+        residuals, flags [k] 0 converged / 1 breakdown / 2 not converged at maxit, steps (one apply plus one SpMM each);
+        last_lobpcg_info keeps the call's info3 (steps, rank of the last basis, largest Jacobi sweep count)."""
+        dev = X0 is not None and _is_torch(X0)
+        if X0 is not None:
+            if dev:
+                import torch
+
+                X0 = self._dev_block(X0, "X0")
+                X = torch.empty((X0.shape[0], X0.shape[1]), dtype=X0.dtype, device=X0.device)
+                io0, io1 = (X0.data_ptr(), X0.stride(0)), (X.data_ptr(), X.stride(0))
+            else:
+                X0 = np.ascontiguousarray(X0, dtype=self.dtype)
+                if X0.ndim != 2 or X0.shape[0] != self.nrows():
+                    raise HifAmdError(2, "X0: expected an [nrows][k] block")
+                io0 = (_p(X0), X0.shape[1])
+            k = int(X0.shape[1])
+        else:
+            io0 = (None, 0)
+        if not dev:
+            X = np.empty((self.nrows(), max(int(k), 1)), dtype=self.dtype)
+            io1 = (_p(X), X.shape[1])
+        nev = int(k) if nev is None else int(nev)
+        lam, res = np.zeros(max(int(k), 1)), np.zeros(max(int(k), 1))
+        fl, info = np.zeros(max(int(k), 1), dtype=np.int32), np.zeros(3, dtype=np.int32)
+        fn = lib().hifamd_lobpcg_dev if dev else lib().hifamd_lobpcg
+        _check(fn(self._h, int(k), nev, *io0, int(seed), float(tol), float(deftol), int(maxit), -1 if full_rank else 0, _p(lam),
+                  *io1, _p(res), _p(fl), _p(info)))
+        self.last_lobpcg_info = info
+        return lam, X, res, fl, int(info[0])
+
     def bgcr(self, b, block=64, restart=10, rtol=1e-6, maxit=500, deftol=1e-12, full_rank=False):
         """Restarted block GCR (x0 = 0; block GMRES(restart) with right preconditioning in exact arithmetic) for a general
         pair (A, M) (hifamd_bgcr_batch / _dev): the columns of b ([n] or [n][nrhs], host array or CUDA tensor) are cut into

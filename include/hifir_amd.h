@@ -468,6 +468,48 @@ HifAmdStatus hifamd_bcg_batch(HifAmdHdl h, const void *B, int64_t ldb, void *X, 
 HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void *dX, int64_t ldx, int64_t nrhs, int block,
                                   double rtol, double deftol, int maxit, int64_t rank, int *flags, int *iters, int *ranks);
 
+/* ---- LOBPCG: the smallest eigenpairs of a Hermitian pair (A, M) -------------------------------- */
+/* Knyazev's locally optimal block preconditioned CG for the nev smallest eigenvalues of the Hermitian matrix given to
+ * hifamd_set_matrix and their eigenvectors, with the hierarchy as preconditioner.  A block of k <= 16 candidates gives the
+ * basis S = [X W P] of s = 3 k <= 48 columns; columns nev .. k - 1 are guard columns, which sharpen convergence and never
+ * hold the solve up.  ||A||_inf is the largest row sum of |a_ij|.
+ *   start: X = X0 ([n][k], row stride ldx0), or, for X0 == NULL, entry (i, j) from counter 16 i + j + 1 of the probe stream
+ *     of `seed` (the imaginary part from counter 16 (n + i) + j + 1; hifamd_nsp_find states the generator); with a basis
+ *     filter on HIFAMD_S in force X <- (I - Q Q^H) X; G = X^H X = S^H S, the pivoted upper Cholesky factor of
+ *     hifamd_bcg_batch stopped at deftol; X <- X I[:, piv] inv(S[:, piv]); AX = A X; X^H AX = V Theta V^H (ascending),
+ *     X <- X V, AX <- AX V, lambda = Theta, P = AP = 0
+ *   loop: R = AX - X diag(lambda); res_j = ||r_j||_2 / ||A||_inf (||x_j|| = 1 by construction); conv_j = res_j <= tol;
+ *     every j < nev converged, or steps == maxit: end.  W = M^{-1} R on the columns that are not converged (filtered like
+ *     every apply; a converged column of W is an exact zero: soft locking); AW = A W; steps += 1;
+ *     GB = S^H S, GA = S^H [AX AW AP] (Hermitian parts); D = diag(GB)^(-1/2) (0 where the diagonal is not positive);
+ *     D GB D = T^H T pivoted as above, rank r; E = D I[:, piv] inv(T[:, piv]); E^H GA E = V Theta V^H by a cyclic Jacobi
+ *     method (ascending; equal values in index order); C = E V[:, :k]; lambda = Theta[:k]; Cp = C with its first k rows
+ *     zero; X <- S C, AX <- AS C, P <- S Cp, AP <- AS Cp
+ * A step is one batched M^{-1} apply plus one SpMM on k columns, one pass for both Grams and one row-local
+ * [n][48] x [48][32] product on the f64 matrix cores, and the small matrices in one workgroup; the host reads back one
+ * integer per step.  Sums run in a fixed order: the same inputs give the same bits.  The eigenvectors come back
+ * orthonormal; their phase (sign) is not fixed.  Smallest eigenvalues of A only: no largest or interior ones, no
+ * generalized problem.  The pair has to be definite for the iteration to converge; on an indefinite pair it runs to maxit
+ * (flag 2), which is not refused.
+ * Refusals, in this order: a NULL handle (HIFAMD_NULL_OBJ); k outside [1, 16], nev outside [1, k], tol <= 0, maxit < 1,
+ * deftol outside (0, 1), a row stride below k (HIFAMD_MISMATCHED_SIZES); a handle that is not finalized (HIFAMD_BAD_PREC;
+ * one finalized with max_nrhs < k: HIFAMD_MISMATCHED_SIZES), no matrix, a hierarchy that is not Hermitian, a constant-mode
+ * filter on HIFAMD_S (HIFAMD_BAD_PREC, as hifamd_pcg_batch; with a basis filter the iteration runs on the complement of
+ * span(Q) and returns the smallest eigenvalues there); a start block that is rank deficient (a Cholesky rank below k) or
+ * not finite, or whose X^H A X is not finite (HIFAMD_BAD_PREC).
+ * Out: lambda[k], X ([n][k], row stride ldx), res[k] (the last res_j), flags[k] -- per column by its own last res_j:
+ * 0 converged, 2 not converged at maxit, 1 breakdown (a non-finite Gram, a basis of rank below k, a Jacobi method that has
+ * not ended after 30 sweeps: lambda and X of the last completed step are returned) -- and info3 = {steps, rank of the
+ * basis in the last step, largest Jacobi sweep count}; lambda, res, flags, info3 may be NULL.  rank: 0 numerical rank,
+ * -1 full.  Host pointers; the _dev variant takes device pointers for X0 and X (the other arrays stay host arrays) and
+ * returns when the solve is done. */
+HifAmdStatus hifamd_lobpcg(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, int64_t ldx0, uint64_t seed, double tol,
+                           double deftol, int maxit, int64_t rank, double *lambda, void *X, int64_t ldx, double *res,
+                           int *flags, int *info3);
+HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
+                               double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
+                               int *flags, int *info3);
+
 /* ---- restarted block GCR for a general pair (A, M): a shared block space without conditions ---- */
 /* Restarted block GCR with x0 = 0: in exact arithmetic block GMRES(restart) with right preconditioning, flexible by
  * construction.  The batch is cut into tiles of `block` <= 64 columns, and the columns of a tile share ONE block Krylov

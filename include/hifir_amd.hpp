@@ -345,6 +345,27 @@ class HIF {
     return std::make_tuple(std::move(X), std::move(flags), std::move(iters), std::move(ranks));
   }
 
+  // ---- LOBPCG: the nev smallest eigenpairs of the Hermitian matrix A, preconditioned by M (hifamd_lobpcg) ----
+  // A block of k <= 16 candidates started from X0 ([n][k] row-interleaved) or, for an empty X0, from the generated block of
+  // `seed`.  -> (lambda, X, res, flags, steps): lambda ascending, X [n][k] orthonormal, res_j = ||A x_j - lambda_j x_j|| /
+  // ||A||_inf at the last test, per column flag 0 converged, 1 breakdown, 2 not converged at maxit.
+  template <class Matrix, class ArrayType>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, int> lobpcg(
+      const Matrix &A, const int k, const int nev, const ArrayType &X0, const double tol, const int maxit,
+      const std::uint64_t seed = 0, const double deftol = 1e-12, const bool full_rank = false) {
+    ensure_matrix(A);
+    if (k < 1) throw std::runtime_error("hifir_amd: lobpcg needs k >= 1");
+    if (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k)
+      throw std::runtime_error("hifir_amd: lobpcg needs an empty X0 or one of nrows() * k entries");
+    ArrayType X((std::size_t)nrows() * k);
+    std::vector<double> lambda(k, 0.0), res(k, 0.0);
+    std::vector<int> flags(k, 0);
+    int info3[3] = {0, 0, 0};
+    detail::check(hifamd_lobpcg(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit, full_rank ? -1 : 0,
+                                lambda.data(), X.data(), k, res.data(), flags.data(), info3));
+    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+  }
+
   // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
   // Needs an is_symm hierarchy: is_hermitian(); neither A nor M has to be definite.  iters counts iterations (one apply
   // plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
