@@ -1,7 +1,8 @@
-// The small-matrix arithmetic of the block CG driver (Engine::bcg_tile, k_bcg_small in kernels.hip.hpp): Hermitian Grams of
-// at most 64 x 64, their pivoted / unpivoted Cholesky factors, triangular inverses and the products and quadratic forms around
-// them.  Plain C++17, no HIP include: the one-workgroup kernel and host programs built with g++
-// (tests/cpp/blockcg_small_test.cpp) run the same code.
+// The small-matrix arithmetic and every decision of the block CG driver (Engine::bcg_tile, k_bcg_beta and k_bcg_small in
+// kernels.hip.hpp): Hermitian Grams of at most 64 x 64, their Cholesky factors, triangular inverses, products and quadratic
+// forms; the constructions that blockgcr_small.hpp and lobpcg_small.hpp share with it; the tile's decisions, mode by mode.
+// Plain C++17, no HIP include: the one-workgroup kernels and host programs built with g++ (tests/cpp/blockcg_small_test.cpp,
+// tests/cpp/blockcg_tile_test.cpp) run the same code.
 //
 // Every matrix is row-major with the row stride kLd = 64, whatever its size.  T is double or a struct {double x, y}.
 // A function is called by every thread of a team: Team gives rank() (0 .. size() - 1), size() and sync() (a barrier that also
@@ -9,6 +10,7 @@
 // fixed order, so the result does not depend on the team's size.  A function ends with a barrier unless it says otherwise.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #ifndef HIFAMD_HD
@@ -27,6 +29,15 @@
 #endif
 
 namespace hifamd {
+
+// what the states of the lock-step solvers (PCG, BiCGSTAB, symmetric QMR, ...) and of the block methods share
+struct KrylovState {
+  double *bnorm;                    // [64]  ||b||
+  int *iter, *flag, *active, *ctl;  // [64] each; ctl[0]: columns still active
+  int maxit;
+  double rtol;
+};
+
 namespace bcg {
 
 constexpr int kLd = 64;  // row stride (and the largest block)
@@ -239,6 +250,180 @@ HIFAMD_HD inline void quad_forms(const T *H, const T *C, int r, int s, T *HC, do
     for (int i = 0; i < r; ++i) tot += re(mul(cj(C[i * kLd + j]), HC[i * kLd + j]));
     out[j] = std::sqrt(tot > 0.0 ? tot : 0.0);
   }
+  tm.sync();
+}
+
+// ---- what block CG, block GCR and LOBPCG build from the functions above ---------------------------------------------------------
+// The small state of a tile of s <= 64 columns (the kernels' BcgState).  bnorm: beta = ||b||; active: 1 for a column of the block (not
+// zero, not excluded); ctl: [0] 1 while the tile runs, [1] rank after the start, [2] rank during the last step, [3] current rank
+template <class T>
+struct Small : KrylovState {
+  T *C, *E1, *E2, *G;  // [64][64] each: R = Q C | the two coefficient matrices of the next row pass | the summed Gram
+  double *relres;      // [64]  ||r|| / ||b|| at the last test (infinite before the first)
+  double deftol;
+};
+
+// What a one-workgroup kernel works in: W1 | W2 | d [64] | piv [64] | taken [64], carved from its dynamic LDS of bytes() bytes
+template <class T>
+struct Work {
+  T *W1, *W2;
+  double *d;
+  int *piv, *taken;
+  static constexpr size_t bytes() { return 2 * kLd * kLd * sizeof(T) + kLd * sizeof(double) + 2 * kLd * sizeof(int); }
+  HIFAMD_HD static Work carve(void *base) {
+    T *W1 = (T *)base;
+    double *d = (double *)(W1 + 2 * kLd * kLd);
+    return Work{W1, W1 + kLd * kLd, d, (int *)(d + kLd), (int *)(d + kLd) + kLd};
+  }
+};
+
+// to = from on rows x cols, zero on the rest of the 64 x 64 (the state's matrices into LDS: no inner loop reads HBM)
+template <class T, class Team>
+HIFAMD_HD inline void stage(const T *from, T *to, int rows, int cols, const Team &tm) {
+  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) {
+    T v;
+    set(v, 0.0);
+    if (e / kLd < rows && e % kLd < cols) v = from[e];  // (not a choice between two lvalues: the zero stays in registers)
+    to[e] = v;
+  }
+  tm.sync();
+}
+
+template <class T, class Team>
+HIFAMD_HD inline void clear(T *E, const Team &tm) {
+  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) set(E[e], 0.0);
+  tm.sync();
+}
+
+template <class Team>
+HIFAMD_HD inline void set_state(const KrylovState &S, int v, const Team &tm) {  // ctl[0] = v
+  if (tm.rank() == 0) S.ctl[0] = v;
+  tm.sync();
+}
+
+// The tile is over: a block column gets flag 0 where res (its last tested ratio) is <= rtol, else `miss`; `done` is its count
+template <class Team>
+HIFAMD_HD inline void end_tile(const KrylovState &S, const double *res, int s, int miss, int done, const Team &tm) {
+  for (int c = tm.rank(); c < s; c += tm.size())
+    if (S.active[c]) S.flag[c] = res[c] <= S.rtol ? 0 : miss, S.iter[c] = done;
+  set_state(S, 0, tm);
+}
+
+// The Hermitian m x m matrix in W.W1 -> pivoted Cholesky factor S (r x m) in W.W2 and, unless it broke down or r == 0,
+// E1 (cleared by the caller) = I[:, piv] inv(S[:, piv]); W.W1 is overwritten.
+template <class T, class Team>
+HIFAMD_HD inline Chol factor_staged(const Work<T> &W, int m, double deftol, T *E1, const Team &tm) {
+  const Chol f = chol(W.W1, m, deftol, true, W.W2, W.piv, W.d, W.taken, tm);
+  if (!f.bad && f.r > 0) tri_inv(W.W2, W.piv, f.r, W.W1, tm), select_rows(W.W1, W.piv, f.r, m, f.r, E1, tm);
+  return f;
+}
+
+// The same on the summed Gram G (m x m), staged into W.W1 and made Hermitian; E1 and E2 are cleared first.
+template <class T, class Team>
+HIFAMD_HD inline Chol factor_basis(const T *G, int m, double deftol, const Work<T> &W, T *E1, T *E2, const Team &tm) {
+  clear(E1, tm);
+  clear(E2, tm);
+  stage(G, W.W1, m, m, tm);
+  hermitize(W.W1, W.W2, m, tm);
+  return factor_staged(W, m, deftol, E1, tm);
+}
+
+// C (r x s) <- S C (r_new x s), zero-padded, with the factor S (r_new x r) in W.W2; W.W1 and G are scratch
+template <class T, class Team>
+HIFAMD_HD inline void advance_C(const Work<T> &W, int r_new, int r, int s, T *C, T *G, const Team &tm) {
+  stage(C, W.W1, r, s, tm);
+  matmul(W.W2, W.W1, false, r_new, r, s, (const double *)nullptr, G, tm);
+  stage(G, C, r_new, s, tm);
+}
+
+// E1 = A C diag(beta) (a x s), A (a x r) in LDS, beta = 0 for a column outside the block; Cw (LDS) receives C, d the betas
+template <class T, class Team>
+HIFAMD_HD inline void times_C_beta(const T *A, int a, int r, int s, const Small<T> &S, T *Cw, double *d, const Team &tm) {
+  for (int c = tm.rank(); c < kLd; c += tm.size()) d[c] = (c < s && S.active[c]) ? S.bnorm[c] : 0.0;
+  stage(S.C, Cw, r, s, tm);
+  matmul(A, Cw, false, a, r, s, d, S.E1, tm);
+}
+
+// ---- the decisions of a block CG tile: what k_bcg_beta and k_bcg_small run, mode by mode ----------------------------------
+// The start's scalars from b2[c] = |b_c|^2: beta_c, and which columns enter the block.  A zero column is done (x = 0,
+// flag 0), a column whose |b|^2 is not finite is excluded (x = 0, flag 1); both 0 iterations.
+template <class T, class Team>
+HIFAMD_HD inline void start_columns(const Small<T> &S, int nc, const double *b2, const Team &tm) {
+  for (int c = tm.rank(); c < nc; c += tm.size()) {
+    const double v = b2[c];
+    const bool in = v != 0.0 && finite(v);
+    S.bnorm[c] = in ? std::sqrt(v) : 0.0, S.active[c] = in ? 1 : 0, S.flag[c] = (v == 0.0 || in) ? 0 : 1;
+    S.iter[c] = 0, S.relres[c] = HUGE_VAL;
+  }
+  if (tm.rank() == 0) S.ctl[0] = 1, S.ctl[1] = S.ctl[2] = 0, S.ctl[3] = nc;
+  tm.sync();
+}
+
+// A breakdown (a Cholesky's, or a next block of rank 0) ends the tile: every column of the block that was not <= rtol at
+// its last test gets flag 1, all get the completed steps, and E1 = E2 = 0 so that the step's remaining passes change nothing.
+// Mode 1, the start: G = R^H Z -> pivoted Cholesky S, rank r; E1 = I[:, piv] inv(S[:, piv]), E2 = 0, C = S.  r == 0 and not bad: every
+// column is zero or excluded, the flags stay.  (Every mode leaves a tile that is over alone, and reads ctl before thread 0 may change it.)
+template <class T, class Team>
+HIFAMD_HD inline void start_factor(const Small<T> &S, const Work<T> &W, int s, const Team &tm) {
+  if (S.ctl[0] == 0) return;
+  tm.sync();
+  const Chol f = factor_basis(S.G, s, S.deftol, W, S.E1, S.E2, tm);
+  if (f.bad) return end_tile(S, S.relres, s, 1, 0, tm);
+  if (f.r == 0) return set_state(S, 0, tm);
+  stage(W.W2, S.C, f.r, s, tm);
+  if (tm.rank() == 0) S.ctl[1] = S.ctl[2] = S.ctl[3] = f.r;
+  tm.sync();
+}
+
+// Mode 2 of step k: Sigma = P^H A P (r x r) -> unpivoted Cholesky, alpha = Sigma^-1; E1 = alpha C diag(beta), E2 = alpha.
+// A Sigma that is not positive definite is a breakdown after k - 1 steps.
+template <class T, class Team>
+HIFAMD_HD inline void step_alpha(const Small<T> &S, const Work<T> &W, int s, int k, const Team &tm) {
+  if (S.ctl[0] == 0) return;
+  tm.sync();
+  const int r = S.ctl[3];
+  clear(S.E1, tm);
+  clear(S.E2, tm);
+  stage(S.G, W.W1, r, r, tm);
+  hermitize(W.W1, W.W2, r, tm);
+  const Chol f = chol(W.W1, r, S.deftol, false, W.W2, W.piv, W.d, W.taken, tm);
+  if (f.bad) return end_tile(S, S.relres, s, 1, k - 1, tm);
+  tri_inv(W.W2, W.piv, f.r, W.W1, tm);
+  matmul(W.W1, W.W1, true, f.r, f.r, f.r, (const double *)nullptr, W.W2, tm);  // alpha = Ti Ti^H
+  stage(W.W2, S.E2, f.r, f.r, tm);
+  times_C_beta(W.W2, f.r, f.r, s, S, W.W1, W.d, tm);
+  if (tm.rank() == 0) S.ctl[2] = f.r;
+  tm.sync();
+}
+
+// Mode 3 of step k: H = Q^H Q (r x r) -> relres_j = sqrt(c_j^H H c_j).  Every column of the block <= rtol: flag 0, k
+// iterations; k == maxit: flag 0 / 2.  Otherwise the tile goes on.
+template <class T, class Team>
+HIFAMD_HD inline void step_test(const Small<T> &S, const Work<T> &W, int s, int k, const Team &tm) {
+  if (S.ctl[0] == 0) return;
+  tm.sync();
+  const int r = S.ctl[3];
+  stage(S.G, W.W1, r, r, tm);
+  hermitize(W.W1, W.W2, r, tm);
+  stage(S.C, W.W2, r, s, tm);
+  quad_forms(W.W1, W.W2, r, s, S.G, S.relres, tm);
+  bool all = true;
+  for (int c = 0; c < s; ++c) all = all && (!S.active[c] || S.relres[c] <= S.rtol);
+  if (all || k >= S.maxit) end_tile(S, S.relres, s, 2, k, tm);
+}
+
+// Mode 4 of step k: G = Q^H W (r x r) -> pivoted Cholesky S, rank r'; E1 = I[:, piv] inv(S[:, piv]), E2 = S^H, C <- S C,
+// r <- r'.  A bad Gram or r' == 0 is a breakdown after k steps.
+template <class T, class Team>
+HIFAMD_HD inline void step_next(const Small<T> &S, const Work<T> &W, int s, int k, const Team &tm) {
+  if (S.ctl[0] == 0) return;
+  tm.sync();
+  const int r = S.ctl[3];
+  const Chol f = factor_basis(S.G, r, S.deftol, W, S.E1, S.E2, tm);
+  if (f.bad || f.r == 0) return end_tile(S, S.relres, s, 1, k, tm);
+  adjoint(W.W2, f.r, r, S.E2, tm);
+  advance_C(W, f.r, r, s, S.C, S.G, tm);
+  if (tm.rank() == 0) S.ctl[3] = f.r;
   tm.sync();
 }
 

@@ -12,50 +12,15 @@ namespace bgcr {
 
 using bcg::kLd;
 
-// The small state of a tile of s <= 64 columns.  The matrices are row-major with the row stride 64.
+// The small state of a tile of s <= 64 columns: block CG's, and what the cycles add.  relres: the recurrence's rel_j.
 //   ctl[0]: 0 the tile is over, 1 inside a cycle, 2 the cycle has ended (the next one starts with a true residual)
 //   ctl[1]: rank after the start of the first cycle; ctl[2]: rank of the residual block during the last step
 //   ctl[3]: current rank r of the residual block; aux[0]: rank q of the step's direction block
 template <class T>
-struct Small {
-  T *C, *E1, *E2, *G;                 // relative residual = Rh C | the coefficients of the next row pass | the summed Gram
-  double *bnorm, *rho, *tres, *relres, *mu;  // [64]: ||b||, ||r|| at the cycle's start, rho / beta, the recurrence's rel; mu[0]
-  int *iter, *flag, *active, *live;   // [64]; live: a block column whose residual is not an exact zero
-  int *ctl, *aux;
-  double rtol, deftol;
-  int maxit;
+struct Small : bcg::Small<T> {
+  double *rho, *tres, *mu;  // [64]: ||r|| at the cycle's start, rho / beta (the last true residual's ratio); mu[0]
+  int *live, *aux;          // [64]; live: a block column whose residual is not an exact zero
 };
-
-// two 64 x 64 working matrices, d [64], piv [64], taken [64] (LDS in the kernel)
-template <class T>
-struct Work {
-  T *W1, *W2;
-  double *d;
-  int *piv, *taken;
-};
-
-// The tile is over: a block column gets flag 0 where its last true residual was <= rtol and `miss` otherwise, and the
-// tile's steps.
-template <class T, class Team>
-HIFAMD_HD inline void end_tile(const Small<T> &S, int s, int miss, int steps, const Team &tm) {
-  for (int c = tm.rank(); c < s; c += tm.size())
-    if (S.active[c]) {
-      S.flag[c] = S.tres[c] <= S.rtol ? 0 : miss;
-      S.iter[c] = steps;
-    }
-  if (tm.rank() == 0) S.ctl[0] = 0;
-  tm.sync();
-}
-
-template <class T, class Team>
-HIFAMD_HD inline void copy_in(const T *from, T *to, int rows, int cols, const Team &tm) {  // zero outside rows x cols
-  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) {
-    T z;
-    bcg::set(z, 0.0);
-    to[e] = (e / kLd < rows && e % kLd < cols) ? from[e] : z;
-  }
-  tm.sync();
-}
 
 // A cycle's start.  rho[c] holds ||r_c||^2 of the true residual; it becomes ||r_c||, tres[c] = ||r_c|| / ||b_c|| (0 for a
 // column outside the block).  All tres <= rtol: flags 0, the tile is over.  steps == maxit: flag 0 / 2.  From the second
@@ -82,50 +47,31 @@ HIFAMD_HD inline void cycle_start(const Small<T> &S, int s, int cycle, int steps
   }
   const double mu_prev = S.mu[0];
   tm.sync();
-  if (all) return end_tile(S, s, 0, steps, tm);
-  if (steps >= S.maxit) return end_tile(S, s, 2, steps, tm);
-  if (cycle > 0 && !(mu < mu_prev)) return end_tile(S, s, 1, steps, tm);
+  if (all) return bcg::end_tile(S, S.tres, s, 0, steps, tm);
+  if (steps >= S.maxit) return bcg::end_tile(S, S.tres, s, 2, steps, tm);
+  if (cycle > 0 && !(mu < mu_prev)) return bcg::end_tile(S, S.tres, s, 1, steps, tm);
   if (tm.rank() == 0) S.mu[0] = mu, S.ctl[0] = 1;
-  tm.sync();
-}
-
-// Loads the summed Gram (m x m, made Hermitian) into W.W1 and factors it (pivoted): S in W.W2.
-template <class T, class Team>
-HIFAMD_HD inline bcg::Chol factor(const Small<T> &S, const Work<T> &W, int m, const Team &tm) {
-  copy_in(S.G, W.W1, m, m, tm);
-  bcg::hermitize(W.W1, W.W2, m, tm);
-  return bcg::chol(W.W1, m, S.deftol, true, W.W2, W.piv, W.d, W.taken, tm);
-}
-
-template <class T, class Team>
-HIFAMD_HD inline void clear(T *E, const Team &tm) {
-  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) bcg::set(E[e], 0.0);
   tm.sync();
 }
 
 // Mode 1, after cycle_start: G = Rn^H Rn of the normalized residuals -> S (r x s), rank r; E1 = I[:, piv] inv(S[:, piv])
 // (Rh = Rn E1), C = S diag(rho / beta).  r == 0 or a bad Gram: every column not <= rtol gets flag 1, the tile is over.
 template <class T, class Team>
-HIFAMD_HD inline void cycle_factor(const Small<T> &S, const Work<T> &W, int s, bool first, int steps, const Team &tm) {
+HIFAMD_HD inline void cycle_factor(const Small<T> &S, const bcg::Work<T> &W, int s, bool first, int steps, const Team &tm) {
   if (S.ctl[0] != 1) return;
   tm.sync();
-  clear(S.E1, tm);
-  clear(S.E2, tm);
-  const bcg::Chol f = factor(S, W, s, tm);
+  const bcg::Chol f = bcg::factor_basis(S.G, s, S.deftol, W, S.E1, S.E2, tm);
   if (tm.rank() == 0) {
     if (first) S.ctl[1] = S.ctl[2] = f.r;
     S.ctl[3] = f.r;
   }
   tm.sync();
-  if (f.bad || f.r == 0) return end_tile(S, s, 1, steps, tm);
-  const int r = f.r;
-  bcg::tri_inv(W.W2, W.piv, r, W.W1, tm);
-  bcg::select_rows(W.W1, W.piv, r, s, r, S.E1, tm);
+  if (f.bad || f.r == 0) return bcg::end_tile(S, S.tres, s, 1, steps, tm);
   for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) {
     const int i = e / kLd, j = e % kLd;
     T v;
     bcg::set(v, 0.0);
-    S.C[e] = (i < r && j < s) ? bcg::scale(S.tres[j], W.W2[e]) : v;
+    S.C[e] = (i < f.r && j < s) ? bcg::scale(S.tres[j], W.W2[e]) : v;
   }
   tm.sync();
 }
@@ -134,78 +80,51 @@ HIFAMD_HD inline void cycle_factor(const Small<T> &S, const Work<T> &W, int s, b
 // P_j = Z E1).  q == 0: the cycle ends (the coefficients stay zero, so the step's remaining passes change nothing).  A bad
 // Gram ends the tile as in mode 1.
 template <class T, class Team>
-HIFAMD_HD inline void step_basis(const Small<T> &S, const Work<T> &W, int s, int steps, const Team &tm) {
+HIFAMD_HD inline void step_basis(const Small<T> &S, const bcg::Work<T> &W, int s, int steps, const Team &tm) {
   if (S.ctl[0] != 1) return;
   const int r = S.ctl[3];
   tm.sync();
-  clear(S.E1, tm);
-  clear(S.E2, tm);
-  const bcg::Chol f = factor(S, W, r, tm);
+  const bcg::Chol f = bcg::factor_basis(S.G, r, S.deftol, W, S.E1, S.E2, tm);
   if (tm.rank() == 0) S.ctl[2] = r, S.aux[0] = f.r;
   tm.sync();
-  if (f.bad) return end_tile(S, s, 1, steps, tm);
-  if (f.r == 0) {
-    if (tm.rank() == 0) S.ctl[0] = 2;
-    tm.sync();
-    return;
-  }
-  bcg::tri_inv(W.W2, W.piv, f.r, W.W1, tm);
-  bcg::select_rows(W.W1, W.piv, f.r, r, f.r, S.E1, tm);
+  if (f.bad) return bcg::end_tile(S, S.tres, s, 1, steps, tm);
+  if (f.r == 0) bcg::set_state(S, 2, tm);
 }
 
 // Mode 3: G = D = Q_j^H Rh (q x r, as it is): E1 = D C diag(beta) (X += P_j E1), E2 = D (Rh -= Q_j E2)
 template <class T, class Team>
-HIFAMD_HD inline void step_coeff(const Small<T> &S, const Work<T> &W, int s, const Team &tm) {
+HIFAMD_HD inline void step_coeff(const Small<T> &S, const bcg::Work<T> &W, int s, const Team &tm) {
   if (S.ctl[0] != 1) return;
   const int r = S.ctl[3], q = S.aux[0];
   tm.sync();
-  clear(S.E1, tm);
-  copy_in(S.G, W.W1, q, r, tm);
-  copy_in(S.C, W.W2, r, s, tm);
-  for (int c = tm.rank(); c < kLd; c += tm.size()) W.d[c] = (c < s && S.active[c]) ? S.bnorm[c] : 0.0;
-  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) S.E2[e] = W.W1[e];
-  tm.sync();
-  bcg::matmul(W.W1, W.W2, false, q, r, s, (const double *)W.d, S.E1, tm);
+  bcg::clear(S.E1, tm);
+  bcg::stage(S.G, W.W1, q, r, tm);
+  bcg::stage(W.W1, S.E2, q, r, tm);
+  bcg::times_C_beta(W.W1, q, r, s, S, W.W2, W.d, tm);
 }
 
 // Mode 4: G = H = Rh^H Rh (r x r): rel_j = sqrt(max(0, c_j^H H c_j)).  All rel <= rtol, steps == maxit or the cycle's last
 // step (`last`): the cycle ends, BEFORE H is factored.  Otherwise H -> S (r' x r): r' == 0 ends the cycle, a bad H the tile;
 // E1 = I[:, piv] inv(S[:, piv]) (Rh <- Rh E1), C <- S C, r <- r'.
 template <class T, class Team>
-HIFAMD_HD inline void step_test(const Small<T> &S, const Work<T> &W, int s, int steps, bool last, const Team &tm) {
+HIFAMD_HD inline void step_test(const Small<T> &S, const bcg::Work<T> &W, int s, int steps, bool last, const Team &tm) {
   if (S.ctl[0] != 1) return;
   const int r = S.ctl[3];
   tm.sync();
-  clear(S.E1, tm);
-  clear(S.E2, tm);
-  copy_in(S.G, W.W1, r, r, tm);
+  bcg::clear(S.E1, tm);
+  bcg::clear(S.E2, tm);
+  bcg::stage(S.G, W.W1, r, r, tm);
   bcg::hermitize(W.W1, W.W2, r, tm);
-  copy_in(S.C, W.W2, r, s, tm);
+  bcg::stage(S.C, W.W2, r, s, tm);
   bcg::quad_forms(W.W1, W.W2, r, s, S.G, S.relres, tm);
   bool all = true;
   for (int c = 0; c < s; ++c) all = all && S.relres[c] <= S.rtol;
   tm.sync();
-  if (all || steps >= S.maxit || last) {
-    if (tm.rank() == 0) S.ctl[0] = 2;
-    tm.sync();
-    return;
-  }
-  const bcg::Chol f = bcg::chol(W.W1, r, S.deftol, true, W.W2, W.piv, W.d, W.taken, tm);
-  if (f.bad) return end_tile(S, s, 1, steps, tm);
-  if (f.r == 0) {
-    if (tm.rank() == 0) S.ctl[0] = 2;
-    tm.sync();
-    return;
-  }
-  bcg::tri_inv(W.W2, W.piv, f.r, W.W1, tm);
-  bcg::select_rows(W.W1, W.piv, f.r, r, f.r, S.E1, tm);
-  copy_in(S.C, W.W1, r, s, tm);
-  bcg::matmul(W.W2, W.W1, false, f.r, r, s, (const double *)nullptr, S.G, tm);  // S C
-  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) {
-    T v;
-    bcg::set(v, 0.0);
-    S.C[e] = (e / kLd < f.r && e % kLd < s) ? S.G[e] : v;
-  }
+  if (all || steps >= S.maxit || last) return bcg::set_state(S, 2, tm);
+  const bcg::Chol f = bcg::factor_staged(W, r, S.deftol, S.E1, tm);
+  if (f.bad) return bcg::end_tile(S, S.tres, s, 1, steps, tm);
+  if (f.r == 0) return bcg::set_state(S, 2, tm);
+  bcg::advance_C(W, f.r, r, s, S.C, S.G, tm);
   if (tm.rank() == 0) S.ctl[3] = f.r;
   tm.sync();
 }

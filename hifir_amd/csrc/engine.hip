@@ -3045,6 +3045,39 @@ class Engine : public EngineBase {
     if (nsp_on) throw Error(HIFAMD_BAD_PREC, who + " does not support " + filter + " (hifamd_set_nsp_const)");
   }
 
+  // ---- what the block methods (block CG, block GCR, LOBPCG) share on top of that ------------------------------------
+  // G = a^H b ([n][nc] each) through the kBcgBlocks partial matrices in pt
+  void block_gram(const D *a, const D *b, int nc, D *pt, D *G) {
+    hipLaunchKernelGGL((k_bcg_gram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, lv[0]->n, nc, a, b, pt);
+    hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, G);
+  }
+  // more than 64 KB of dynamic LDS: the function's limit is raised first, once per function whichever solvers share it
+  std::map<const void *, size_t> lds_limit;
+  void raise_lds(const void *fn, size_t bytes) {
+    size_t &have = lds_limit[fn];
+    if (bytes <= 64 * 1024 || bytes <= have) return;
+    HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
+  }
+  // the tile's rank after its start and during its last step (ctl[1..2]) -> ranks[0..1] (may be null)
+  void block_ranks(const KrylovState &S, int *ranks) {
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+  }
+  void block_check(int block, double deftol, int restart = 1) {
+    if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
+    if (restart < 1 || restart > HIFAMD_BGCR_MAX_RESTART) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= restart <= HIFAMD_BGCR_MAX_RESTART");
+    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < deftol < 1");
+  }
+  // krylov_batch on tiles of `block` columns: tile(b, x, nc, flags, iters, ranks of tile t)
+  template <class Check, class Tile>
+  void block_batch(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int block, int *flags, int *iters, int *ranks, Check check, Tile tile) {
+    const int width = block >= 1 && block <= 64 ? block : 64;  // (a block out of range: check refuses it before any tile)
+    auto one = [&](const D *b, D *x, int nc, int *fl, int *it, int *) { tile(b, x, nc, fl, it, ranks ? ranks + 2 * ((b - dB) / width) : nullptr); };
+    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, check, one, width);
+  }
+
   // ---- right-preconditioned restarted GMRES, batched over columns ----------------------------------
   // The reference's driver (examples/advanced/gmres.hpp:19-123: MGS Arnoldi, Givens rotations, relative
   // residual |y_{j+1}| / ||b||, flags 0 converged / 1 stagnated / 2 reached maxit) run for up to 64
@@ -3429,21 +3462,14 @@ class Engine : public EngineBase {
     krylov_vectors(4, vec);
     if (ir_part.bytes < part) ir_part.alloc(part);
     D *Q = kr_vec[0].as<D>(), *W = kr_vec[1].as<D>(), *P = kr_vec[2].as<D>(), *Tm = kr_vec[3].as<D>(), *pt = ir_part.as<D>();
-    const size_t lds_pass = 2 * mat, lds_small = 2 * mat + 64 * sizeof(double) + 128 * sizeof(int);
-    if (lds_small > 64 * 1024 && !bcg_lds_raised) {  // (the small kernel's 65 KB; a complex handle's 128 KB)
-      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_xq<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
-      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_qp<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
-      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-      bcg_lds_raised = true;
-    }
+    const size_t lds_pass = 2 * mat, lds_small = bcg::Work<D>::bytes();  // (the small kernel's 65 KB; a complex handle's 129 KB)
+    raise_lds((const void *)k_bcg_xq<D>, lds_pass);
+    raise_lds((const void *)k_bcg_qp<D>, lds_pass);
+    raise_lds((const void *)k_bcg_small<D>, lds_small);
     StreamWait wait{stream};
     BcgState<D> S;
     krylov_state(S, {{&S.C, 64}, {&S.E1, 64}, {&S.E2, 64}, {&S.G, 64}}, {&S.bnorm, &S.relres}, rtol, maxit);
     S.deftol = deftol;
-    auto gram = [&](const D *a, const D *b) {  // S.G = a^H b
-      hipLaunchKernelGGL((k_bcg_gram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
-      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
-    };
     auto small = [&](int mode, int k) {
       hipLaunchKernelGGL((k_bcg_small<D>), dim3(1), dim3(256), lds_small, stream, mode, k, nc, S);
     };
@@ -3460,13 +3486,13 @@ class Engine : public EngineBase {
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
     HIP_OK(hipMemsetAsync(P, 0, vec, stream));
     solve_dev((const D *)Q, nc, W, nc, nc, rank, nullptr);  // Z = M^{-1} R
-    gram(Q, W);
+    block_gram(Q, W, nc, pt, S.G);
     small(1, 0);
     qp();  // Q = R E, P = Z E (E2 = 0)
     HIP_OK(hipGetLastError());
     for (int k = 1, go = krylov_active(S); k <= maxit && go > 0; ++k) {
       spmv_dev((const D *)P, nc, Tm, nc, nc, nullptr);  // T = A P
-      gram(P, Tm);
+      block_gram(P, Tm, nc, pt, S.G);
       small(2, k);  // alpha = (P^H T)^{-1}
       hipLaunchKernelGGL((k_bcg_xq<D>), dim3(kBcgBlocks), dim3(256), lds_pass, stream, n, nc, dX, ldx, Q, (const D *)P,
                          (const D *)Tm, (const D *)S.E1, (const D *)S.E2, pt);
@@ -3474,31 +3500,24 @@ class Engine : public EngineBase {
       small(3, k);  // the residual test
       if ((go = krylov_active(S)) == 0) break;
       solve_dev((const D *)Q, nc, W, nc, nc, rank, nullptr);  // W = M^{-1} Q
-      gram(Q, W);
+      block_gram(Q, W, nc, pt, S.G);
       small(4, k);  // the next block: rank, E, S^H, C
       qp();
       HIP_OK(hipGetLastError());
     }
     krylov_result(S, nc, flags, iters);
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+    block_ranks(S, ranks);
   }
-  bool bcg_lds_raised = false;
 
   void bcg_check(int block, double deftol, int maxit, double rtol) {
     krylov_check("block CG", maxit, rtol);
     hermitian_check("block CG", "GMRES", "a null-space filter");
-    if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
-    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < deftol < 1");
+    block_check(block, deftol);
   }
   void bcg_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int block, double rtol, double deftol, int maxit,
                int64_t rank, int *flags, int *iters, int *ranks) {
-    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { bcg_check(block, deftol, maxit, rtol); },
-                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) {
-                   bcg_tile(b, ldb, x, ldx, nc, rtol, deftol, maxit, rank, fl, it, ranks ? ranks + 2 * ((b - dB) / block) : nullptr);
-                 },
-                 block >= 1 && block <= 64 ? block : 64);
+    block_batch(dB, ldb, dX, ldx, nrhs, block, flags, iters, ranks, [&] { bcg_check(block, deftol, maxit, rtol); },
+                [&](const D *b, D *x, int nc, int *fl, int *it, int *rk) { bcg_tile(b, ldb, x, ldx, nc, rtol, deftol, maxit, rank, fl, it, rk); });
   }
   void bcg_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int block, double rtol, double deftol, int maxit,
                 int64_t rank, int *flags, int *iters, int *ranks) {
@@ -3530,11 +3549,8 @@ class Engine : public EngineBase {
     if (kr_vec[2].bytes < blk / 3) kr_vec[2].alloc(blk / 3);  // R is [n][k]
     if (ir_part.bytes < part) ir_part.alloc(part);
     D *Sb = kr_vec[0].as<D>(), *ASb = kr_vec[1].as<D>(), *R = kr_vec[2].as<D>(), *pt = ir_part.as<D>();
-    const size_t lds_small = 2 * mat + 64 * sizeof(D) + 3 * 64 * sizeof(double) + (4 * 64 + 4) * sizeof(int);
-    if (!lob_lds_raised) {  // (68 KB; a complex handle's 133 KB)
-      HIP_OK(hipFuncSetAttribute((const void *)k_lob_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-      lob_lds_raised = true;
-    }
+    const size_t lds_small = lob::RitzScratch<D>::bytes();  // (68 KB; a complex handle's 133 KB)
+    raise_lds((const void *)k_lob_small<D>, lds_small);
     StreamWait wait{stream};
     LobState<D> S;
     krylov_state(S, {{&S.GB, 64}, {&S.GA, 64}, {&S.CC, 64}, {&S.X1, 64}, {&S.X2, 64}, {&S.X3, 64}}, {&S.bnorm, &S.lam, &S.res}, tol,
@@ -3606,7 +3622,6 @@ class Engine : public EngineBase {
     }
     if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
   }
-  bool lob_lds_raised = false;
 
   void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx) {
     if (k < 1 || k > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= k <= 16");
@@ -3667,14 +3682,11 @@ class Engine : public EngineBase {
     if (gm_Z.bytes < vec * (size_t)restart) gm_Z.alloc(vec * (size_t)restart);
     if (ir_part.bytes < part) ir_part.alloc(part);
     D *Rh = kr_vec[0].as<D>(), *Qs = gm_Q.as<D>(), *Ps = gm_Z.as<D>(), *pt = ir_part.as<D>();
-    const size_t lds_pass = 2 * mat, lds_small = 2 * mat + 64 * sizeof(double) + 128 * sizeof(int);
+    const size_t lds_pass = 2 * mat, lds_small = bcg::Work<D>::bytes();
     const size_t lds_proj = (size_t)kBgcrGroup<D> * mat;
-    if (!bgcr_lds_raised) {
-      HIP_OK(hipFuncSetAttribute((const void *)k_bcg_xq<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
-      HIP_OK(hipFuncSetAttribute((const void *)k_bgcr_proj<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_proj));
-      HIP_OK(hipFuncSetAttribute((const void *)k_bgcr_small<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small));
-      bgcr_lds_raised = true;
-    }
+    raise_lds((const void *)k_bcg_xq<D>, lds_pass);
+    raise_lds((const void *)k_bgcr_proj<D>, lds_proj);
+    raise_lds((const void *)k_bgcr_small<D>, lds_small);
     StreamWait wait{stream};
     BgcrState<D> S;
     double *ints = nullptr;  // (a [64] double slot that holds live | aux as integers)
@@ -3683,10 +3695,6 @@ class Engine : public EngineBase {
     S.deftol = deftol;
     S.live = (int *)ints;
     S.aux = S.live + 64;
-    auto gram = [&](const D *a, const D *b) {  // S.G = a^H b
-      hipLaunchKernelGGL((k_bcg_gram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, nc, a, b, pt);
-      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
-    };
     auto small = [&](int mode, int steps, bool flag) {
       hipLaunchKernelGGL((k_bgcr_small<D>), dim3(1), dim3(256), lds_small, stream, mode, steps, flag ? 1 : 0, nc, S);
     };
@@ -3710,7 +3718,7 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_bgcr_rho<D>), dim3(1), dim3(1024), 0, stream, (const D *)pt, nc, cycle, steps, S);
       hipLaunchKernelGGL((k_bcg_norm<D>), dim3(vec_grid(n * nc)), dim3(256), 0, stream, n, nc, Rh, (const double *)S.rho,
                          (const int *)S.live);
-      gram(Rh, Rh);
+      block_gram(Rh, Rh, nc, pt, S.G);
       small(1, steps, cycle == 0);
       rmul(Rh, nullptr);  // Rh = Rn E
       if ((go = state()) != 1) break;
@@ -3730,7 +3738,7 @@ class Engine : public EngineBase {
         hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, nc, S.G);
         small(2, steps, false);  // W^H W -> rank q, E1
         rmul(Qj, Pj);            // Q_j = W E, P_j = Z E
-        gram(Qj, Rh);
+        block_gram(Qj, Rh, nc, pt, S.G);
         small(3, steps, false);  // D -> E1 = D C diag(beta), E2 = D
         hipLaunchKernelGGL((k_bcg_xq<D>), dim3(kBcgBlocks), dim3(256), lds_pass, stream, n, nc, dX, ldx, Rh, (const D *)Pj,
                            (const D *)Qj, (const D *)S.E1, (const D *)S.E2, pt);
@@ -3740,27 +3748,17 @@ class Engine : public EngineBase {
       }
     }
     krylov_result(S, nc, flags, iters);
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+    block_ranks(S, ranks);
   }
-  bool bgcr_lds_raised = false;
 
   void bgcr_check(int block, int restart, double deftol, int maxit, double rtol) {
     krylov_check("block GCR", maxit, rtol);
-    if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
-    if (restart < 1 || restart > HIFAMD_BGCR_MAX_RESTART)
-      throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= restart <= HIFAMD_BGCR_MAX_RESTART");
-    if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "need 0 < deftol < 1");
+    block_check(block, deftol, restart);
   }
   void bgcr_dev(const D *dB, int64_t ldb, D *dX, int64_t ldx, int64_t nrhs, int block, int restart, double rtol, double deftol,
                 int maxit, int64_t rank, int *flags, int *iters, int *ranks) {
-    krylov_batch(dB, ldb, dX, ldx, nrhs, flags, iters, nullptr, [&] { bgcr_check(block, restart, deftol, maxit, rtol); },
-                 [&](const D *b, D *x, int nc, int *fl, int *it, int *) {
-                   bgcr_tile(b, ldb, x, ldx, nc, restart, rtol, deftol, maxit, rank, fl, it,
-                             ranks ? ranks + 2 * ((b - dB) / block) : nullptr);
-                 },
-                 block >= 1 && block <= 64 ? block : 64);
+    block_batch(dB, ldb, dX, ldx, nrhs, block, flags, iters, ranks, [&] { bgcr_check(block, restart, deftol, maxit, rtol); },
+                [&](const D *b, D *x, int nc, int *fl, int *it, int *rk) { bgcr_tile(b, ldb, x, ldx, nc, restart, rtol, deftol, maxit, rank, fl, it, rk); });
   }
   void bgcr_host(const T *B, int64_t ldb, T *X, int64_t ldx, int64_t nrhs, int block, int restart, double rtol, double deftol,
                  int maxit, int64_t rank, int *flags, int *iters, int *ranks) {

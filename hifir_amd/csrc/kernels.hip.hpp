@@ -2249,14 +2249,7 @@ __global__ void __launch_bounds__(256) k_gm_colop(int op, int64_t n, int nc, T *
 // ---------------------------------------------------------------------------------------------
 constexpr int kCgBlocks = 1024;  // blocks of 4 waves of every fused pass (and partials per column)
 
-// what the states of the lock-step solvers (PCG, BiCGSTAB, symmetric QMR) share
-struct KrylovState {
-  double *bnorm;              // [64]  ||b||
-  int *iter, *flag, *active;  // [64]
-  int *ctl;                   // [0] columns still active
-  int maxit;
-  double rtol;
-};
+// (KrylovState, what the lock-step solvers' states share: blockcg_small.hpp, whose host-tested decisions need it HIP-free)
 
 template <class T>
 struct CgState : KrylovState {
@@ -5889,13 +5882,7 @@ __global__ void __launch_bounds__(256) k_block_inverse(const int32_t *__restrict
 constexpr int kBcgBlocks = 256;  // workgroups of 4 waves of every pass (one per compute unit) and partial matrices per Gram
 
 template <class T>
-struct BcgState : KrylovState {
-  // bnorm: beta = ||b|| per column; active: 1 for a column of the block (not zero, not excluded)
-  // ctl: [0] 1 while the tile runs, [1] rank after the start, [2] rank during the last step, [3] current rank
-  T *C, *E1, *E2, *G;  // [64][64] each: R = Q C | the two coefficient matrices of the next row pass | the summed Gram
-  double *relres;      // [64]  ||r|| / ||b|| at the last test (infinite before the first)
-  double deftol;
-};
+using BcgState = bcg::Small<T>;  // (C, E1, E2, G, relres, deftol beside the KrylovState: blockcg_small.hpp)
 
 template <class T>
 struct BcgAcc;
@@ -6142,23 +6129,23 @@ __global__ void __launch_bounds__(256) k_bcg_qp(int64_t n, int nc, T *__restrict
   }
 }
 
-// The start's scalars from the kCgBlocks partials of |b_j|^2 (k_cg_dot): beta_j, and which columns enter the block.  A zero
-// column is done (x = 0, flag 0), a column whose |b|^2 is not finite is excluded (x = 0, flag 1); both 0 iterations.
+struct BcgTeam {
+  __device__ int rank() const { return threadIdx.x; }
+  __device__ int size() const { return blockDim.x; }
+  __device__ void sync() const { __syncthreads(); }
+};
+
+// The start's scalars from the kCgBlocks partials of |b_j|^2 (k_cg_dot): the sums, then bcg::start_columns (beta_j, which
+// columns enter the block, the flags of those that do not).  One workgroup of 1024 threads.
 template <class T>
 __global__ void __launch_bounds__(1024) k_bcg_beta(const T *__restrict__ partial, int nc, BcgState<T> S) {
   __shared__ T sm[16 * 64];
   const T tot = cg_sum_partials(partial, nc, sm);
-  if (threadIdx.x < nc) {
-    const int c = threadIdx.x;
-    const double b2 = vreal(tot);
-    const bool in = b2 != 0.0 && isfinite(b2);
-    S.bnorm[c] = in ? sqrt(b2) : 0.0;
-    S.active[c] = in ? 1 : 0;
-    S.flag[c] = (b2 == 0.0 || in) ? 0 : 1;
-    S.iter[c] = 0;
-    S.relres[c] = __builtin_huge_val();
-  }
-  if (threadIdx.x == 0) S.ctl[0] = 1, S.ctl[1] = S.ctl[2] = 0, S.ctl[3] = nc;
+  double *b2 = (double *)sm;  // (the partials have been read)
+  __syncthreads();
+  if (threadIdx.x < nc) b2[threadIdx.x] = vreal(tot);
+  __syncthreads();
+  bcg::start_columns(S, nc, b2, BcgTeam{});
 }
 
 // R[:, c] = R[:, c] / beta_c for a column of the block, an exact zero otherwise (selected, not multiplied: a NaN stays out)
@@ -6173,90 +6160,18 @@ __global__ void __launch_bounds__(256) k_bcg_norm(int64_t n, int nc, T *__restri
   }
 }
 
-struct BcgTeam {
-  __device__ int rank() const { return threadIdx.x; }
-  __device__ int size() const { return blockDim.x; }
-  __device__ void sync() const { __syncthreads(); }
-};
-
-// One workgroup of 256 threads on the summed Gram S.G of step k (1-based), with blockcg_small.hpp's arithmetic on two
-// 64 x 64 working matrices in LDS:
-//   mode 1: start: G = R^H Z -> pivoted Cholesky S, rank r; E1 = I[:, piv] inv(S[:, piv]), E2 = 0, C = S
-//   mode 2: Sigma = P^H A P -> unpivoted Cholesky, alpha = Sigma^-1; E1 = alpha C diag(beta), E2 = alpha
-//   mode 3: H = Q^H Q -> relres_j = sqrt(c_j^H H c_j); all <= rtol: flag 0, k iterations; k == maxit: flag 0 / 2
-//   mode 4: G = Q^H W -> pivoted Cholesky S, rank r'; E1 = I[:, piv] inv(S[:, piv]), E2 = S^H, C = S C, r = r'
-// A breakdown (the Cholesky's, or r' = 0) ends the tile: every column of the block that was not <= rtol at its last test
-// gets flag 1, all get the completed steps as iterations, and E1 = E2 = 0 so that the step's remaining passes change nothing.
-// A tile that is over (ctl[0] == 0) is left alone.
+// One workgroup of 256 threads on the summed Gram S.G of step k (1-based): blockcg_small.hpp's modes (the arithmetic and every
+// decision; a host program replays them) on two 64 x 64 working matrices in LDS.  1: the start's G = R^H Z, 2: Sigma = P^H A P,
+// 3: H = Q^H Q and the residual test, 4: G = Q^H W and the next block.  A tile that is over (ctl[0] == 0) is left alone.
 template <class T>
 __global__ void __launch_bounds__(256) k_bcg_small(int mode, int k, int s, BcgState<T> S) {
   extern __shared__ double bcg_lds_raw[];
-  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64;
-  double *d = (double *)(W2 + 64 * 64);
-  int *piv = (int *)(d + 64), *taken = piv + 64;
+  const bcg::Work<T> W = bcg::Work<T>::carve(bcg_lds_raw);
   const BcgTeam tm;
-  if (S.ctl[0] == 0) return;
-  const int m = (mode == 1) ? s : S.ctl[3];
-  __syncthreads();  // (everybody has read ctl before thread 0 may change it)
-  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) W1[e] = (e / 64 < m && e % 64 < m) ? S.G[e] : vzero(T());
-  __syncthreads();
-  bcg::hermitize(W1, W2, m, tm);
-  auto clear_coefficients = [&] {
-    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.E1[e] = S.E2[e] = vzero(T());
-    __syncthreads();
-  };
-  auto stop = [&](bool broke, int done) {  // flags and iterations of the block's columns; the tile is over
-    if (threadIdx.x < s && S.active[threadIdx.x]) {
-      const bool conv = S.relres[threadIdx.x] <= S.rtol;
-      S.flag[threadIdx.x] = conv ? 0 : (broke ? 1 : 2);
-      S.iter[threadIdx.x] = done;
-    }
-    if (threadIdx.x == 0) S.ctl[0] = 0;
-  };
-  auto stage = [&](const T *from, T *to) {  // a 64 x 64 matrix of the state into LDS: no inner loop reads HBM
-    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) to[e] = from[e];
-    __syncthreads();
-  };
-  if (mode == 3) {
-    stage(S.C, W2);
-    bcg::quad_forms(W1, W2, m, s, S.G, S.relres, tm);
-    bool all = true;
-    for (int c = 0; c < s; ++c) all = all && (!S.active[c] || S.relres[c] <= S.rtol);
-    if (all || k >= S.maxit) stop(false, k);
-    return;
-  }
-  clear_coefficients();
-  const bcg::Chol f = bcg::chol(W1, m, S.deftol, mode != 2, W2, piv, d, taken, tm);
-  if (f.bad || (mode != 2 && f.r == 0)) {
-    if (mode == 1 && !f.bad) {  // every column zero or excluded: nothing to do
-      if (threadIdx.x == 0) S.ctl[0] = 0;
-    } else {
-      stop(true, mode == 4 ? k : (mode == 2 ? k - 1 : 0));
-    }
-    return;
-  }
-  const int r = f.r;
-  bcg::tri_inv(W2, piv, r, W1, tm);  // W1 = inv(S[:, piv])
-  if (mode == 2) {
-    for (int c = threadIdx.x; c < 64; c += blockDim.x) d[c] = (c < s && S.active[c]) ? S.bnorm[c] : 0.0;
-    bcg::matmul(W1, W1, true, r, r, r, (const double *)nullptr, W2, tm);  // alpha = Ti Ti^H
-    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.E2[e] = (e / 64 < r && e % 64 < r) ? W2[e] : vzero(T());
-    stage(S.C, W1);
-    bcg::matmul(W2, W1, false, r, r, s, d, S.E1, tm);
-    if (threadIdx.x == 0) S.ctl[2] = r;
-    return;
-  }
-  bcg::select_rows(W1, piv, r, m, r, S.E1, tm);
-  if (mode == 1) {
-    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.C[e] = (e / 64 < r && e % 64 < s) ? W2[e] : vzero(T());
-    if (threadIdx.x == 0) S.ctl[1] = S.ctl[2] = S.ctl[3] = r;
-    return;
-  }
-  bcg::adjoint(W2, r, m, S.E2, tm);
-  stage(S.C, W1);
-  bcg::matmul(W2, W1, false, r, m, s, (const double *)nullptr, S.G, tm);  // S C
-  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) S.C[e] = (e / 64 < r && e % 64 < s) ? S.G[e] : vzero(T());
-  if (threadIdx.x == 0) S.ctl[3] = r;
+  if (mode == 1) bcg::start_factor(S, W, s, tm);
+  if (mode == 2) bcg::step_alpha(S, W, s, k, tm);
+  if (mode == 3) bcg::step_test(S, W, s, k, tm);
+  if (mode == 4) bcg::step_next(S, W, s, k, tm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -6271,16 +6186,8 @@ __global__ void __launch_bounds__(256) k_bcg_small(int mode, int k, int s, BcgSt
 // A complex handle runs the same kernels on its real planes, as block CG does.  Sums run in a fixed order, no atomics.
 // ---------------------------------------------------------------------------------------------
 template <class T>
-struct BgcrState : BcgState<T> {
-  // ctl: [0] 0 the tile is over / 1 inside a cycle / 2 the cycle has ended, [1] rank after the first cycle's start,
-  // [2] rank during the last step, [3] current rank; relres: the recurrence's rel_j
-  T *Cs;                     // [restart][64][64]  the coefficient matrices C_i of a step
-  double *rho, *tres, *mu;   // [64]  ||r|| and ||r|| / ||b|| at the cycle's start; mu[0]: the last cycle's largest tres
-  int *live, *aux;           // [64]  block columns with a nonzero residual; aux[0]: rank of the step's direction block
-  __host__ __device__ bgcr::Small<T> small() const {
-    return bgcr::Small<T>{this->C, this->E1, this->E2, this->G, this->bnorm, rho, tres, this->relres, mu, this->iter,
-                          this->flag, this->active, live, this->ctl, aux, this->rtol, this->deftol, this->maxit};
-  }
+struct BgcrState : bgcr::Small<T> {  // (rho, tres, mu, live, aux beside block CG's state: blockgcr_small.hpp)
+  T *Cs;  // [restart][64][64]  the coefficient matrices C_i of a step
 };
 
 __device__ __forceinline__ void bcg_put(BcgAcc<double> &c, int reg, double v) { c.re[reg] = v; }
@@ -6469,7 +6376,7 @@ __global__ void __launch_bounds__(1024) k_bgcr_rho(const T *__restrict__ partial
   __syncthreads();
   if (threadIdx.x < nc) S.rho[threadIdx.x] = vreal(tot);
   __syncthreads();
-  bgcr::cycle_start(S.small(), nc, cycle, steps, BcgTeam{});
+  bgcr::cycle_start(S, nc, cycle, steps, BcgTeam{});
 }
 
 // One workgroup of 256 threads on the summed Gram S.G, with blockgcr_small.hpp's modes on two 64 x 64 working matrices in LDS:
@@ -6481,16 +6388,12 @@ __global__ void __launch_bounds__(1024) k_bgcr_rho(const T *__restrict__ partial
 template <class T>
 __global__ void __launch_bounds__(256) k_bgcr_small(int mode, int steps, int flag, int s, BgcrState<T> S) {
   extern __shared__ double bcg_lds_raw[];
-  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64;
-  double *d = (double *)(W2 + 64 * 64);
-  int *piv = (int *)(d + 64), *taken = piv + 64;
-  const bgcr::Work<T> W{W1, W2, d, piv, taken};
-  const bgcr::Small<T> Sm = S.small();
+  const bcg::Work<T> W = bcg::Work<T>::carve(bcg_lds_raw);
   const BcgTeam tm;
-  if (mode == 1) bgcr::cycle_factor(Sm, W, s, flag != 0, steps, tm);
-  if (mode == 2) bgcr::step_basis(Sm, W, s, steps, tm);
-  if (mode == 3) bgcr::step_coeff(Sm, W, s, tm);
-  if (mode == 4) bgcr::step_test(Sm, W, s, steps, flag != 0, tm);
+  if (mode == 1) bgcr::cycle_factor(S, W, s, flag != 0, steps, tm);
+  if (mode == 2) bgcr::step_basis(S, W, s, steps, tm);
+  if (mode == 3) bgcr::step_coeff(S, W, s, tm);
+  if (mode == 4) bgcr::step_test(S, W, s, steps, flag != 0, tm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -6698,10 +6601,7 @@ __global__ void __launch_bounds__(256) k_lob_lock(int64_t n, int k, T *__restric
 template <class T>
 __global__ void __launch_bounds__(256) k_lob_small(int mode, int step, const double *__restrict__ partial, LobState<T> S) {
   extern __shared__ double bcg_lds_raw[];
-  T *W1 = (T *)bcg_lds_raw, *W2 = W1 + 64 * 64, *js = W2 + 64 * 64;
-  double *d = (double *)(js + 64), *dsc = d + 64, *jc = dsc + 64;
-  int *piv = (int *)(jc + 64), *taken = piv + 64, *perm = taken + 64, *mate = perm + 64, *count = mate + 64;
-  const lob::RitzScratch<T> W{W1, W2, S.X1, S.X2, S.X3, d, dsc, piv, taken, perm, lob::JacobiScratch<T>{mate, jc, js, count}};
+  const lob::RitzScratch<T> W = lob::RitzScratch<T>::carve(bcg_lds_raw, S.X1, S.X2, S.X3);
   const lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev};
   const BcgTeam tm;
   if (mode == 0) lob::start_factor(Sm, W, tm);

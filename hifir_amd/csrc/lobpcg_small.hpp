@@ -3,7 +3,7 @@
 // orthonormalizes the basis and drops its dependent columns, the reduced matrix, its Hermitian eigendecomposition by a cyclic
 // Jacobi method, and the coefficient matrices [C Cp] of the row pass.  Plain C++17, no HIP include: the one-workgroup kernel
 // and host programs built with g++ (tests/cpp/lobpcg_small_test.cpp) run the same code.  The Cholesky, the triangular
-// inverse and the products are blockcg_small.hpp's, and so are the conventions: row-major matrices of row stride kLd = 64,
+// inverse, the products and the shared constructions (bcg::stage, clear, factor_staged) are blockcg_small.hpp's, and so are the conventions: row-major matrices of row stride kLd = 64,
 // functions called by every thread of a Team, every output element computed by one thread with its sums in a fixed order (the
 // team's size does not change a bit), a barrier at the end of every function.
 #pragma once
@@ -69,12 +69,6 @@ HIFAMD_HD inline void matmul_ah(const T *A, const T *B, int a, int b, int c, T *
     for (int l = 0; l < a; ++l) acc = bcg::add(acc, bcg::mul(bcg::cj(A[l * kLd + i]), B[l * kLd + j]));
     Out[i * kLd + j] = acc;
   }
-  tm.sync();
-}
-
-template <class T, class Team>
-HIFAMD_HD inline void copy(const T *A, int a, int b, T *Out, const Team &tm) {
-  for (int e = tm.rank(); e < a * b; e += tm.size()) Out[(e / b) * kLd + e % b] = A[(e / b) * kLd + e % b];
   tm.sync();
 }
 
@@ -199,13 +193,22 @@ struct Ritz {
   bcg::Chol f;  // what the Cholesky left (chol == true)
 };
 
-// what rayleigh_ritz() works in: W1, W2 are the hot matrices (LDS on the device), X1 .. X3 may be slow (HBM); all [64][64]
+// what rayleigh_ritz() works in: W1, W2 are the hot matrices (LDS on the device), X1 .. X3 may be slow (HBM); all [64][64].  All
+// but X1 .. X3 is carved from the kernel's dynamic LDS of bytes() bytes: W1 | W2 | jac.s | d | dsc | jac.c | piv | taken | perm | mate | count
 template <class T>
 struct RitzScratch {
   T *W1, *W2, *X1, *X2, *X3;
   double *d, *dsc;  // [64] each
   int *piv, *taken, *perm;  // [64] each
   JacobiScratch<T> jac;
+  HIFAMD_HD bcg::Work<T> work() const { return bcg::Work<T>{W1, W2, d, piv, taken}; }  // (what block CG's constructions take)
+  static constexpr size_t bytes() { return bcg::Work<T>::bytes() + kLd * sizeof(T) + 2 * kLd * sizeof(double) + (2 * kLd + 4) * sizeof(int); }
+  HIFAMD_HD static RitzScratch carve(void *base, T *X1, T *X2, T *X3) {
+    T *W1 = (T *)base, *W2 = W1 + kLd * kLd, *js = W2 + kLd * kLd;
+    double *d = (double *)(js + kLd), *dsc = d + kLd, *jc = dsc + kLd;
+    int *piv = (int *)(jc + kLd), *taken = piv + kLd, *perm = taken + kLd, *mate = perm + kLd;
+    return RitzScratch{W1, W2, X1, X2, X3, d, dsc, piv, taken, perm, JacobiScratch<T>{mate, jc, js, mate + kLd}};
+  }
 };
 
 // One Rayleigh-Ritz step on a basis S of s columns with the summed Grams GB = S^H S and GA = S^H A S (upper triangles):
@@ -221,21 +224,19 @@ HIFAMD_HD inline Ritz rayleigh_ritz(const T *GB, const T *GA, int s, int k, doub
   Ritz out{s, 0, false, bcg::Chol{0, false, 0.0, 0.0, 0.0}};
   T *W1 = w.W1, *W2 = w.W2;
   if (chol) {
-    copy(GB, s, s, W1, tm);
+    bcg::stage(GB, W1, s, s, tm);
     hermitize_upper(W1, s, tm);
     if (any_nonfinite(W1, s, w.jac.count, tm)) {
       out.bad = true;
       return out;
     }
     scale_unit_diagonal(W1, s, w.dsc, tm);
-    out.f = bcg::chol(W1, s, deftol, true, W2, w.piv, w.d, w.taken, tm);
+    out.f = bcg::factor_staged(w.work(), s, deftol, W2, tm);  // (W2: the factor, then I[:, piv] inv(T[:, piv]))
     out.r = out.f.r;
     if (out.f.bad || out.r < k) {
       out.bad = true;
       return out;
     }
-    bcg::tri_inv(W2, w.piv, out.r, W1, tm);
-    bcg::select_rows(W1, w.piv, out.r, s, out.r, W2, tm);
     for (int e = tm.rank(); e < s * out.r; e += tm.size()) {
       T &v = W2[(e / out.r) * kLd + e % out.r];
       v = bcg::scale(w.dsc[e / out.r], v);
@@ -245,12 +246,12 @@ HIFAMD_HD inline Ritz rayleigh_ritz(const T *GB, const T *GA, int s, int k, doub
     identity(W2, s, tm);
   }
   const int r = out.r;
-  copy(W2, s, r, w.X1, tm);  // E
-  copy(GA, s, s, W1, tm);
+  bcg::stage((const T *)W2, w.X1, s, r, tm);  // E
+  bcg::stage(GA, W1, s, s, tm);
   hermitize_upper(W1, s, tm);
   bcg::matmul(W1, W2, false, s, s, r, (const double *)nullptr, w.X2, tm);  // GA E
   matmul_ah(W2, w.X2, s, r, r, w.X3, tm);                                   // E^H GA E
-  copy(w.X3, r, r, W1, tm);
+  bcg::stage((const T *)w.X3, W1, r, r, tm);
   bcg::hermitize(W1, w.X3, r, tm);
   if (any_nonfinite(W1, r, w.jac.count, tm)) {
     out.bad = true;
@@ -304,19 +305,14 @@ HIFAMD_HD inline void start_factor(const Small<T> &S, const RitzScratch<T> &w, c
   for (int t = tm.rank(); t < kLd; t += tm.size())
     S.flag[t] = 0, S.iter[t] = 0, S.active[t] = t < k ? 1 : 0, S.res[t] = HUGE_VAL, S.lam[t] = 0.0;
   if (tm.rank() == 0) S.ctl[0] = 1, S.ctl[1] = k, S.ctl[2] = 0, S.ctl[3] = kStartFine;
-  for (int e = tm.rank(); e < kLd * kLd; e += tm.size()) bcg::set(S.CC[e], 0.0);
-  copy((const T *)S.GB, k, k, w.W1, tm);
+  bcg::clear(S.CC, tm);
+  bcg::stage((const T *)S.GB, w.W1, k, k, tm);
   hermitize_upper(w.W1, k, tm);
   const bool inf = any_nonfinite(w.W1, k, w.jac.count, tm);
   bcg::Chol f{0, false, 0.0, 0.0, 0.0};
-  if (!inf) f = bcg::chol(w.W1, k, S.deftol, true, w.W2, w.piv, w.d, w.taken, tm);
-  if (inf || f.bad || f.r < k) {
-    if (tm.rank() == 0) S.ctl[0] = 0, S.ctl[3] = inf ? kStartNotFinite : kStartRankDeficient;
-    tm.sync();
-    return;
-  }
-  bcg::tri_inv(w.W2, w.piv, k, w.W1, tm);
-  bcg::select_rows(w.W1, w.piv, k, k, k, S.CC, tm);
+  if (!inf) f = bcg::factor_staged(w.work(), k, S.deftol, S.CC, tm);  // (the Gram arrives as an upper triangle: no factor_basis)
+  if ((inf || f.bad || f.r < k) && tm.rank() == 0) S.ctl[0] = 0, S.ctl[3] = inf ? kStartNotFinite : kStartRankDeficient;
+  tm.sync();
 }
 
 // The residual test after `step` completed steps on nb partials of |r_j|^2 (partial[b][16], summed in block order):

@@ -51,10 +51,10 @@ static int run_case(const std::string &name, int s, double rtol, double deftol, 
   for (int c = 0; c < s; ++c)
     if (std::fscanf(f, "%d", &active[c]) != 1) return 1;
   ctl[0] = 1, ctl[3] = s;  // (what k_bcg_beta leaves)
-  const bgcr::Small<T> S{C.data(), E1.data(), E2.data(), G.data(), bnorm.data(), rho.data(), tres.data(), relres.data(),
-                         mu.data(), iter.data(), flag.data(), active.data(), live.data(), ctl.data(), aux.data(), rtol,
-                         deftol, maxit};
-  const bgcr::Work<T> W{W1.data(), W2.data(), d.data(), piv.data(), taken.data()};
+  const bgcr::Small<T> S{{{bnorm.data(), iter.data(), flag.data(), active.data(), ctl.data(), maxit, rtol},
+                          C.data(), E1.data(), E2.data(), G.data(), relres.data(), deftol},
+                         rho.data(), tres.data(), mu.data(), live.data(), aux.data()};
+  const bcg::Work<T> W{W1.data(), W2.data(), d.data(), piv.data(), taken.data()};
   const bcg::Serial tm;
   for (int op = 0; op < nops; ++op) {
     int kind, a, b;

@@ -27,6 +27,9 @@ namespace lob = hifamd::lob;
 struct Z {
   double x, y;
 };
+// (the dynamic LDS of k_lob_small, real and complex: two matrices, jac.s, d | dsc | jac.c, piv | taken | perm | mate, count)
+static_assert(lob::RitzScratch<double>::bytes() == 2 * 32768 + 512 + 3 * 512 + 4 * 256 + 16, "k_lob_small's LDS, real");
+static_assert(lob::RitzScratch<Z>::bytes() == 2 * 65536 + 1024 + 3 * 512 + 4 * 256 + 16, "k_lob_small's LDS, complex");
 static void put(double a) { std::printf(" %.17g 0", a); }
 static void put(const Z &a) { std::printf(" %.17g %.17g", a.x, a.y); }
 static void make(double &a, double re, double) { a = re; }
