@@ -79,6 +79,10 @@ SIGNATURES = {
     "hifamd_bgcr_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _dbl, _dbl, _int, _i64, _vp, _vp, _vp]),
     "hifamd_lobpcg": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "hifamd_lobpcg_dev": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hifamd_set_mass_matrix": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "hifamd_lobpcg_gen": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "hifamd_lobpcg_gen_dev": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp,
+                                     _vp]),
     "hifamd_bicgstab_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_bicgstab_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_idrs_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, C.c_uint64, _dbl, _int, _i64, _vp, _vp]),

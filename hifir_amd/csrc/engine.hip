@@ -459,6 +459,8 @@ class Engine : public EngineBase {
   DevDense dn;
   DevCsr A;
   bool has_A = false;
+  DevCsr Bm;  // the mass matrix of the generalized eigenproblem (set_mass_matrix)
+  bool has_B = false;
   std::map<GraphKey, GraphEntry> graphs;
   static constexpr size_t kIoRing = 1024;  // pinned staging of the (B, X) pointers handed to the graphs
   void **io_ring = nullptr;
@@ -1395,7 +1397,8 @@ class Engine : public EngineBase {
     }
   }
 
-  void set_matrix(int64_t n, const int64_t *indptr, const int32_t *indices, const T *vals) {
+  // the checks of hifamd_set_matrix / hifamd_set_mass_matrix on a user's CRS arrays (0- or 1-based), and its 0-based copy
+  Csr<T> crs_from_user(int64_t n, const int64_t *indptr, const int32_t *indices, const T *vals) const {
     if (!indptr || !indices || !vals) throw Error(HIFAMD_NULL_OBJ, "NULL CRS array");
     if (!host.levels.empty() && n != host.levels[0].n)
       throw Error(HIFAMD_MISMATCHED_SIZES, "matrix size differs from the preconditioner size");
@@ -1415,23 +1418,42 @@ class Engine : public EngineBase {
     }
     C.val.assign(vals, vals + nz);
     if (!finalized) throw Error(HIFAMD_BAD_PREC, "attach the matrix after hifamd_finalize");
+    return C;
+  }
+  void set_matrix(int64_t n, const int64_t *indptr, const int32_t *indices, const T *vals) {
+    const Csr<T> C = crs_from_user(n, indptr, indices, vals);
     if (adj) adj->upload_matrix(adjoint_of_csr(C));
     host.A = C;  // kept for the adjoint engine (built on first use)
     host.has_A = true;
     upload_matrix(C);
   }
+  // B of the generalized eigenproblem A x = lambda B x (lobpcg_gen_tile): a second CRS matrix of THIS engine only -- the adjoint
+  // engine does not get it, hifamd_save does not write it, and like A it is not checked for being Hermitian or definite
+  void set_mass_matrix(int64_t n, const int64_t *indptr, const int32_t *indices, const T *vals) {
+    const Csr<T> C = crs_from_user(n, indptr, indices, vals);
+    HIP_OK(hipSetDevice(device));
+    Bm.upload(C, nullptr);
+    HIP_OK(hipStreamSynchronize(stream));
+    B_norm_inf = crs_norm_inf(C);
+    has_B = true;
+  }
 
+  static double crs_norm_inf(const Csr<T> &C) {  // largest row sum of |c_ij|; a NaN row sum wins
+    double nrm = 0.0;
+    for (int64_t i = 0; i < C.nrows; ++i) {
+      double s = 0.0;
+      for (int32_t k = C.ptr[(size_t)i]; k < C.ptr[(size_t)i + 1]; ++k) s += abs_(C.val[(size_t)k]);
+      if (s > nrm || s != s) nrm = s;
+    }
+    return nrm;
+  }
   double A_norm_inf = 0.0;  // largest row sum of |a_ij| of THIS engine's matrix (the adjoint engine: of A^H), for nsp_find
+  double B_norm_inf = 0.0;  // the same of the mass matrix
   void upload_matrix(const Csr<T> &C) {
     HIP_OK(hipSetDevice(device));
     A.upload(C, nullptr);
     HIP_OK(hipStreamSynchronize(stream));  // (transfers were synchronous on the transfer stream)
-    A_norm_inf = 0.0;
-    for (int64_t i = 0; i < C.nrows; ++i) {
-      double s = 0.0;
-      for (int32_t k = C.ptr[(size_t)i]; k < C.ptr[(size_t)i + 1]; ++k) s += abs_(C.val[(size_t)k]);
-      if (s > A_norm_inf || s != s) A_norm_inf = s;
-    }
+    A_norm_inf = crs_norm_inf(C);
     has_A = true;
   }
 
@@ -2772,12 +2794,22 @@ class Engine : public EngineBase {
     if (!has_A) throw Error(HIFAMD_BAD_PREC, "no matrix attached (hifamd_set_matrix)");
     if (!dX || !dY) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
     HIP_OK(hipSetDevice(device));
-    hipStream_t st = user ? user : stream;
+    spmm_launch(A, dX, ldx, dY, ldy, nrhs, user ? user : stream);
+  }
+  // Y = B X with the mass matrix (set_mass_matrix), as spmv_dev runs it on A
+  void spmv_mass_dev(const D *dX, int64_t ldx, D *dY, int64_t ldy, int64_t nrhs, hipStream_t user) {
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (!has_B) throw Error(HIFAMD_BAD_PREC, "no mass matrix attached (hifamd_set_mass_matrix)");
+    if (!dX || !dY) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    spmm_launch(Bm, dX, ldx, dY, ldy, nrhs, user ? user : stream);
+  }
+  void spmm_launch(const DevCsr &C, const D *dX, int64_t ldx, D *dY, int64_t ldy, int64_t nrhs, hipStream_t st) {
     for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
       const int nc = (int)std::min<int64_t>(64, nrhs - c0);
       const int logR = pick_logR(nc);
-      hipLaunchKernelGGL((k_crs_spmm<D, false>), dim3(grid_for(A.nrows, logR)), dim3(256), 0, st, A.nrows,
-                         A.ptr.as<int32_t>(), A.col.as<int32_t>(), A.val.as<D>(), dX + c0, ldx, (const D *)nullptr,
+      hipLaunchKernelGGL((k_crs_spmm<D, false>), dim3(grid_for(C.nrows, logR)), dim3(256), 0, st, C.nrows,
+                         C.ptr.as<int32_t>(), C.col.as<int32_t>(), C.val.as<D>(), dX + c0, ldx, (const D *)nullptr,
                          (int64_t)0, dY + c0, ldy, nc, logR);
     }
     HIP_OK(hipGetLastError());
@@ -3623,7 +3655,9 @@ class Engine : public EngineBase {
     if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
   }
 
-  void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx) {
+  // gen: the generalized driver's checks (lobpcg_gen_*): the mass matrix directly after the matrix, no filter of any kind
+  void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx,
+                    bool gen = false) {
     if (k < 1 || k > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= k <= 16");
     if (nev < 1 || nev > k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= nev <= k");
     if (!(tol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need tol > 0");
@@ -3634,7 +3668,13 @@ class Engine : public EngineBase {
     if (k > std::max<int64_t>(Rmax, max_nrhs))
       throw Error(HIFAMD_MISMATCHED_SIZES, "block wider than the max_nrhs given to hifamd_finalize");
     if (!has_A) throw Error(HIFAMD_BAD_PREC, "LOBPCG needs the matrix (hifamd_set_matrix)");
-    hermitian_check("LOBPCG", "hifamd_nsp_find for null vectors", "a constant-mode null-space filter");
+    if (!gen) return hermitian_check("LOBPCG", "hifamd_nsp_find for null vectors", "a constant-mode null-space filter");
+    if (!has_B) throw Error(HIFAMD_BAD_PREC, "generalized LOBPCG needs the mass matrix (hifamd_set_mass_matrix)");
+    static const char *const filter =
+      "a null-space filter: the Euclidean projector I - Q Q^H solves the pencil (A, P B P), not (A, B), and the B-orthogonal "
+      "projector I - Q (Q^H B Q)^{-1} Q^H B is not implemented";
+    hermitian_check("generalized LOBPCG", "hifamd_nsp_find for null vectors", filter);
+    if (nsp_k > 0) throw Error(HIFAMD_BAD_PREC, std::string("generalized LOBPCG does not support ") + filter + " (hifamd_set_nsp_basis)");
   }
   void lobpcg_dev(int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
                   int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info3) {
@@ -3656,6 +3696,133 @@ class Engine : public EngineBase {
     if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
     lobpcg_tile(X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, (int)k, (int)nev, tol, deftol, maxit, rank, stage_x.as<D>(), k,
                 lambda, res, flags, info3);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
+  // ---- generalized LOBPCG: the nev smallest eigenpairs of A x = lambda B x, B the mass matrix of set_mass_matrix ---------
+  // The iteration above with a third block BS = [BX BW BP] beside S and AS, and B-orthonormal Ritz vectors:
+  //   start: X = X0 (or generated, as above), BX = B X; G = X^H BX = S^H S (pivoted Cholesky; rank < k or not finite: refused),
+  //          X, BX <- . E; AX = A X; X^H AX = V Theta V^H, X, AX, BX <- . V, lambda = Theta, P = AP = BP = 0;
+  //   loop:  R = AX - BX diag(lambda), res_j = ||r_j|| / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||) (the normwise backward error
+  //          of the pair: X is B-normalized, so ||x_j|| is in the scale), conv_j = res_j <= tol; all j < nev converged or
+  //          steps == maxit: end.  W = M^{-1} R (converged columns exact zeros), AW = A W, BW = B W; GB = S^H BS, GA = S^H AS;
+  //          lob::ritz_step as it is -> [C Cp], lambda; X, P <- S [C Cp], AX, AP <- AS [C Cp], BX, BP <- BS [C Cp].
+  // Per step over lobpcg_tile: one more SpMM on k columns; k_lob_gram3, k_lob_update3, k_lob_resid_gen and k_lob_test_gen in the
+  // places of k_lob_gram2, k_lob_update, k_lob_resid and k_lob_small's mode 2; kr_vec[3] = BS.  With B = I given explicitly BS
+  // is a bitwise copy of S and every iterate is the standard driver's, bit for bit, until the two stopping tests differ.
+  // Outputs, flags and info3 as lobpcg_tile; X^H B X = I.
+  void lobpcg_gen_tile(const D *dX0, int64_t ldx0, uint64_t seed, int k, int nev, double tol, double deftol, int maxit,
+                       int64_t rank, D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3) {
+    const int64_t n = lv[0]->n;
+    const int s = 3 * k;
+    const size_t blk = (size_t)n * s * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
+    const size_t part = std::max(2 * (size_t)kBcgBlocks * mat, (size_t)kLobResBlocks * 32 * sizeof(double));
+    krylov_vectors(2, blk);
+    if (kr_vec[2].bytes < blk / 3) kr_vec[2].alloc(blk / 3);  // R is [n][k]
+    if (kr_vec[3].bytes < blk) kr_vec[3].alloc(blk);
+    if (ir_part.bytes < part) ir_part.alloc(part);
+    D *Sb = kr_vec[0].as<D>(), *ASb = kr_vec[1].as<D>(), *R = kr_vec[2].as<D>(), *BSb = kr_vec[3].as<D>(), *pt = ir_part.as<D>();
+    const size_t lds_small = lob::RitzScratch<D>::bytes();
+    raise_lds((const void *)k_lob_small<D>, lds_small);
+    StreamWait wait{stream};
+    LobState<D> S;
+    krylov_state(S, {{&S.GB, 64}, {&S.GA, 64}, {&S.CC, 64}, {&S.X1, 64}, {&S.X2, 64}, {&S.X3, 64}}, {&S.bnorm, &S.lam, &S.res}, tol,
+                 maxit);
+    S.deftol = deftol, S.anorm = A_norm_inf, S.k = k, S.nev = nev;
+    auto gram = [&] {  // S.GB = S^H BS, S.GA = S^H AS
+      hipLaunchKernelGGL((k_lob_gram3<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, (const D *)Sb,
+                         (const D *)BSb, (const D *)ASb, pt);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, s, S.GB);
+      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)(pt + (size_t)kBcgBlocks * 64 * 64), kBcgBlocks,
+                         s, S.GA);
+    };
+    auto small = [&](int mode, int step) {
+      hipLaunchKernelGGL((k_lob_small<D>), dim3(1), dim3(256), lds_small, stream, mode, step, (const double *)pt, S);
+    };
+    auto update = [&] {
+      hipLaunchKernelGGL((k_lob_update3<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, k, Sb, ASb, BSb, (const D *)S.CC);
+    };
+    auto refused = [&] {  // the start's verdict
+      HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+      check_device_error();
+      if (kr_pin[3] == 1)
+        throw Error(HIFAMD_BAD_PREC, "generalized LOBPCG: X^H B X of the start block has Cholesky rank below k: the start block is rank "
+                                     "deficient, or B is not positive definite");
+      if (kr_pin[3] == 2)
+        throw Error(HIFAMD_BAD_PREC, "generalized LOBPCG: X^H B X of the start block is not finite (the start block or B is not finite)");
+      if (kr_pin[3] == 3)
+        throw Error(HIFAMD_BAD_PREC,
+                    "generalized LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end");
+    };
+    HIP_OK(hipMemsetAsync(Sb, 0, blk, stream));
+    HIP_OK(hipMemsetAsync(ASb, 0, blk, stream));
+    HIP_OK(hipMemsetAsync(BSb, 0, blk, stream));
+    if (dX0) {
+      vec_op(1, n, k, Sb, s, dX0, ldx0, nullptr, 0);
+    } else {
+      hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, k, seed, R);
+      vec_op(1, n, k, Sb, s, (const D *)R, k, nullptr, 0);
+    }
+    spmm_launch(Bm, (const D *)Sb, s, BSb, s, k, stream);  // BX = B X
+    gram();
+    small(0, 0);
+    refused();
+    update();  // X, BX <- . E
+    spmv_dev((const D *)Sb, s, ASb, s, k, nullptr);  // AX = A X
+    gram();
+    small(1, 0);
+    refused();
+    update();  // X, AX, BX <- . V, P = AP = BP = 0
+    HIP_OK(hipGetLastError());
+    for (int step = 0;; ++step) {
+      hipLaunchKernelGGL((k_lob_resid_gen<D>), dim3(kLobResBlocks), dim3(256), 0, stream, n, s, k, (const D *)Sb, (const D *)ASb,
+                         (const D *)BSb, (const double *)S.lam, R, (double *)pt);
+      hipLaunchKernelGGL((k_lob_test_gen<D>), dim3(1), dim3(256), 0, stream, step, (const double *)pt, S, B_norm_inf);
+      if (krylov_active(S) == 0) break;
+      hipLaunchKernelGGL((k_lob_lock<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, R, (const int *)S.active);
+      solve_dev((const D *)R, k, Sb + k, s, k, rank, nullptr);  // W = M^{-1} R
+      spmv_dev((const D *)(Sb + k), s, ASb + k, s, k, nullptr);  // AW = A W
+      spmm_launch(Bm, (const D *)(Sb + k), s, BSb + k, s, k, stream);  // BW = B W
+      gram();
+      small(3, step);
+      update();
+      HIP_OK(hipGetLastError());
+    }
+    vec_op(1, n, k, dX, ldx, (const D *)Sb, s, nullptr, 0);
+    int its[64];
+    krylov_result(S, k, flags, its);
+    std::vector<double> out(128);
+    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(out.data(), S.lam, 128 * sizeof(double), hipMemcpyDeviceToHost, stream));  // lam | res
+    HIP_OK(hipStreamSynchronize(stream));
+    for (int c = 0; c < k; ++c) {
+      if (lambda) lambda[c] = out[(size_t)c];
+      if (res) res[c] = out[64 + (size_t)c];
+    }
+    if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
+  }
+  void lobpcg_gen_dev(int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+                      int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info3) {
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, dX0 != nullptr, ldx, true);
+    if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    lobpcg_gen_tile(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
+  }
+  void lobpcg_gen_host(int64_t k, int64_t nev, const T *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+                       int64_t rank, double *lambda, T *X, int64_t ldx, double *res, int *flags, int *info3) {
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, X0 != nullptr, ldx, true);
+    if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t need = (size_t)n * k * sizeof(T);
+    if (stage_b.bytes < need) stage_b.alloc(need);
+    if (stage_x.bytes < need) stage_x.alloc(need);
+    StreamWait wait{stream};
+    if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    lobpcg_gen_tile(X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, (int)k, (int)nev, tol, deftol, maxit, rank, stage_x.as<D>(),
+                    k, lambda, res, flags, info3);
     HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
   }
@@ -4904,6 +5071,32 @@ HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *
   API_BEGIN
   visit(h, [&](auto &E) {
     E.lobpcg_dev(k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_set_mass_matrix(HifAmdHdl h, int64_t n, const int64_t *indptr, const int32_t *indices, const void *vals) {
+  API_BEGIN
+  visit(h, [&](auto &E) { E.set_mass_matrix(n, indptr, indices, E.val(vals)); });
+  API_END
+}
+
+HifAmdStatus hifamd_lobpcg_gen(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, int64_t ldx0, uint64_t seed, double tol,
+                               double deftol, int maxit, int64_t rank, double *lambda, void *X, int64_t ldx, double *res,
+                               int *flags, int *info3) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.lobpcg_gen_host(k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_lobpcg_gen_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
+                                   double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
+                                   int *flags, int *info3) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.lobpcg_gen_dev(k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
   });
   API_END
 }

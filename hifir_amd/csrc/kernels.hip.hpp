@@ -39,6 +39,8 @@
 //                    stacked Gram, the fused block Gram-Schmidt pass, in-place right-multiplication, decisions (blockgcr_small.hpp)
 //   k_lob_gram2 / k_lob_update / k_lob_resid / k_lob_lock / k_lob_small   device-resident LOBPCG: both Grams of the basis
 //                    [X W P] in one pass, the row-local update, the Rayleigh-Ritz step in one workgroup (lobpcg_small.hpp)
+//   k_lob_gram3 / k_lob_update3 / k_lob_resid_gen / k_lob_test_gen   their siblings for the generalized problem A x = lambda B x:
+//                    a third block [BX BW BP], the Grams S^H BS and S^H AS, the backward-error stopping test
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -6607,6 +6609,185 @@ __global__ void __launch_bounds__(256) k_lob_small(int mode, int step, const dou
   if (mode == 0) lob::start_factor(Sm, W, tm);
   if (mode == 1 || mode == 3) lob::ritz_step(Sm, W, mode == 1, step, tm);
   if (mode == 2) lob::residual_test(Sm, partial, kLobResBlocks, step, tm);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The generalized problem A x = lambda B x (Engine::lobpcg_gen_tile): a third [n][ld] block BS = [BX BW BP] beside S and AS.
+// Siblings of the kernels above, with their lane maps, row ownership and orders of summation, so that an explicit identity
+// B (BS a bitwise copy of S) reproduces the standard driver's iterates bit for bit:
+//   k_lob_gram3       partials of GB = S^H BS and GA = S^H AS: the conjugated strip of S is the left operand of both
+//   k_lob_update3     X, P / AX, AP / BX, BP <- S, AS, BS [C Cp] in one launch
+//   k_lob_resid_gen   R = AX - BX diag(lambda) and the partials of |r_j|^2 and |x_j|^2
+//   k_lob_test_gen    one workgroup: lob::residual_test_gen
+// k_lob_lock, k_lob_small (modes 0, 1, 3: they see GB = S^H BS) and k_bcg_sum are reused as they are.
+// ---------------------------------------------------------------------------------------------
+// partial[0][blockIdx.x] and partial[1][blockIdx.x] ([64][64] each) = the block's share of S^H BS and S^H AS, tiles (ti <= tj)
+// only; row groups (two in flight per wave), K steps, wave-order sum and output as k_lob_gram2.
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_gram3(int64_t n, int ld, int s, const T *__restrict__ S, const T *__restrict__ BS,
+                                                   const T *__restrict__ AS, T *__restrict__ partial /* [2][gridDim.x][64][64] */) {
+  __shared__ T lds[12 * 4 * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (s + 15) >> 4;
+  BcgAcc<T> acc[2][6];  // tile (ti, tj), ti <= tj < 3, at index 3 ti + tj - ti (ti + 1) / 2
+#pragma unroll
+  for (int w = 0; w < 2; ++w)
+#pragma unroll
+    for (int t = 0; t < 6; ++t) bcg_clear(acc[w][t]);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t g = (int64_t)blockIdx.x * 4 + wave; 4 * g < n; g += 2 * stride) {
+    T a[2][3], b[2][3], c[2][3];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        a[u][t] = vconj(lob_load(S, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci));
+        b[u][t] = lob_load(BS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+        c[u][t] = lob_load(AS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+        for (int tj = ti; tj < 3; ++tj)
+          if (tj < nt) {
+            bcg_mma(acc[0][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], b[u][tj]);
+            bcg_mma(acc[1][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], c[u][tj]);
+          }
+  }
+  // the four waves of the block in wave order
+  for (int w = 1; w < 4; ++w) {
+    __syncthreads();
+    if (wave == w) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) lds[((m * 6 + t) * 4 + reg) * 64 + lane] = bcg_get(acc[m][t], reg);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const T v = lds[((m * 6 + t) * 4 + reg) * 64 + lane];
+            if constexpr (std::is_same<T, cplx>::value)
+              acc[m][t].re[reg] += v.x, acc[m][t].im[reg] += v.y;
+            else
+              acc[m][t].re[reg] += v;
+          }
+    }
+  }
+  if (wave != 0) return;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    T *__restrict__ out = partial + ((int64_t)m * gridDim.x + blockIdx.x) * 64 * 64;
+#pragma unroll
+    for (int ti = 0; ti < 3; ++ti)
+#pragma unroll
+      for (int tj = ti; tj < 3; ++tj)
+        if (tj < nt) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg)
+            out[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[m][3 * ti + tj - ti * (ti + 1) / 2], reg);
+        }
+  }
+}
+
+// X <- S C, P <- S Cp, and the same for AS (AX, AP) and BS (BX, BP), in place: CC, its staging, the strips and the lane map as
+// k_lob_update.  A wave reads its strip of all three blocks completely, as operands, before it writes any of it.
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_update3(int64_t n, int ld, int s, int k, T *__restrict__ S, T *__restrict__ AS,
+                                                     T *__restrict__ BS, const T *__restrict__ CC) {
+  __shared__ T cc[48 * 32];
+  for (int e = threadIdx.x; e < 48 * 32; e += blockDim.x) cc[e] = CC[(e >> 5) * 64 + (e & 31)];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (s + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    T x[12], ax[12], bx[12];
+#pragma unroll
+    for (int kk = 0; kk < 12; ++kk) {
+      x[kk] = ax[kk] = bx[kk] = vzero(T());
+      if (kk < 4 * nt) {
+        x[kk] = lob_load((const T *)S, n, ld, s, r0 + ci, 4 * kk + kq);
+        ax[kk] = lob_load((const T *)AS, n, ld, s, r0 + ci, 4 * kk + kq);
+        bx[kk] = lob_load((const T *)BS, n, ld, s, r0 + ci, 4 * kk + kq);
+      }
+    }
+    BcgAcc<T> as[2], aa[2], ab[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) bcg_clear(as[t]), bcg_clear(aa[t]), bcg_clear(ab[t]);
+#pragma unroll
+    for (int kk = 0; kk < 12; ++kk)
+      if (kk < 4 * nt) {
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) {
+          const T b = cc[(4 * kk + kq) * 32 + 16 * tj + ci];
+          bcg_mma(as[tj], x[kk], b);
+          bcg_mma(aa[tj], ax[kk], b);
+          bcg_mma(ab[tj], bx[kk], b);
+        }
+      }
+#pragma unroll
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t row = r0 + kq + 4 * reg;
+        if (row < n && ci < k) {
+          S[row * ld + 2 * k * tj + ci] = bcg_get(as[tj], reg);
+          AS[row * ld + 2 * k * tj + ci] = bcg_get(aa[tj], reg);
+          BS[row * ld + 2 * k * tj + ci] = bcg_get(ab[tj], reg);
+        }
+      }
+  }
+}
+
+// R = AX - BX diag(lambda) ([n][k]; X, AX and BX are the first k columns of their [n][ld] blocks) and the block's share of
+// |r_j|^2 and |x_j|^2: rows, columns and the order of the sums as k_lob_resid: partial[blockIdx.x][32], |r_j|^2 at j and
+// |x_j|^2 at 16 + j
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_resid_gen(int64_t n, int ld, int k, const T *__restrict__ S, const T *__restrict__ AS,
+                                                       const T *__restrict__ BS, const double *__restrict__ lam, T *__restrict__ R,
+                                                       double *__restrict__ partial /* [gridDim.x][32] */) {
+  __shared__ double sm[512];
+  const int c = threadIdx.x & 15, sub = threadIdx.x >> 4;
+  double acc = 0.0, accx = 0.0;
+  if (c < k) {
+    const double l = lam[c];
+    for (int64_t i = (int64_t)blockIdx.x * 16 + sub; i < n; i += (int64_t)gridDim.x * 16) {
+      const T r = vsub(AS[i * ld + c], vscale(l, BS[i * ld + c]));
+      R[i * k + c] = r;
+      acc += vabs2(r);
+      accx += vabs2(S[i * ld + c]);
+    }
+  }
+  sm[threadIdx.x] = acc;
+  sm[256 + threadIdx.x] = accx;
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    const int j = threadIdx.x & 15, base = threadIdx.x < 16 ? 0 : 256;
+    double tot = sm[base + j];
+    for (int u = 1; u < 16; ++u) tot += sm[base + 16 * u + j];
+    partial[blockIdx.x * 32 + threadIdx.x] = tot;
+  }
+}
+
+// One workgroup: lob::residual_test_gen on the kLobResBlocks partials of |r_j|^2 and |x_j|^2 (k_lob_small's mode 2 for the
+// generalized problem; modes 0, 1 and 3 are k_lob_small's own)
+template <class T>
+__global__ void __launch_bounds__(256) k_lob_test_gen(int step, const double *__restrict__ partial, LobState<T> S, double bnorm) {
+  lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev};
+  Sm.bnorm = bnorm;
+  const BcgTeam tm;
+  lob::residual_test_gen(Sm, partial, kLobResBlocks, step, tm);
 }
 
 }  // namespace hifamd

@@ -176,6 +176,14 @@ class HIF:
         _check(lib().hifamd_set_matrix(self._h, len(ip) - 1, _p(ip), _p(ix), _p(v)))
         self._A = True
 
+    def set_mass_matrix(self, indptr, indices, vals):
+        """Attach the CRS mass matrix B of the generalized eigenproblem A x = lambda B x (hifamd_set_mass_matrix; lobpcg_gen).
+        Arguments and checks of set_matrix; B is not checked for being Hermitian or positive definite."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        v = np.ascontiguousarray(vals, dtype=self.dtype)
+        _check(lib().hifamd_set_mass_matrix(self._h, len(ip) - 1, _p(ip), _p(ix), _p(v)))
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             lib().hifamd_destroy(self._h)
@@ -689,6 +697,17 @@ class HIF:
         (lam, X, res, flags, steps): lam [k] ascending, X [n][k] orthonormal (a CUDA tensor where X0 is one), res [k] the last
         residuals, flags [k] 0 converged / 1 breakdown / 2 not converged at maxit, steps (one apply plus one SpMM each);
         last_lobpcg_info keeps the call's info3 (steps, rank of the last basis, largest Jacobi sweep count)."""
+        return self._lobpcg("hifamd_lobpcg", k, nev, X0, seed, tol, maxit, deftol, full_rank)
+
+    def lobpcg_gen(self, k=8, nev=None, X0=None, seed=0, tol=1e-8, maxit=200, deftol=1e-12, full_rank=False):
+        """LOBPCG for the nev smallest eigenpairs of the Hermitian definite pencil A x = lambda B x, A of set_matrix and B of
+        set_mass_matrix, preconditioned by the hierarchy (hifamd_lobpcg_gen / _dev).  Arguments and returns of lobpcg; X comes
+        back with X^H B X = I, and a column is converged when ||A x - lambda B x||_2 <= tol (||A||_inf + |lambda| ||B||_inf)
+        ||x||_2, the normwise backward error of the pair.  Needs set_matrix, set_mass_matrix and is_hermitian(), and runs
+        under no null-space filter (neither set_nsp_const nor set_nsp_basis: the projector would have to be B-orthogonal)."""
+        return self._lobpcg("hifamd_lobpcg_gen", k, nev, X0, seed, tol, maxit, deftol, full_rank)
+
+    def _lobpcg(self, entry, k, nev, X0, seed, tol, maxit, deftol, full_rank):
         dev = X0 is not None and _is_torch(X0)
         if X0 is not None:
             if dev:
@@ -711,7 +730,7 @@ class HIF:
         nev = int(k) if nev is None else int(nev)
         lam, res = np.zeros(max(int(k), 1)), np.zeros(max(int(k), 1))
         fl, info = np.zeros(max(int(k), 1), dtype=np.int32), np.zeros(3, dtype=np.int32)
-        fn = lib().hifamd_lobpcg_dev if dev else lib().hifamd_lobpcg
+        fn = getattr(lib(), entry + "_dev" if dev else entry)
         _check(fn(self._h, int(k), nev, *io0, int(seed), float(tol), float(deftol), int(maxit), -1 if full_rank else 0, _p(lam),
                   *io1, _p(res), _p(fl), _p(info)))
         self.last_lobpcg_info = info

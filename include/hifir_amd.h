@@ -488,8 +488,8 @@ HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void
  * A step is one batched M^{-1} apply plus one SpMM on k columns, one pass for both Grams and one row-local
  * [n][48] x [48][32] product on the f64 matrix cores, and the small matrices in one workgroup; the host reads back one
  * integer per step.  Sums run in a fixed order: the same inputs give the same bits.  The eigenvectors come back
- * orthonormal; their phase (sign) is not fixed.  Smallest eigenvalues of A only: no largest or interior ones, no
- * generalized problem.  The pair has to be definite for the iteration to converge; on an indefinite pair it runs to maxit
+ * orthonormal; their phase (sign) is not fixed.  Smallest eigenvalues of A only: no largest or interior ones; the
+ * generalized problem A x = lambda B x is hifamd_lobpcg_gen's.  The pair has to be definite for the iteration to converge; on an indefinite pair it runs to maxit
  * (flag 2), which is not refused.
  * Refusals, in this order: a NULL handle (HIFAMD_NULL_OBJ); k outside [1, 16], nev outside [1, k], tol <= 0, maxit < 1,
  * deftol outside (0, 1), a row stride below k (HIFAMD_MISMATCHED_SIZES); a handle that is not finalized (HIFAMD_BAD_PREC;
@@ -509,6 +509,40 @@ HifAmdStatus hifamd_lobpcg(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, 
 HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
                                double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
                                int *flags, int *info3);
+
+/* ---- generalized LOBPCG: the smallest eigenpairs of A x = lambda B x ---------------------------- */
+/* The mass matrix B in CRS (copied to HBM as a second matrix of the handle): arguments, index bases, checks and refusal
+ * codes of hifamd_set_matrix.  It serves hifamd_lobpcg_gen only: it is not given to the adjoint engine, hifamd_save does not
+ * write it, and like A it is NOT checked for being Hermitian or positive definite -- a B that is not shows as a refused start
+ * block or as a breakdown.  ||B||_inf is the largest row sum of |b_ij|. */
+HifAmdStatus hifamd_set_mass_matrix(HifAmdHdl h, int64_t n, const int64_t *indptr, const int32_t *indices,
+                                    const void *vals);
+/* hifamd_lobpcg for the nev smallest eigenvalues of the Hermitian definite pencil (A, B), B Hermitian positive definite: the
+ * iteration, its arguments and its outputs with a third block BS = [BX BW BP] carried beside S and AS = [AX AW AP]:
+ *   start: X as hifamd_lobpcg generates or takes it; BX = B X; G = X^H BX = S^H S (pivoted Cholesky stopped at deftol);
+ *     X, BX <- . I[:, piv] inv(S[:, piv]); AX = A X; X^H AX = V Theta V^H, X, AX, BX <- . V, lambda = Theta, P = AP = BP = 0
+ *   loop: R = AX - BX diag(lambda); res_j = ||r_j||_2 / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||_2), the normwise
+ *     backward error of the pair (lambda_j, x_j) -- the vectors are B-normalized, so ||x_j||_2 is not 1 and belongs in the
+ *     scale, and the test does not depend on how B is scaled; conv_j = res_j <= tol; every j < nev converged, or
+ *     steps == maxit: end.  W = M^{-1} R (exact zeros in converged columns); AW = A W; BW = B W; steps += 1; GB = S^H BS,
+ *     GA = S^H AS; the Rayleigh-Ritz step of hifamd_lobpcg on (GB, GA) unchanged; X, P <- S [C Cp], AX, AP <- AS [C Cp],
+ *     BX, BP <- BS [C Cp]
+ * A step costs one more SpMM on k columns than hifamd_lobpcg's, and its row passes read and move a third block.  The
+ * orders of summation are hifamd_lobpcg's: with an explicit identity as B the iterates are that driver's, bit for bit,
+ * until the two stopping tests decide differently.  Out: lambda ascending, X with X^H B X = I, res, flags, info3 as
+ * hifamd_lobpcg.  Not done here: a null-space basis under B, largest or interior eigenvalues, k > 16.
+ * Refusals in hifamd_lobpcg's order, with: no mass matrix (hifamd_set_mass_matrix; HIFAMD_BAD_PREC) directly after no
+ * matrix; after the Hermitian check ANY null-space filter on HIFAMD_S, the constant-mode one and a basis filter alike
+ * (HIFAMD_BAD_PREC): the Euclidean projector I - Q Q^H would solve the pencil (A, P B P), and the B-orthogonal projector
+ * I - Q (Q^H B Q)^{-1} Q^H B is not implemented; a start block whose X^H B X is not finite, or has a Cholesky rank below k
+ * -- a rank-deficient block, or a B that is not positive definite: the message names both -- or whose X^H A X is not
+ * finite (HIFAMD_BAD_PREC). */
+HifAmdStatus hifamd_lobpcg_gen(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, int64_t ldx0, uint64_t seed, double tol,
+                               double deftol, int maxit, int64_t rank, double *lambda, void *X, int64_t ldx, double *res,
+                               int *flags, int *info3);
+HifAmdStatus hifamd_lobpcg_gen_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
+                                   double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
+                                   int *flags, int *info3);
 
 /* ---- restarted block GCR for a general pair (A, M): a shared block space without conditions ---- */
 /* Restarted block GCR with x0 = 0: in exact arithmetic block GMRES(restart) with right preconditioning, flexible by

@@ -61,11 +61,11 @@ class HIF {
   typedef ValueType value_type;
   typedef std::size_t size_type;
 
-  explicit HIF(int device = -1) : _h(nullptr), _device(device), _has_A(false), _zop(0) {}
+  explicit HIF(int device = -1) : _h(nullptr), _device(device), _has_A(false), _has_B(false), _zop(0) {}
   ~HIF() { clear(); }
   HIF(const HIF &) = delete;
   HIF &operator=(const HIF &) = delete;
-  HIF(HIF &&o) noexcept : _h(o._h), _device(o._device), _has_A(o._has_A), _zop(o._zop) { o._h = nullptr; }
+  HIF(HIF &&o) noexcept : _h(o._h), _device(o._device), _has_A(o._has_A), _has_B(o._has_B), _zop(o._zop) { o._h = nullptr; }
 
   /// Complex hierarchies: the explicit operators the next attach() asks for (HIFAMD_ZOP_TAIL | HIFAMD_ZOP_TOP,
   /// hifamd_set_complex_operators; 0, the default, keeps the plan complex handles always had).  They are planner options,
@@ -142,7 +142,7 @@ class HIF {
   void clear() {
     if (_h) hifamd_destroy(_h);
     _h = nullptr;
-    _has_A = false;
+    _has_A = _has_B = false;
   }
   HifAmdHdl handle() const { return _h; }  ///< for the device-pointer entry points of hifir_amd.h
   /// HIF::nsp / nsp_tran with NspFilter::set_nsp_const (NspFilter.hpp:118-125); start > end removes it
@@ -366,6 +366,39 @@ class HIF {
     return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
   }
 
+  // ---- generalized LOBPCG: the nev smallest eigenpairs of A x = lambda B x (hifamd_lobpcg_gen) ----
+  // B: the mass matrix (copied to HBM beside A by set_mass_matrix; lobpcg_gen sends it once per facade object).
+  void set_mass_matrix(const size_type n, const std::int64_t *indptr, const std::int32_t *indices, const value_type *vals) {
+    require();
+    detail::check(hifamd_set_mass_matrix(_h, (std::int64_t)n, indptr, indices, vals));
+    _has_B = true;
+  }
+  template <class Crs>
+  void set_mass_matrix(const Crs &B) {
+    const std::vector<std::int64_t> ip(B.row_start().cbegin(), B.row_start().cend());
+    const std::vector<std::int32_t> ci(B.col_ind().cbegin(), B.col_ind().cend());
+    set_mass_matrix(B.nrows(), ip.data(), ci.data(), B.vals().data());
+  }
+  // Arguments and returns of lobpcg; X comes back with X^H B X = I and res_j = ||A x_j - lambda_j B x_j|| /
+  // ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||).  No null-space filter may be in force.
+  template <class Matrix, class ArrayType>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, int> lobpcg_gen(
+      const Matrix &A, const Matrix &B, const int k, const int nev, const ArrayType &X0, const double tol, const int maxit,
+      const std::uint64_t seed = 0, const double deftol = 1e-12, const bool full_rank = false) {
+    ensure_matrix(A);
+    if (!_has_B) set_mass_matrix(B);
+    if (k < 1) throw std::runtime_error("hifir_amd: lobpcg_gen needs k >= 1");
+    if (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k)
+      throw std::runtime_error("hifir_amd: lobpcg_gen needs an empty X0 or one of nrows() * k entries");
+    ArrayType X((std::size_t)nrows() * k);
+    std::vector<double> lambda(k, 0.0), res(k, 0.0);
+    std::vector<int> flags(k, 0);
+    int info3[3] = {0, 0, 0};
+    detail::check(hifamd_lobpcg_gen(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit,
+                                    full_rank ? -1 : 0, lambda.data(), X.data(), k, res.data(), flags.data(), info3));
+    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+  }
+
   // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
   // Needs an is_symm hierarchy: is_hermitian(); neither A nor M has to be definite.  iters counts iterations (one apply
   // plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
@@ -418,7 +451,7 @@ class HIF {
 
   HifAmdHdl _h;
   int _device;
-  bool _has_A;
+  bool _has_A, _has_B;
   int _zop;  // set_complex_operators: applied by attach()
 };
 
