@@ -1427,7 +1427,7 @@ class Engine : public EngineBase {
     host.has_A = true;
     upload_matrix(C);
   }
-  // B of the generalized eigenproblem A x = lambda B x (lobpcg_gen_tile): a second CRS matrix of THIS engine only -- the adjoint
+  // B of the generalized eigenproblem A x = lambda B x (lobpcg_tile<true>): a second CRS matrix of THIS engine only -- the adjoint
   // engine does not get it, hifamd_save does not write it, and like A it is not checked for being Hermitian or definite
   void set_mass_matrix(int64_t n, const int64_t *indptr, const int32_t *indices, const T *vals) {
     const Csr<T> C = crs_from_user(n, indptr, indices, vals);
@@ -3566,30 +3566,48 @@ class Engine : public EngineBase {
   //          S = [X W P]; D = diag(GB)^(-1/2), D GB D = T^H T (pivoted, stopped at deftol, rank r; r < k: breakdown),
   //          E = D I[:, piv] inv(T[:, piv]); E^H GA E = V Theta V^H ascending; C = E V[:, :k], lambda = Theta[:k], Cp = C with its
   //          first k rows zero; X, P <- S [C Cp], AX, AP <- AS [C Cp].
-  // Per step one batched apply, one SpMM, one Gram pass (k_lob_gram2), one row-local pass (k_lob_update), the residual pass
+  // Per step one batched apply, one SpMM, one Gram pass (k_lob_gram), one row-local pass (k_lob_update), the residual pass
   // (k_lob_resid, k_lob_lock), two one-workgroup kernels (k_lob_small) and ONE read-back, after the test.  The vectors are
   // kr_vec[0..2] = S [n][3 k], AS [n][3 k], R [n][k]; the small matrices live beside the KrylovState (LobState).  flags
   // 0 converged / 1 breakdown / 2 not converged at maxit, per column by its own last res_j.  info3: steps, rank of the basis
   // in the last step, largest Jacobi sweep count.
+  // GEN: the generalized problem A x = lambda B x, B the mass matrix of set_mass_matrix.  The same iteration and the same
+  // kernels with a third block BS = [BX BW BP] = B S in kr_vec[3] (one more SpMM on k columns at the start and per step; the
+  // row pass carries it along), GB = S^H BS in the places of S^H S, so that the Ritz vectors are B-orthonormal, X^H B X = I;
+  // R = AX - BX diag(lambda) and res_j = ||r_j|| / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||), the normwise backward error
+  // of the pair (X is B-normalized, so ||x_j|| is in the scale).  No filter of any kind (lobpcg_check).  With B = I given
+  // explicitly BS is a bitwise copy of S and every iterate is the standard problem's, bit for bit, until the two stopping
+  // tests differ.
+  template <bool GEN>
   void lobpcg_tile(const D *dX0, int64_t ldx0, uint64_t seed, int k, int nev, double tol, double deftol, int maxit, int64_t rank,
                    D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3) {
+    static const char *const refusal[2][3] = {
+      {"LOBPCG: the start block is rank deficient", "LOBPCG: the start block is not finite",
+       "LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end"},
+      {"generalized LOBPCG: X^H B X of the start block has Cholesky rank below k: the start block is rank deficient, or B is not "
+       "positive definite",
+       "generalized LOBPCG: X^H B X of the start block is not finite (the start block or B is not finite)",
+       "generalized LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end"}};
     const int64_t n = lv[0]->n;
     const int s = 3 * k;
     const size_t blk = (size_t)n * s * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
-    const size_t part = std::max(2 * (size_t)kBcgBlocks * mat, (size_t)kLobResBlocks * 16 * sizeof(double));
+    const size_t part = std::max(2 * (size_t)kBcgBlocks * mat, (size_t)kLobResBlocks * (GEN ? 32 : 16) * sizeof(double));
     krylov_vectors(2, blk);
     if (kr_vec[2].bytes < blk / 3) kr_vec[2].alloc(blk / 3);  // R is [n][k]
+    if (GEN && kr_vec[3].bytes < blk) kr_vec[3].alloc(blk);
     if (ir_part.bytes < part) ir_part.alloc(part);
     D *Sb = kr_vec[0].as<D>(), *ASb = kr_vec[1].as<D>(), *R = kr_vec[2].as<D>(), *pt = ir_part.as<D>();
+    D *BSb = GEN ? kr_vec[3].as<D>() : nullptr;  // (the standard problem's kernels never read it)
     const size_t lds_small = lob::RitzScratch<D>::bytes();  // (68 KB; a complex handle's 133 KB)
     raise_lds((const void *)k_lob_small<D>, lds_small);
     StreamWait wait{stream};
     LobState<D> S;
     krylov_state(S, {{&S.GB, 64}, {&S.GA, 64}, {&S.CC, 64}, {&S.X1, 64}, {&S.X2, 64}, {&S.X3, 64}}, {&S.bnorm, &S.lam, &S.res}, tol,
                  maxit);
-    S.deftol = deftol, S.anorm = A_norm_inf, S.k = k, S.nev = nev;
-    auto gram = [&] {  // S.GB = S^H S, S.GA = S^H AS
-      hipLaunchKernelGGL((k_lob_gram2<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, (const D *)Sb, (const D *)ASb, pt);
+    S.deftol = deftol, S.anorm = A_norm_inf, S.b_inf = GEN ? B_norm_inf : 0.0, S.k = k, S.nev = nev, S.gen = GEN;
+    auto gram = [&] {  // S.GB = S^H S (GEN: S^H BS), S.GA = S^H AS
+      hipLaunchKernelGGL((k_lob_gram<D, GEN>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, (const D *)Sb, (const D *)BSb,
+                         (const D *)ASb, pt);
       hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, s, S.GB);
       hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)(pt + (size_t)kBcgBlocks * 64 * 64), kBcgBlocks,
                          s, S.GA);
@@ -3598,44 +3616,45 @@ class Engine : public EngineBase {
       hipLaunchKernelGGL((k_lob_small<D>), dim3(1), dim3(256), lds_small, stream, mode, step, (const double *)pt, S);
     };
     auto update = [&] {
-      hipLaunchKernelGGL((k_lob_update<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, k, Sb, ASb, (const D *)S.CC);
+      hipLaunchKernelGGL((k_lob_update<D, GEN ? 3 : 2>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, k, Sb, ASb, BSb,
+                         (const D *)S.CC);
     };
     auto refused = [&] {  // the start's verdict
       HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
       HIP_OK(hipStreamSynchronize(stream));
       check_device_error();
-      if (kr_pin[3] == 1) throw Error(HIFAMD_BAD_PREC, "LOBPCG: the start block is rank deficient");
-      if (kr_pin[3] == 2) throw Error(HIFAMD_BAD_PREC, "LOBPCG: the start block is not finite");
-      if (kr_pin[3] == 3)
-        throw Error(HIFAMD_BAD_PREC, "LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end");
+      if (kr_pin[3] >= 1 && kr_pin[3] <= 3) throw Error(HIFAMD_BAD_PREC, refusal[GEN][kr_pin[3] - 1]);
     };
     HIP_OK(hipMemsetAsync(Sb, 0, blk, stream));
     HIP_OK(hipMemsetAsync(ASb, 0, blk, stream));
+    if (GEN) HIP_OK(hipMemsetAsync(BSb, 0, blk, stream));
     if (dX0) {
       vec_op(1, n, k, Sb, s, dX0, ldx0, nullptr, 0);
     } else {
       hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, k, seed, R);
       vec_op(1, n, k, Sb, s, (const D *)R, k, nullptr, 0);
     }
-    if (nsp_k > 0) apply_nsp(Sb, s, k, stream);  // on the complement of span(Q)
+    if (!GEN && nsp_k > 0) apply_nsp(Sb, s, k, stream);  // on the complement of span(Q)
+    if (GEN) spmm_launch(Bm, (const D *)Sb, s, BSb, s, k, stream);  // BX = B X
     gram();
     small(0, 0);
     refused();
-    update();  // X <- X E
+    update();  // X <- X E (GEN: and BX)
     spmv_dev((const D *)Sb, s, ASb, s, k, nullptr);  // AX = A X
     gram();
     small(1, 0);
     refused();
-    update();  // X <- X V, AX <- AX V, P = AP = 0
+    update();  // X <- X V, AX <- AX V, P = AP = 0 (GEN: and BX, BP)
     HIP_OK(hipGetLastError());
     for (int step = 0;; ++step) {
-      hipLaunchKernelGGL((k_lob_resid<D>), dim3(kLobResBlocks), dim3(256), 0, stream, n, s, k, (const D *)Sb, (const D *)ASb,
-                         (const double *)S.lam, R, (double *)pt);
+      hipLaunchKernelGGL((k_lob_resid<D, GEN>), dim3(kLobResBlocks), dim3(256), 0, stream, n, s, k, (const D *)Sb, (const D *)ASb,
+                         (const D *)BSb, (const double *)S.lam, R, (double *)pt);
       small(2, step);
       if (krylov_active(S) == 0) break;
       hipLaunchKernelGGL((k_lob_lock<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, R, (const int *)S.active);
       solve_dev((const D *)R, k, Sb + k, s, k, rank, nullptr);  // W = M^{-1} R
       spmv_dev((const D *)(Sb + k), s, ASb + k, s, k, nullptr);  // AW = A W
+      if (GEN) spmm_launch(Bm, (const D *)(Sb + k), s, BSb + k, s, k, stream);  // BW = B W
       gram();
       small(3, step);
       update();
@@ -3655,9 +3674,8 @@ class Engine : public EngineBase {
     if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
   }
 
-  // gen: the generalized driver's checks (lobpcg_gen_*): the mass matrix directly after the matrix, no filter of any kind
-  void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx,
-                    bool gen = false) {
+  // gen: the generalized problem's checks: the mass matrix directly after the matrix, no filter of any kind
+  void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx, bool gen) {
     if (k < 1 || k > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= k <= 16");
     if (nev < 1 || nev > k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= nev <= k");
     if (!(tol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need tol > 0");
@@ -3676,16 +3694,19 @@ class Engine : public EngineBase {
     hermitian_check("generalized LOBPCG", "hifamd_nsp_find for null vectors", filter);
     if (nsp_k > 0) throw Error(HIFAMD_BAD_PREC, std::string("generalized LOBPCG does not support ") + filter + " (hifamd_set_nsp_basis)");
   }
-  void lobpcg_dev(int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+  void lobpcg_dev(bool gen, int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
                   int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info3) {
-    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, dX0 != nullptr, ldx);
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, dX0 != nullptr, ldx, gen);
     if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
     HIP_OK(hipSetDevice(device));
-    lobpcg_tile(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
+    if (gen)
+      lobpcg_tile<true>(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
+    else
+      lobpcg_tile<false>(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
   }
-  void lobpcg_host(int64_t k, int64_t nev, const T *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
+  void lobpcg_host(bool gen, int64_t k, int64_t nev, const T *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
                    int64_t rank, double *lambda, T *X, int64_t ldx, double *res, int *flags, int *info3) {
-    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, X0 != nullptr, ldx);
+    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, X0 != nullptr, ldx, gen);
     if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
     HIP_OK(hipSetDevice(device));
     const int64_t n = lv[0]->n;
@@ -3694,135 +3715,8 @@ class Engine : public EngineBase {
     if (stage_x.bytes < need) stage_x.alloc(need);
     StreamWait wait{stream};
     if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
-    lobpcg_tile(X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, (int)k, (int)nev, tol, deftol, maxit, rank, stage_x.as<D>(), k,
-                lambda, res, flags, info3);
-    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-  }
-
-  // ---- generalized LOBPCG: the nev smallest eigenpairs of A x = lambda B x, B the mass matrix of set_mass_matrix ---------
-  // The iteration above with a third block BS = [BX BW BP] beside S and AS, and B-orthonormal Ritz vectors:
-  //   start: X = X0 (or generated, as above), BX = B X; G = X^H BX = S^H S (pivoted Cholesky; rank < k or not finite: refused),
-  //          X, BX <- . E; AX = A X; X^H AX = V Theta V^H, X, AX, BX <- . V, lambda = Theta, P = AP = BP = 0;
-  //   loop:  R = AX - BX diag(lambda), res_j = ||r_j|| / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||) (the normwise backward error
-  //          of the pair: X is B-normalized, so ||x_j|| is in the scale), conv_j = res_j <= tol; all j < nev converged or
-  //          steps == maxit: end.  W = M^{-1} R (converged columns exact zeros), AW = A W, BW = B W; GB = S^H BS, GA = S^H AS;
-  //          lob::ritz_step as it is -> [C Cp], lambda; X, P <- S [C Cp], AX, AP <- AS [C Cp], BX, BP <- BS [C Cp].
-  // Per step over lobpcg_tile: one more SpMM on k columns; k_lob_gram3, k_lob_update3, k_lob_resid_gen and k_lob_test_gen in the
-  // places of k_lob_gram2, k_lob_update, k_lob_resid and k_lob_small's mode 2; kr_vec[3] = BS.  With B = I given explicitly BS
-  // is a bitwise copy of S and every iterate is the standard driver's, bit for bit, until the two stopping tests differ.
-  // Outputs, flags and info3 as lobpcg_tile; X^H B X = I.
-  void lobpcg_gen_tile(const D *dX0, int64_t ldx0, uint64_t seed, int k, int nev, double tol, double deftol, int maxit,
-                       int64_t rank, D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3) {
-    const int64_t n = lv[0]->n;
-    const int s = 3 * k;
-    const size_t blk = (size_t)n * s * sizeof(D), mat = (size_t)64 * 64 * sizeof(D);
-    const size_t part = std::max(2 * (size_t)kBcgBlocks * mat, (size_t)kLobResBlocks * 32 * sizeof(double));
-    krylov_vectors(2, blk);
-    if (kr_vec[2].bytes < blk / 3) kr_vec[2].alloc(blk / 3);  // R is [n][k]
-    if (kr_vec[3].bytes < blk) kr_vec[3].alloc(blk);
-    if (ir_part.bytes < part) ir_part.alloc(part);
-    D *Sb = kr_vec[0].as<D>(), *ASb = kr_vec[1].as<D>(), *R = kr_vec[2].as<D>(), *BSb = kr_vec[3].as<D>(), *pt = ir_part.as<D>();
-    const size_t lds_small = lob::RitzScratch<D>::bytes();
-    raise_lds((const void *)k_lob_small<D>, lds_small);
-    StreamWait wait{stream};
-    LobState<D> S;
-    krylov_state(S, {{&S.GB, 64}, {&S.GA, 64}, {&S.CC, 64}, {&S.X1, 64}, {&S.X2, 64}, {&S.X3, 64}}, {&S.bnorm, &S.lam, &S.res}, tol,
-                 maxit);
-    S.deftol = deftol, S.anorm = A_norm_inf, S.k = k, S.nev = nev;
-    auto gram = [&] {  // S.GB = S^H BS, S.GA = S^H AS
-      hipLaunchKernelGGL((k_lob_gram3<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, (const D *)Sb,
-                         (const D *)BSb, (const D *)ASb, pt);
-      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, s, S.GB);
-      hipLaunchKernelGGL((k_bcg_sum<D>), dim3(16), dim3(256), 0, stream, (const D *)(pt + (size_t)kBcgBlocks * 64 * 64), kBcgBlocks,
-                         s, S.GA);
-    };
-    auto small = [&](int mode, int step) {
-      hipLaunchKernelGGL((k_lob_small<D>), dim3(1), dim3(256), lds_small, stream, mode, step, (const double *)pt, S);
-    };
-    auto update = [&] {
-      hipLaunchKernelGGL((k_lob_update3<D>), dim3(kBcgBlocks), dim3(256), 0, stream, n, s, s, k, Sb, ASb, BSb, (const D *)S.CC);
-    };
-    auto refused = [&] {  // the start's verdict
-      HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
-      check_device_error();
-      if (kr_pin[3] == 1)
-        throw Error(HIFAMD_BAD_PREC, "generalized LOBPCG: X^H B X of the start block has Cholesky rank below k: the start block is rank "
-                                     "deficient, or B is not positive definite");
-      if (kr_pin[3] == 2)
-        throw Error(HIFAMD_BAD_PREC, "generalized LOBPCG: X^H B X of the start block is not finite (the start block or B is not finite)");
-      if (kr_pin[3] == 3)
-        throw Error(HIFAMD_BAD_PREC,
-                    "generalized LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end");
-    };
-    HIP_OK(hipMemsetAsync(Sb, 0, blk, stream));
-    HIP_OK(hipMemsetAsync(ASb, 0, blk, stream));
-    HIP_OK(hipMemsetAsync(BSb, 0, blk, stream));
-    if (dX0) {
-      vec_op(1, n, k, Sb, s, dX0, ldx0, nullptr, 0);
-    } else {
-      hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, k, seed, R);
-      vec_op(1, n, k, Sb, s, (const D *)R, k, nullptr, 0);
-    }
-    spmm_launch(Bm, (const D *)Sb, s, BSb, s, k, stream);  // BX = B X
-    gram();
-    small(0, 0);
-    refused();
-    update();  // X, BX <- . E
-    spmv_dev((const D *)Sb, s, ASb, s, k, nullptr);  // AX = A X
-    gram();
-    small(1, 0);
-    refused();
-    update();  // X, AX, BX <- . V, P = AP = BP = 0
-    HIP_OK(hipGetLastError());
-    for (int step = 0;; ++step) {
-      hipLaunchKernelGGL((k_lob_resid_gen<D>), dim3(kLobResBlocks), dim3(256), 0, stream, n, s, k, (const D *)Sb, (const D *)ASb,
-                         (const D *)BSb, (const double *)S.lam, R, (double *)pt);
-      hipLaunchKernelGGL((k_lob_test_gen<D>), dim3(1), dim3(256), 0, stream, step, (const double *)pt, S, B_norm_inf);
-      if (krylov_active(S) == 0) break;
-      hipLaunchKernelGGL((k_lob_lock<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, R, (const int *)S.active);
-      solve_dev((const D *)R, k, Sb + k, s, k, rank, nullptr);  // W = M^{-1} R
-      spmv_dev((const D *)(Sb + k), s, ASb + k, s, k, nullptr);  // AW = A W
-      spmm_launch(Bm, (const D *)(Sb + k), s, BSb + k, s, k, stream);  // BW = B W
-      gram();
-      small(3, step);
-      update();
-      HIP_OK(hipGetLastError());
-    }
-    vec_op(1, n, k, dX, ldx, (const D *)Sb, s, nullptr, 0);
-    int its[64];
-    krylov_result(S, k, flags, its);
-    std::vector<double> out(128);
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipMemcpyAsync(out.data(), S.lam, 128 * sizeof(double), hipMemcpyDeviceToHost, stream));  // lam | res
-    HIP_OK(hipStreamSynchronize(stream));
-    for (int c = 0; c < k; ++c) {
-      if (lambda) lambda[c] = out[(size_t)c];
-      if (res) res[c] = out[64 + (size_t)c];
-    }
-    if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
-  }
-  void lobpcg_gen_dev(int64_t k, int64_t nev, const D *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
-                      int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info3) {
-    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, dX0 != nullptr, ldx, true);
-    if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
-    HIP_OK(hipSetDevice(device));
-    lobpcg_gen_tile(dX0, ldx0, seed, (int)k, (int)nev, tol, deftol, maxit, rank, dX, ldx, lambda, res, flags, info3);
-  }
-  void lobpcg_gen_host(int64_t k, int64_t nev, const T *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit,
-                       int64_t rank, double *lambda, T *X, int64_t ldx, double *res, int *flags, int *info3) {
-    lobpcg_check(k, nev, tol, deftol, maxit, ldx0, X0 != nullptr, ldx, true);
-    if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
-    HIP_OK(hipSetDevice(device));
-    const int64_t n = lv[0]->n;
-    const size_t need = (size_t)n * k * sizeof(T);
-    if (stage_b.bytes < need) stage_b.alloc(need);
-    if (stage_x.bytes < need) stage_x.alloc(need);
-    StreamWait wait{stream};
-    if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
-    lobpcg_gen_tile(X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, (int)k, (int)nev, tol, deftol, maxit, rank, stage_x.as<D>(),
-                    k, lambda, res, flags, info3);
+    lobpcg_dev(gen, k, nev, X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed, tol, deftol, maxit, rank, lambda, stage_x.as<D>(), k, res,
+               flags, info3);
     HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
   }
@@ -5060,7 +4954,7 @@ HifAmdStatus hifamd_lobpcg(HifAmdHdl h, int64_t k, int64_t nev, const void *X0, 
                            int *info3) {
   API_BEGIN
   visit(h, [&](auto &E) {
-    E.lobpcg_host(k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
+    E.lobpcg_host(false, k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
   });
   API_END
 }
@@ -5070,7 +4964,7 @@ HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *
                                int *flags, int *info3) {
   API_BEGIN
   visit(h, [&](auto &E) {
-    E.lobpcg_dev(k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
+    E.lobpcg_dev(false, k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
   });
   API_END
 }
@@ -5086,7 +4980,7 @@ HifAmdStatus hifamd_lobpcg_gen(HifAmdHdl h, int64_t k, int64_t nev, const void *
                                int *flags, int *info3) {
   API_BEGIN
   visit(h, [&](auto &E) {
-    E.lobpcg_gen_host(k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
+    E.lobpcg_host(true, k, nev, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res, flags, info3);
   });
   API_END
 }
@@ -5096,7 +4990,7 @@ HifAmdStatus hifamd_lobpcg_gen_dev(HifAmdHdl h, int64_t k, int64_t nev, const vo
                                    int *flags, int *info3) {
   API_BEGIN
   visit(h, [&](auto &E) {
-    E.lobpcg_gen_dev(k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
+    E.lobpcg_dev(true, k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
   });
   API_END
 }

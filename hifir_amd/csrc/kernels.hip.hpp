@@ -37,10 +37,9 @@
 //                    row-local products on the f64 matrix cores, the small matrices in one workgroup (blockcg_small.hpp)
 //   k_bgcr_gram / k_bgcr_sum / k_bgcr_proj / k_bgcr_rmul / k_bgcr_rho / k_bgcr_small   device-resident restarted block GCR: the
 //                    stacked Gram, the fused block Gram-Schmidt pass, in-place right-multiplication, decisions (blockgcr_small.hpp)
-//   k_lob_gram2 / k_lob_update / k_lob_resid / k_lob_lock / k_lob_small   device-resident LOBPCG: both Grams of the basis
-//                    [X W P] in one pass, the row-local update, the Rayleigh-Ritz step in one workgroup (lobpcg_small.hpp)
-//   k_lob_gram3 / k_lob_update3 / k_lob_resid_gen / k_lob_test_gen   their siblings for the generalized problem A x = lambda B x:
-//                    a third block [BX BW BP], the Grams S^H BS and S^H AS, the backward-error stopping test
+//   k_lob_gram / k_lob_update / k_lob_resid / k_lob_lock / k_lob_small   device-resident LOBPCG: both Grams of the basis
+//                    [X W P] in one pass, the row-local update, the Rayleigh-Ritz step in one workgroup (lobpcg_small.hpp);
+//                    instantiated with a third block [BX BW BP] for the generalized problem A x = lambda B x
 //   k_colsum_partial / k_sub_colmean   null-space-filter BLAS-1
 //   k_nsp_coef / k_nsp_finish / k_nsp_sub   basis mode of the null-space filter: x -= Q (Q^H x)
 //   k_probe_fill / k_blk_rmul   null-space search: counter-based probe block, V <- V C for a 16 x 16 C
@@ -6401,13 +6400,19 @@ __global__ void __launch_bounds__(256) k_bgcr_small(int mode, int steps, int fla
 // ---------------------------------------------------------------------------------------------
 // Device-resident LOBPCG for the smallest eigenpairs of a Hermitian pair (A, M) (Engine::lobpcg_tile): k <= 16 candidates,
 // the basis S = [X W P] and its image AS = [AX AW AP] as two [n][ld] blocks (ld = s = 3 k <= 48 columns, X at column 0, W at
-// k, P at 2 k), the residual R as [n][k].  Per step:
-//   k_lob_resid    R = AX - X diag(lambda) and the partials of |r_j|^2
-//   k_lob_lock     exact zeros in the columns of R that the test found converged (so that W = M^{-1} R is zero there)
-//   k_lob_gram2    partials of GB = S^H S and GA = S^H AS in one pass, upper block triangle, v_mfma_f64_16x16x4_f64
-//   k_lob_update   X, P <- S [C Cp] and AX, AP <- AS [C Cp] on the matrix cores, [C Cp] staged in LDS
-//   k_lob_small    one workgroup: the residual test, the Rayleigh-Ritz step (lobpcg_small.hpp, shared with the host), every
-//                  decision and flag
+// k, P at 2 k), the residual R as [n][k].  The generalized problem A x = lambda B x (GEN, or NB = 3) has a third [n][ld]
+// block BS = [BX BW BP] beside them and is the same kernels instantiated for three blocks: one lane map, one row ownership
+// and one order of summation, so that an explicit identity B (BS a bitwise copy of S) reproduces the standard iterates bit
+// for bit.  Per step:
+//   k_lob_resid<GEN>   R = AX - X diag(lambda) and the partials of |r_j|^2; GEN: R = AX - BX diag(lambda), and the partials
+//                      of |x_j|^2 as well
+//   k_lob_lock         exact zeros in the columns of R that the test found converged (so that W = M^{-1} R is zero there)
+//   k_lob_gram<GEN>    partials of GB = S^H S (GEN: S^H BS) and GA = S^H AS in one pass, upper block triangle,
+//                      v_mfma_f64_16x16x4_f64
+//   k_lob_update<NB>   X, P <- S [C Cp], AX, AP <- AS [C Cp] (NB = 3: and BX, BP <- BS [C Cp]) on the matrix cores, [C Cp]
+//                      staged in LDS
+//   k_lob_small        one workgroup: the residual test (the generalized one where LobState says so), the Rayleigh-Ritz step
+//                      (lobpcg_small.hpp, shared with the host; it sees GB whichever product it is), every decision and flag
 // Lane maps, complex handles on real planes, fixed-order partials (k_bcg_sum adds the blocks): as block CG above.
 // ---------------------------------------------------------------------------------------------
 constexpr int kLobResBlocks = 1024;  // workgroups (and partials per column) of k_lob_resid
@@ -6418,9 +6423,10 @@ struct LobState : KrylovState {
   // ctl: [0] 1 while the tile runs, [1] rank of the basis in the last step, [2] largest Jacobi sweep count,
   //      [3] the start's verdict (lob::kStart*)
   T *GB, *GA, *CC, *X1, *X2, *X3;  // [64][64] each: the summed Grams, [C Cp] of the next row pass, scratch of the small kernel
-  double *lam, *res;               // [64]  Ritz values; ||r_j|| / ||A||_inf of the last test
-  double deftol, anorm;
+  double *lam, *res;               // [64]  Ritz values; the scaled ||r_j|| of the last test
+  double deftol, anorm, b_inf;     // b_inf: ||B||_inf of the generalized problem (KrylovState's bnorm is the [64] slot)
   int k, nev;
+  bool gen;                        // the generalized problem: mode 2 of k_lob_small runs the generalized test
 };
 
 // element (row, col) of an [n][ld] block whose first s columns are in use, an exact zero outside; the load is unconditional
@@ -6431,12 +6437,13 @@ __device__ __forceinline__ T lob_load(const T *__restrict__ x, int64_t n, int ld
   return ok ? v : vzero(T());
 }
 
-// partial[0][blockIdx.x] and partial[1][blockIdx.x] ([64][64] each) = the block's share of S^H S and S^H AS, tiles (ti <= tj)
-// only.  Wave w of block b owns the row groups g = 4 b + w + k * 4 gridDim.x (rows 4 g .. 4 g + 3, one K step each); the
-// conjugated strip of S is loaded once and is the left operand of both products.
-template <class T>
-__global__ void __launch_bounds__(256) k_lob_gram2(int64_t n, int ld, int s, const T *__restrict__ S, const T *__restrict__ AS,
-                                                   T *__restrict__ partial /* [2][gridDim.x][64][64] */) {
+// partial[0][blockIdx.x] and partial[1][blockIdx.x] ([64][64] each) = the block's share of S^H S (GEN: S^H BS) and S^H AS,
+// tiles (ti <= tj) only.  Wave w of block b owns the row groups g = 4 b + w + k * 4 gridDim.x (rows 4 g .. 4 g + 3, one K
+// step each), two of them in flight; the conjugated strip of S is loaded once and is the left operand of both products --
+// and, where there is no BS (!GEN: BS is not read), the right operand of the first.
+template <class T, bool GEN>
+__global__ void __launch_bounds__(256) k_lob_gram(int64_t n, int ld, int s, const T *__restrict__ S, const T *__restrict__ BS,
+                                                  const T *__restrict__ AS, T *__restrict__ partial /* [2][gridDim.x][64][64] */) {
   __shared__ T lds[12 * 4 * 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
   const int nt = (s + 15) >> 4;
@@ -6452,9 +6459,11 @@ __global__ void __launch_bounds__(256) k_lob_gram2(int64_t n, int ld, int s, con
     for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        b[u][t] = lob_load(S, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+        const T x = lob_load(S, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
+        a[u][t] = vconj(x);
+        b[u][t] = x;
+        if constexpr (GEN) b[u][t] = lob_load(BS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
         c[u][t] = lob_load(AS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
-        a[u][t] = vconj(b[u][t]);
       }
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -6510,40 +6519,46 @@ __global__ void __launch_bounds__(256) k_lob_gram2(int64_t n, int ld, int s, con
   }
 }
 
-// X <- S C, P <- S Cp, AX <- AS C, AP <- AS Cp in place: CC [64][64] holds C in its columns 0 .. 15 and Cp in 16 .. 31 (rows
-// >= s and columns >= k of either are zero), staged in LDS once per workgroup.  A wave owns the 16-row strips
-// 4 b + w + j * 4 gridDim.x and reads its strip of S and of AS completely, as operands, before it writes any of it.
-template <class T>
+// X <- S C, P <- S Cp, and the same for AS (AX, AP) and, NB = 3, for BS (BX, BP; NB = 2: BS is not touched), in place: CC
+// [64][64] holds C in its columns 0 .. 15 and Cp in 16 .. 31 (rows >= s and columns >= k of either are zero), staged in LDS
+// once per workgroup.  A wave owns the 16-row strips 4 b + w + j * 4 gridDim.x and reads its strip of all NB blocks
+// completely, as operands, before it writes any of it.  Inside a K step the products go block by block: S, AS[, BS].
+template <class T, int NB>
 __global__ void __launch_bounds__(256) k_lob_update(int64_t n, int ld, int s, int k, T *__restrict__ S, T *__restrict__ AS,
-                                                    const T *__restrict__ CC) {
+                                                    T *__restrict__ BS, const T *__restrict__ CC) {
+  static_assert(NB == 2 || NB == 3, "two blocks (S, AS) or three (S, AS, BS)");
   __shared__ T cc[48 * 32];
   for (int e = threadIdx.x; e < 48 * 32; e += blockDim.x) cc[e] = CC[(e >> 5) * 64 + (e & 31)];
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
   const int nt = (s + 15) >> 4;
   const int64_t stride = (int64_t)gridDim.x * 4;
+  T *const blk[3] = {S, AS, BS};
   for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
     const int64_t r0 = 16 * st;
-    T x[12], ax[12];
+    T x[NB][12];
 #pragma unroll
     for (int kk = 0; kk < 12; ++kk) {
-      x[kk] = ax[kk] = vzero(T());
+#pragma unroll
+      for (int m = 0; m < NB; ++m) x[m][kk] = vzero(T());
       if (kk < 4 * nt) {
-        x[kk] = lob_load((const T *)S, n, ld, s, r0 + ci, 4 * kk + kq);
-        ax[kk] = lob_load((const T *)AS, n, ld, s, r0 + ci, 4 * kk + kq);
+#pragma unroll
+        for (int m = 0; m < NB; ++m) x[m][kk] = lob_load((const T *)blk[m], n, ld, s, r0 + ci, 4 * kk + kq);
       }
     }
-    BcgAcc<T> as[2], aa[2];
+    BcgAcc<T> acc[NB][2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) bcg_clear(as[t]), bcg_clear(aa[t]);
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int m = 0; m < NB; ++m) bcg_clear(acc[m][t]);
 #pragma unroll
     for (int kk = 0; kk < 12; ++kk)
       if (kk < 4 * nt) {
 #pragma unroll
         for (int tj = 0; tj < 2; ++tj) {
           const T b = cc[(4 * kk + kq) * 32 + 16 * tj + ci];
-          bcg_mma(as[tj], x[kk], b);
-          bcg_mma(aa[tj], ax[kk], b);
+#pragma unroll
+          for (int m = 0; m < NB; ++m) bcg_mma(acc[m][tj], x[m][kk], b);
         }
       }
 #pragma unroll
@@ -6552,37 +6567,44 @@ __global__ void __launch_bounds__(256) k_lob_update(int64_t n, int ld, int s, in
       for (int reg = 0; reg < 4; ++reg) {
         const int64_t row = r0 + kq + 4 * reg;
         if (row < n && ci < k) {
-          S[row * ld + 2 * k * tj + ci] = bcg_get(as[tj], reg);
-          AS[row * ld + 2 * k * tj + ci] = bcg_get(aa[tj], reg);
+#pragma unroll
+          for (int m = 0; m < NB; ++m) blk[m][row * ld + 2 * k * tj + ci] = bcg_get(acc[m][tj], reg);
         }
       }
   }
 }
 
-// R = AX - X diag(lambda) ([n][k]; X and AX are the first k columns of their [n][ld] blocks) and the block's share of
-// |r_j|^2: thread t owns column t & 15 of the rows 16 b + (t >> 4) + j * 16 gridDim.x in that order, the sixteen row
-// classes of a block are added in order: partial[blockIdx.x][16]
-template <class T>
+// R = AX - X diag(lambda) (GEN: AX - BX diag(lambda)) ([n][k]; X, AX and BX are the first k columns of their [n][ld] blocks;
+// !GEN: BS is not read) and the block's share of |r_j|^2: thread t owns column t & 15 of the rows
+// 16 b + (t >> 4) + j * 16 gridDim.x in that order, the sixteen row classes of a block are added in order:
+// partial[blockIdx.x][16].  GEN: the share of |x_j|^2 as well, same rows and order: partial[blockIdx.x][32], |r_j|^2 at j
+// and |x_j|^2 at 16 + j.
+template <class T, bool GEN>
 __global__ void __launch_bounds__(256) k_lob_resid(int64_t n, int ld, int k, const T *__restrict__ S, const T *__restrict__ AS,
-                                                   const double *__restrict__ lam, T *__restrict__ R,
-                                                   double *__restrict__ partial /* [gridDim.x][16] */) {
-  __shared__ double sm[256];
+                                                   const T *__restrict__ BS, const double *__restrict__ lam, T *__restrict__ R,
+                                                   double *__restrict__ partial /* [gridDim.x][GEN ? 32 : 16] */) {
+  constexpr int np = GEN ? 32 : 16;
+  __shared__ double sm[16 * np];
   const int c = threadIdx.x & 15, sub = threadIdx.x >> 4;
-  double acc = 0.0;
+  const T *__restrict__ X = GEN ? BS : S;  // what lambda multiplies
+  double acc = 0.0, accx = 0.0;
   if (c < k) {
     const double l = lam[c];
     for (int64_t i = (int64_t)blockIdx.x * 16 + sub; i < n; i += (int64_t)gridDim.x * 16) {
-      const T r = vsub(AS[i * ld + c], vscale(l, S[i * ld + c]));
+      const T r = vsub(AS[i * ld + c], vscale(l, X[i * ld + c]));
       R[i * k + c] = r;
       acc += vabs2(r);
+      if constexpr (GEN) accx += vabs2(S[i * ld + c]);
     }
   }
   sm[threadIdx.x] = acc;
+  if constexpr (GEN) sm[256 + threadIdx.x] = accx;
   __syncthreads();
-  if (threadIdx.x < 16) {
-    double tot = sm[threadIdx.x];
-    for (int u = 1; u < 16; ++u) tot += sm[16 * u + threadIdx.x];
-    partial[blockIdx.x * 16 + threadIdx.x] = tot;
+  if (threadIdx.x < np) {
+    const int j = threadIdx.x & 15, base = threadIdx.x < 16 ? 0 : 256;
+    double tot = sm[base + j];
+    for (int u = 1; u < 16; ++u) tot += sm[base + 16 * u + j];
+    partial[blockIdx.x * np + threadIdx.x] = tot;
   }
 }
 
@@ -6598,196 +6620,24 @@ __global__ void __launch_bounds__(256) k_lob_lock(int64_t n, int k, T *__restric
 // more, of the state, in HBM).  step: the completed steps.
 //   mode 0: lob::start_factor  (X0^H X0 -> CC = [E 0], or the start's refusal)
 //   mode 1: lob::ritz_step at the start  (X^H A X = V Theta V^H -> CC = [V 0], lambda)
-//   mode 2: lob::residual_test on the kLobResBlocks partials of |r_j|^2
+//   mode 2: lob::residual_test on the kLobResBlocks partials of |r_j|^2; S.gen: the generalized test, on those of |r_j|^2
+//           and |x_j|^2
 //   mode 3: lob::ritz_step  (GB, GA -> CC = [C Cp], lambda, rank; or the breakdown)
 template <class T>
 __global__ void __launch_bounds__(256) k_lob_small(int mode, int step, const double *__restrict__ partial, LobState<T> S) {
   extern __shared__ double bcg_lds_raw[];
   const lob::RitzScratch<T> W = lob::RitzScratch<T>::carve(bcg_lds_raw, S.X1, S.X2, S.X3);
-  const lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev};
+  const lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev, S.b_inf};
   const BcgTeam tm;
+  if (mode == 2) {  // (first and apart: behind the Ritz modes the complex instantiation takes one VGPR past five waves)
+    if (S.gen)
+      lob::residual_test_gen(Sm, partial, kLobResBlocks, step, tm);
+    else
+      lob::residual_test(Sm, partial, kLobResBlocks, step, tm);
+    return;
+  }
   if (mode == 0) lob::start_factor(Sm, W, tm);
   if (mode == 1 || mode == 3) lob::ritz_step(Sm, W, mode == 1, step, tm);
-  if (mode == 2) lob::residual_test(Sm, partial, kLobResBlocks, step, tm);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The generalized problem A x = lambda B x (Engine::lobpcg_gen_tile): a third [n][ld] block BS = [BX BW BP] beside S and AS.
-// Siblings of the kernels above, with their lane maps, row ownership and orders of summation, so that an explicit identity
-// B (BS a bitwise copy of S) reproduces the standard driver's iterates bit for bit:
-//   k_lob_gram3       partials of GB = S^H BS and GA = S^H AS: the conjugated strip of S is the left operand of both
-//   k_lob_update3     X, P / AX, AP / BX, BP <- S, AS, BS [C Cp] in one launch
-//   k_lob_resid_gen   R = AX - BX diag(lambda) and the partials of |r_j|^2 and |x_j|^2
-//   k_lob_test_gen    one workgroup: lob::residual_test_gen
-// k_lob_lock, k_lob_small (modes 0, 1, 3: they see GB = S^H BS) and k_bcg_sum are reused as they are.
-// ---------------------------------------------------------------------------------------------
-// partial[0][blockIdx.x] and partial[1][blockIdx.x] ([64][64] each) = the block's share of S^H BS and S^H AS, tiles (ti <= tj)
-// only; row groups (two in flight per wave), K steps, wave-order sum and output as k_lob_gram2.
-template <class T>
-__global__ void __launch_bounds__(256) k_lob_gram3(int64_t n, int ld, int s, const T *__restrict__ S, const T *__restrict__ BS,
-                                                   const T *__restrict__ AS, T *__restrict__ partial /* [2][gridDim.x][64][64] */) {
-  __shared__ T lds[12 * 4 * 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
-  const int nt = (s + 15) >> 4;
-  BcgAcc<T> acc[2][6];  // tile (ti, tj), ti <= tj < 3, at index 3 ti + tj - ti (ti + 1) / 2
-#pragma unroll
-  for (int w = 0; w < 2; ++w)
-#pragma unroll
-    for (int t = 0; t < 6; ++t) bcg_clear(acc[w][t]);
-  const int64_t stride = (int64_t)gridDim.x * 4;
-  for (int64_t g = (int64_t)blockIdx.x * 4 + wave; 4 * g < n; g += 2 * stride) {
-    T a[2][3], b[2][3], c[2][3];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        a[u][t] = vconj(lob_load(S, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci));
-        b[u][t] = lob_load(BS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
-        c[u][t] = lob_load(AS, n, ld, s, 4 * (g + u * stride) + kq, 16 * t + ci);
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int ti = 0; ti < 3; ++ti)
-#pragma unroll
-        for (int tj = ti; tj < 3; ++tj)
-          if (tj < nt) {
-            bcg_mma(acc[0][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], b[u][tj]);
-            bcg_mma(acc[1][3 * ti + tj - ti * (ti + 1) / 2], a[u][ti], c[u][tj]);
-          }
-  }
-  // the four waves of the block in wave order
-  for (int w = 1; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) lds[((m * 6 + t) * 4 + reg) * 64 + lane] = bcg_get(acc[m][t], reg);
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            const T v = lds[((m * 6 + t) * 4 + reg) * 64 + lane];
-            if constexpr (std::is_same<T, cplx>::value)
-              acc[m][t].re[reg] += v.x, acc[m][t].im[reg] += v.y;
-            else
-              acc[m][t].re[reg] += v;
-          }
-    }
-  }
-  if (wave != 0) return;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    T *__restrict__ out = partial + ((int64_t)m * gridDim.x + blockIdx.x) * 64 * 64;
-#pragma unroll
-    for (int ti = 0; ti < 3; ++ti)
-#pragma unroll
-      for (int tj = ti; tj < 3; ++tj)
-        if (tj < nt) {
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg)
-            out[(16 * ti + kq + 4 * reg) * 64 + 16 * tj + ci] = bcg_get(acc[m][3 * ti + tj - ti * (ti + 1) / 2], reg);
-        }
-  }
-}
-
-// X <- S C, P <- S Cp, and the same for AS (AX, AP) and BS (BX, BP), in place: CC, its staging, the strips and the lane map as
-// k_lob_update.  A wave reads its strip of all three blocks completely, as operands, before it writes any of it.
-template <class T>
-__global__ void __launch_bounds__(256) k_lob_update3(int64_t n, int ld, int s, int k, T *__restrict__ S, T *__restrict__ AS,
-                                                     T *__restrict__ BS, const T *__restrict__ CC) {
-  __shared__ T cc[48 * 32];
-  for (int e = threadIdx.x; e < 48 * 32; e += blockDim.x) cc[e] = CC[(e >> 5) * 64 + (e & 31)];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
-  const int nt = (s + 15) >> 4;
-  const int64_t stride = (int64_t)gridDim.x * 4;
-  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
-    const int64_t r0 = 16 * st;
-    T x[12], ax[12], bx[12];
-#pragma unroll
-    for (int kk = 0; kk < 12; ++kk) {
-      x[kk] = ax[kk] = bx[kk] = vzero(T());
-      if (kk < 4 * nt) {
-        x[kk] = lob_load((const T *)S, n, ld, s, r0 + ci, 4 * kk + kq);
-        ax[kk] = lob_load((const T *)AS, n, ld, s, r0 + ci, 4 * kk + kq);
-        bx[kk] = lob_load((const T *)BS, n, ld, s, r0 + ci, 4 * kk + kq);
-      }
-    }
-    BcgAcc<T> as[2], aa[2], ab[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) bcg_clear(as[t]), bcg_clear(aa[t]), bcg_clear(ab[t]);
-#pragma unroll
-    for (int kk = 0; kk < 12; ++kk)
-      if (kk < 4 * nt) {
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-          const T b = cc[(4 * kk + kq) * 32 + 16 * tj + ci];
-          bcg_mma(as[tj], x[kk], b);
-          bcg_mma(aa[tj], ax[kk], b);
-          bcg_mma(ab[tj], bx[kk], b);
-        }
-      }
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int64_t row = r0 + kq + 4 * reg;
-        if (row < n && ci < k) {
-          S[row * ld + 2 * k * tj + ci] = bcg_get(as[tj], reg);
-          AS[row * ld + 2 * k * tj + ci] = bcg_get(aa[tj], reg);
-          BS[row * ld + 2 * k * tj + ci] = bcg_get(ab[tj], reg);
-        }
-      }
-  }
-}
-
-// R = AX - BX diag(lambda) ([n][k]; X, AX and BX are the first k columns of their [n][ld] blocks) and the block's share of
-// |r_j|^2 and |x_j|^2: rows, columns and the order of the sums as k_lob_resid: partial[blockIdx.x][32], |r_j|^2 at j and
-// |x_j|^2 at 16 + j
-template <class T>
-__global__ void __launch_bounds__(256) k_lob_resid_gen(int64_t n, int ld, int k, const T *__restrict__ S, const T *__restrict__ AS,
-                                                       const T *__restrict__ BS, const double *__restrict__ lam, T *__restrict__ R,
-                                                       double *__restrict__ partial /* [gridDim.x][32] */) {
-  __shared__ double sm[512];
-  const int c = threadIdx.x & 15, sub = threadIdx.x >> 4;
-  double acc = 0.0, accx = 0.0;
-  if (c < k) {
-    const double l = lam[c];
-    for (int64_t i = (int64_t)blockIdx.x * 16 + sub; i < n; i += (int64_t)gridDim.x * 16) {
-      const T r = vsub(AS[i * ld + c], vscale(l, BS[i * ld + c]));
-      R[i * k + c] = r;
-      acc += vabs2(r);
-      accx += vabs2(S[i * ld + c]);
-    }
-  }
-  sm[threadIdx.x] = acc;
-  sm[256 + threadIdx.x] = accx;
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    const int j = threadIdx.x & 15, base = threadIdx.x < 16 ? 0 : 256;
-    double tot = sm[base + j];
-    for (int u = 1; u < 16; ++u) tot += sm[base + 16 * u + j];
-    partial[blockIdx.x * 32 + threadIdx.x] = tot;
-  }
-}
-
-// One workgroup: lob::residual_test_gen on the kLobResBlocks partials of |r_j|^2 and |x_j|^2 (k_lob_small's mode 2 for the
-// generalized problem; modes 0, 1 and 3 are k_lob_small's own)
-template <class T>
-__global__ void __launch_bounds__(256) k_lob_test_gen(int step, const double *__restrict__ partial, LobState<T> S, double bnorm) {
-  lob::Small<T> Sm{S.GB, S.GA, S.CC, S.lam, S.res, S.flag, S.iter, S.active, S.ctl, S.rtol, S.deftol, S.anorm, S.maxit, S.k, S.nev};
-  Sm.bnorm = bnorm;
-  const BcgTeam tm;
-  lob::residual_test_gen(Sm, partial, kLobResBlocks, step, tm);
 }
 
 }  // namespace hifamd

@@ -294,7 +294,7 @@ struct Small {
   int *flag, *iter, *active, *ctl;
   double tol, deftol, anorm;
   int maxit, k, nev;
-  double bnorm = 0.0;  // ||B||_inf of the generalized problem (residual_test_gen); the standard driver leaves it alone
+  double bnorm = 0.0;  // ||B||_inf of the generalized problem (residual_gen); the standard test does not read it
 };
 
 // The start's factorization: GB = X0^H X0 (k x k) -> pivoted Cholesky.  Not finite / rank < k (or a leftover below -deftol):
@@ -316,18 +316,40 @@ HIFAMD_HD inline void start_factor(const Small<T> &S, const RitzScratch<T> &w, c
   tm.sync();
 }
 
-// The residual test after `step` completed steps on nb partials of |r_j|^2 (partial[b][16], summed in block order):
-// res_j = sqrt(sum) / ||A||_inf, active_j = res_j > tol; every j < nev converged, or step >= maxit: flags 0 / 2 by each
-// column's own res_j, iter = step, and the tile is over.  A tile that is over is left alone.
-template <class T, class Team>
-HIFAMD_HD inline void residual_test(const Small<T> &S, const double *partial, int nb, int step, const Team &tm) {
+// res_j of the standard problem from nb partials of |r_j|^2 (partial[b][16], summed in block order): sqrt(sum) / ||A||_inf
+template <class T>
+HIFAMD_HD inline double residual_std(const Small<T> &S, const double *partial, int nb, int c) {
+  double tot = partial[c];
+  for (int b = 1; b < nb; ++b) tot += partial[b * kMaxK + c];
+  return S.anorm > 0.0 ? std::sqrt(tot) / S.anorm : std::sqrt(tot);
+}
+
+// res_j of the generalized problem A x = lambda B x from nb partials of |r_j|^2 and |x_j|^2 (partial[b][32]: |r_j|^2 at j,
+// |x_j|^2 at 16 + j; summed in block order), r_j = A x_j - lambda_j B x_j:
+// res_j = ||r_j|| / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||), the normwise backward error of the pair -- the vectors are
+// B-normalized, so ||x_j|| belongs in the scale.  A scale of exactly zero (x_j = 0, or both norms zero) leaves res_j = ||r_j||;
+// a scale that is not finite counts as not converged (res_j = HUGE_VAL), and so does a partial that is not finite (res_j is
+// NaN).
+template <class T>
+HIFAMD_HD inline double residual_gen(const Small<T> &S, const double *partial, int nb, int c) {
+  double rr = partial[c], xx = partial[kMaxK + c];
+  for (int b = 1; b < nb; ++b) rr += partial[b * 2 * kMaxK + c], xx += partial[b * 2 * kMaxK + kMaxK + c];
+  const double scale = (S.anorm + std::fabs(S.lam[c]) * S.bnorm) * std::sqrt(xx);
+  double res = scale == 0.0 ? std::sqrt(rr) : std::sqrt(rr) / scale;
+  if (scale > 1.7976931348623157e308) res = HUGE_VAL;
+  return res;
+}
+
+// The residual test after `step` completed steps: res_j = res_of(c) for every column (residual_std or residual_gen of the
+// partials), active_j = res_j > tol; every j < nev converged, or step >= maxit: flags 0 / 2 by each column's own res_j,
+// iter = step, and the tile is over.  A tile that is over is left alone.
+template <class T, class Team, class ResOf>
+HIFAMD_HD inline void residual_verdict(const Small<T> &S, int step, const Team &tm, const ResOf &res_of) {
   const bool over = S.ctl[0] == 0;
   tm.sync();  // (everybody has read ctl before thread 0 may change it)
   if (over) return;
   for (int c = tm.rank(); c < S.k; c += tm.size()) {
-    double tot = partial[c];
-    for (int b = 1; b < nb; ++b) tot += partial[b * kMaxK + c];
-    const double res = S.anorm > 0.0 ? std::sqrt(tot) / S.anorm : std::sqrt(tot);
+    const double res = res_of(c);
     S.res[c] = res;
     S.active[c] = res <= S.tol ? 0 : 1;
   }
@@ -340,35 +362,13 @@ HIFAMD_HD inline void residual_test(const Small<T> &S, const double *partial, in
   }
   tm.sync();
 }
-
-// The residual test of the generalized problem A x = lambda B x (Engine::lobpcg_gen_tile) on nb partials of |r_j|^2 and
-// |x_j|^2 (partial[b][32]: |r_j|^2 at j, |x_j|^2 at 16 + j; summed in block order), r_j = A x_j - lambda_j B x_j:
-// res_j = ||r_j|| / ((||A||_inf + |lambda_j| ||B||_inf) ||x_j||), the normwise backward error of the pair -- the vectors are
-// B-normalized, so ||x_j|| belongs in the scale.  A scale of exactly zero (x_j = 0, or both norms zero) leaves res_j = ||r_j||;
-// a scale that is not finite counts as not converged (res_j = HUGE_VAL), and so does a partial that is not finite (res_j is
-// NaN).  Decisions, flags and the end of the tile: as residual_test.
+template <class T, class Team>
+HIFAMD_HD inline void residual_test(const Small<T> &S, const double *partial, int nb, int step, const Team &tm) {
+  residual_verdict(S, step, tm, [&](int c) { return residual_std(S, partial, nb, c); });
+}
 template <class T, class Team>
 HIFAMD_HD inline void residual_test_gen(const Small<T> &S, const double *partial, int nb, int step, const Team &tm) {
-  const bool over = S.ctl[0] == 0;
-  tm.sync();
-  if (over) return;
-  for (int c = tm.rank(); c < S.k; c += tm.size()) {
-    double rr = partial[c], xx = partial[kMaxK + c];
-    for (int b = 1; b < nb; ++b) rr += partial[b * 2 * kMaxK + c], xx += partial[b * 2 * kMaxK + kMaxK + c];
-    const double scale = (S.anorm + std::fabs(S.lam[c]) * S.bnorm) * std::sqrt(xx);
-    double res = scale == 0.0 ? std::sqrt(rr) : std::sqrt(rr) / scale;
-    if (scale > 1.7976931348623157e308) res = HUGE_VAL;
-    S.res[c] = res;
-    S.active[c] = res <= S.tol ? 0 : 1;
-  }
-  tm.sync();
-  bool all = true;
-  for (int c = 0; c < S.nev; ++c) all = all && S.active[c] == 0;
-  if (all || step >= S.maxit) {
-    for (int c = tm.rank(); c < S.k; c += tm.size()) S.flag[c] = S.active[c] ? 2 : 0, S.iter[c] = step;
-    if (tm.rank() == 0) S.ctl[0] = 0;
-  }
-  tm.sync();
+  residual_verdict(S, step, tm, [&](int c) { return residual_gen(S, partial, nb, c); });
 }
 
 // The Rayleigh-Ritz step of the tile after `step` completed steps.  start: on GA = X^H A X (k x k), no Cholesky; a failure

@@ -354,16 +354,7 @@ class HIF {
       const Matrix &A, const int k, const int nev, const ArrayType &X0, const double tol, const int maxit,
       const std::uint64_t seed = 0, const double deftol = 1e-12, const bool full_rank = false) {
     ensure_matrix(A);
-    if (k < 1) throw std::runtime_error("hifir_amd: lobpcg needs k >= 1");
-    if (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k)
-      throw std::runtime_error("hifir_amd: lobpcg needs an empty X0 or one of nrows() * k entries");
-    ArrayType X((std::size_t)nrows() * k);
-    std::vector<double> lambda(k, 0.0), res(k, 0.0);
-    std::vector<int> flags(k, 0);
-    int info3[3] = {0, 0, 0};
-    detail::check(hifamd_lobpcg(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit, full_rank ? -1 : 0,
-                                lambda.data(), X.data(), k, res.data(), flags.data(), info3));
-    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+    return lobpcg_call<ArrayType>(hifamd_lobpcg, "lobpcg", k, nev, X0, tol, maxit, seed, deftol, full_rank);
   }
 
   // ---- generalized LOBPCG: the nev smallest eigenpairs of A x = lambda B x (hifamd_lobpcg_gen) ----
@@ -387,16 +378,7 @@ class HIF {
       const std::uint64_t seed = 0, const double deftol = 1e-12, const bool full_rank = false) {
     ensure_matrix(A);
     if (!_has_B) set_mass_matrix(B);
-    if (k < 1) throw std::runtime_error("hifir_amd: lobpcg_gen needs k >= 1");
-    if (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k)
-      throw std::runtime_error("hifir_amd: lobpcg_gen needs an empty X0 or one of nrows() * k entries");
-    ArrayType X((std::size_t)nrows() * k);
-    std::vector<double> lambda(k, 0.0), res(k, 0.0);
-    std::vector<int> flags(k, 0);
-    int info3[3] = {0, 0, 0};
-    detail::check(hifamd_lobpcg_gen(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit,
-                                    full_rank ? -1 : 0, lambda.data(), X.data(), k, res.data(), flags.data(), info3));
-    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+    return lobpcg_call<ArrayType>(hifamd_lobpcg_gen, "lobpcg_gen", k, nev, X0, tol, maxit, seed, deftol, full_rank);
   }
 
   // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
@@ -440,6 +422,22 @@ class HIF {
   }
 
  private:
+  // what lobpcg and lobpcg_gen share: the size checks (in the caller's name), the outputs, the call, the tuple
+  template <class ArrayType, class Entry>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, int> lobpcg_call(
+      Entry entry, const std::string &method, const int k, const int nev, const ArrayType &X0, const double tol, const int maxit,
+      const std::uint64_t seed, const double deftol, const bool full_rank) {
+    if (k < 1) throw std::runtime_error("hifir_amd: " + method + " needs k >= 1");
+    if (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k)
+      throw std::runtime_error("hifir_amd: " + method + " needs an empty X0 or one of nrows() * k entries");
+    ArrayType X((std::size_t)nrows() * k);
+    std::vector<double> lambda(k, 0.0), res(k, 0.0);
+    std::vector<int> flags(k, 0);
+    int info3[3] = {0, 0, 0};
+    detail::check(entry(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit, full_rank ? -1 : 0, lambda.data(),
+                        X.data(), k, res.data(), flags.data(), info3));
+    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+  }
   void require() const {
     if (!_h) throw std::runtime_error("hifir_amd: MILU-Prec is empty!");  // builder.hpp:412
   }

@@ -2,7 +2,7 @@
 // tests/test_lobpcg_gen_host.py; no GPU, no input file).
 //
 // lob::residual_test_gen of hifir_amd/csrc/lobpcg_small.hpp, the stopping test of the generalized LOBPCG driver, with the team
-// of one -- what k_lob_test_gen must reproduce bit for bit -- on hand-made partials [nb][32] (|r_j|^2 at j, |x_j|^2 at 16 + j).
+// of one -- what k_lob_small's mode 2 must reproduce bit for bit -- on hand-made partials [nb][32] (|r_j|^2 at j, |x_j|^2 at 16 + j).
 // Every expectation is computed here: res_j = sqrt(sum r) / ((anorm + |lambda_j| bnorm) sqrt(sum x)) with the sums in block
 // order, active_j = !(res_j <= tol), and the tile's end (flags 0 / 2, iter = step, ctl[0] = 0) when every j < nev is
 // converged or step == maxit.  Exit code 0 and "GEN SMALL TEST OK" = every check holds.

@@ -81,33 +81,42 @@ def trace(steps):
     print("trace LOBPCG", steps, "steps:", out[4], M.last_lobpcg_info.tolist())
 
 
+def kernel_key(name):
+    """a profiler's kernel name -> its key in SHAPES: the base name, and for the kernels that are instantiated per problem
+    (k_lob_gram<T, GEN>, k_lob_update<T, NB>, k_lob_resid<T, GEN>) their last template argument: k_lob_gram<true>"""
+    m = re.search(r"(k_lob_\w+)(?:<([^>]*)>)?", name)
+    if not m:
+        return None
+    args = [a.strip() for a in (m.group(2) or "").split(",")]
+    return "%s<%s>" % (m.group(1), args[-1]) if len(args) > 1 else m.group(1)
+
+
 # float64 columns of n rows that a kernel reads plus writes per launch at k = 16
 SHAPES = {
-    "k_lob_gram2": 96,    # S and AS read, 48 columns each
-    "k_lob_update": 160,  # S and AS read (96), X, P, AX, AP written (64)
-    "k_lob_resid": 48,    # X, AX read, R written
-    "k_lob_lock": 0,      # writes converged columns only
+    "k_lob_gram<false>": 96,   # S and AS read, 48 columns each
+    "k_lob_update<2>": 160,    # S and AS read (96), X, P, AX, AP written (64)
+    "k_lob_resid<false>": 48,  # X, AX read, R written
+    "k_lob_lock": 0,           # writes converged columns only
     "k_lob_small": 0,
 }
 
 
-def kernel_stats(path, out_dir):
+def kernel_stats(path, out_dir, shapes=SHAPES, json_name="lobpcg.json", script="dev_lobpcg.py"):
     out = {}
     for r in csv.DictReader(open(path)):
-        name = r.get("Name") or r.get("KernelName") or ""
-        m = re.search(r"(k_lob_\w+)", name)
-        if not m:
+        key = kernel_key(r.get("Name") or r.get("KernelName") or "")
+        if key not in shapes:
             continue
-        nbytes = SHAPES[m.group(1)] * COL
+        nbytes = shapes[key] * COL
         avg_ns = float(r["AverageNs"])
-        out[m.group(1)] = {"calls": int(r["Calls"]), "avg_us": avg_ns / 1e3, "bytes": nbytes,
+        out[key] = {"calls": int(r["Calls"]), "avg_us": avg_ns / 1e3, "bytes": nbytes,
                            "GB_per_s": nbytes / avg_ns if nbytes else None, "us_at_8TB_per_s": nbytes / 8e6 if nbytes else None}
     print(json.dumps(out, indent=1))
     if out_dir:
-        p = os.path.join(out_dir, "lobpcg.json")
+        p = os.path.join(out_dir, json_name)
         res = json.load(open(p)) if os.path.exists(p) else {}
-        res["kernel_stats_note"] = ("rocprofv3 --kernel-trace --stats of `dev_lobpcg.py --trace-steps` (a run of its own, no "
-                                    "counters); bytes from the shapes at k = 16")
+        res["kernel_stats_note"] = ("rocprofv3 --kernel-trace --stats of `%s --trace-steps` (a run of its own, no "
+                                    "counters); bytes from the shapes at k = 16" % script)
         res["kernel_stats"] = out
         with open(p, "w") as f:
             json.dump(res, f, indent=1)

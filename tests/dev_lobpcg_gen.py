@@ -8,9 +8,9 @@ nev = 10, tol 1e-8, generated start, device-pointer (torch) entry, one handle, o
         -> DIR/lobpcg_gen.json (stamped with the head and the library).  --hier: the factorized hierarchy is read from FILE
         (hifamd_load) when it exists and written there when not, so that further runs do not factorize again
   python tests/dev_lobpcg_gen.py --parent-lib SO [--out DIR] [--hier FILE]
-        ms per step of the standard lobpcg with ANOTHER build of the library (the parent commit's, which has none of the new
-        symbols), same repeats; with --out merged into DIR/lobpcg_gen.json next to this build's figure and the verdict: this
-        build's median does not exceed the parent's by more than the spread (max - min) of the parent's own repeats
+        ms per step of the standard lobpcg, and of lobpcg_gen where it has it, with ANOTHER build of the library (the parent
+        commit's), same repeats; with --out merged into DIR/lobpcg_gen.json next to this build's figures and the verdicts:
+        this build's median does not exceed the parent's by more than the spread (max - min) of the parent's own repeats
   python tests/dev_lobpcg_gen.py --trace-steps K [--hier FILE]
         one K-step call after a warm-up, for a rocprofv3 --kernel-trace --stats run of its own
   python tests/dev_lobpcg_gen.py --kernel-stats CSV [--out DIR]
@@ -18,10 +18,8 @@ nev = 10, tol 1e-8, generated start, device-pointer (torch) entry, one handle, o
         columns, 8 B) next to the time those bytes need at 8 TB/s; with --out merged into DIR/lobpcg_gen.json
 """
 import argparse
-import csv
 import json
 import os
-import re
 import sys
 import time
 
@@ -130,22 +128,35 @@ def measure(out_dir, hier):
 
 
 def parent(lib_path, out_dir, hier):
-    """the standard driver's step with another build of the library; that build has none of the new symbols"""
+    """both drivers' steps with another build of the library (the parent commit's); the signatures of entry points that build
+    lacks are dropped, and the generalized step is measured only where it has them"""
+    import ctypes
+    import hashlib
+
+    import torch  # noqa: F401  (before the library, as in measure(): torch found no GPU when its runtime came second)
+
     os.environ["HIFIR_AMD_LIB"] = os.path.abspath(lib_path)
     from hifir_amd import _lib
 
     _lib.LIB_PATH = os.path.abspath(lib_path)
+    other = ctypes.CDLL(_lib.LIB_PATH)
+    has_gen = all(hasattr(other, name) for name in NEW_SYMBOLS)
     for name in NEW_SYMBOLS:
-        _lib.SIGNATURES.pop(name, None)
-    import hashlib
-
-    A, B, M = setup(hier, mass=False)
+        if not has_gen:
+            _lib.SIGNATURES.pop(name, None)
+    A, B, M = setup(hier, mass=has_gen)
     X0 = start_block()
     M.lobpcg(X0=X0, nev=NEV, tol=1e-300, maxit=2)
+    if has_gen:
+        M.lobpcg_gen(X0=X0, nev=NEV, tol=1e-300, maxit=2)
+    gen = per_step(lambda m: M.lobpcg_gen(X0=X0, nev=NEV, tol=1e-300, maxit=m)) if has_gen else None
     std = per_step(lambda m: M.lobpcg(X0=X0, nev=NEV, tol=1e-300, maxit=m))
     out = {"parent_lib_sha256": hashlib.sha256(open(lib_path, "rb").read()).hexdigest(),
            "parent_lobpcg_ms_per_step": float(np.median(std)), "parent_lobpcg_ms_per_step_repeats": std,
            "parent_spread_ms": float(max(std) - min(std))}
+    if has_gen:
+        out.update(parent_ms_per_step=float(np.median(gen)), parent_ms_per_step_repeats=gen,
+                   parent_gen_spread_ms=float(max(gen) - min(gen)))
     M.close()
     if out_dir:
         p = os.path.join(out_dir, "lobpcg_gen.json")
@@ -154,10 +165,13 @@ def parent(lib_path, out_dir, hier):
         if "lobpcg_ms_per_step" in res:
             res["standard_step_within_parent_spread"] = bool(
                 res["lobpcg_ms_per_step"] <= out["parent_lobpcg_ms_per_step"] + out["parent_spread_ms"])
+        if has_gen and "ms_per_step" in res:
+            res["generalized_step_within_parent_spread"] = bool(
+                res["ms_per_step"] <= out["parent_ms_per_step"] + out["parent_gen_spread_ms"])
         with open(p, "w") as f:
             json.dump(res, f, indent=1)
         out = res
-    print(json.dumps({k: v for k, v in out.items() if "lobpcg_ms" in k or "parent" in k}, indent=1))
+    print(json.dumps({k: v for k, v in out.items() if "ms_per_step" in k or "parent" in k}, indent=1))
 
 
 def trace(steps, hier):
@@ -171,38 +185,20 @@ def trace(steps, hier):
     print("trace generalized LOBPCG", steps, "steps:", out[4], M.last_lobpcg_info.tolist())
 
 
-# float64 columns of n rows that a kernel reads plus writes per launch at k = 16
+# float64 columns of n rows that a kernel reads plus writes per launch at k = 16 (keys: dev_lobpcg.kernel_key)
 SHAPES = {
-    "k_lob_gram3": 144,      # S, BS and AS read, 48 columns each
-    "k_lob_update3": 240,    # S, AS and BS read (144), X, P, AX, AP, BX, BP written (96)
-    "k_lob_resid_gen": 64,   # X, AX, BX read, R written
-    "k_lob_test_gen": 0,
-    "k_lob_lock": 0,         # writes converged columns only
+    "k_lob_gram<true>": 144,   # S, BS and AS read, 48 columns each
+    "k_lob_update<3>": 240,    # S, AS and BS read (144), X, P, AX, AP, BX, BP written (96)
+    "k_lob_resid<true>": 64,   # X, AX, BX read, R written
+    "k_lob_lock": 0,           # writes converged columns only
     "k_lob_small": 0,
 }
 
 
 def kernel_stats(path, out_dir):
-    out = {}
-    for r in csv.DictReader(open(path)):
-        name = r.get("Name") or r.get("KernelName") or ""
-        m = re.search(r"(k_lob_\w+)", name)
-        if not m or m.group(1) not in SHAPES:
-            continue
-        nbytes = SHAPES[m.group(1)] * COL
-        avg_ns = float(r["AverageNs"])
-        out[m.group(1)] = {"calls": int(r["Calls"]), "avg_us": avg_ns / 1e3, "bytes": nbytes,
-                           "GB_per_s": nbytes / avg_ns if nbytes else None, "us_at_8TB_per_s": nbytes / 8e6 if nbytes else None}
-    print(json.dumps(out, indent=1))
-    if out_dir:
-        p = os.path.join(out_dir, "lobpcg_gen.json")
-        res = json.load(open(p)) if os.path.exists(p) else {}
-        res["kernel_stats_note"] = ("rocprofv3 --kernel-trace --stats of `dev_lobpcg_gen.py --trace-steps` (a run of its own, no "
-                                    "counters); bytes from the shapes at k = 16")
-        res["kernel_stats"] = out
-        with open(p, "w") as f:
-            json.dump(res, f, indent=1)
-    return out
+    from dev_lobpcg import kernel_stats as stats
+
+    return stats(path, out_dir, SHAPES, "lobpcg_gen.json", "dev_lobpcg_gen.py")
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""Generalized LOBPCG for the smallest eigenpairs of A x = lambda B x as Engine::lobpcg_gen_tile runs it, restated in numpy
+"""Generalized LOBPCG for the smallest eigenpairs of A x = lambda B x as Engine::lobpcg_tile<true> runs it, restated in numpy
 around a solve(r) callback in the order of operations of the device, the mass matrices and the inputs the GPU tests use
 (test_lobpcg_gen_host.py pins them on the CPU, test_gpu_lobpcg_gen.py holds the driver against them).  numpy / scipy only.
 
