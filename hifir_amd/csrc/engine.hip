@@ -553,8 +553,29 @@ class Engine : public EngineBase {
   // nsp_on and nsp_k > 0 exclude each other.  (Twin engines never filter: solve_dev filters after their join.)
   int nsp_k = 0, nsp_kp = 0;
   DevBuf nsp_Q, nsp_cpart, nsp_C;
-  DevBuf gm_Q, gm_Z, gm_alpha;  // GMRES: Krylov basis, per-column coefficients (its work vectors: kr_vec)
+  DevBuf gm_Q, gm_Z;  // GMRES: Krylov basis, flexible: the preconditioned vectors (its work vectors: kr_vec, its scalars: kr_state)
   int64_t ir_cols = 0;
+
+  // Every read-back of the engine's own (counters, flags, norms, small matrices; not the callers' arrays, which the host
+  // entries copy under StreamWait or staged): `count` values of V from `dev` on `stream` into the one pinned buffer, waited
+  // for before the return.  The buffer grows on demand and is freed by ~Engine only, so no copy outlives its destination
+  // whichever call throws.  The pointer holds until the next read_back.
+  void *rb_pin = nullptr;
+  size_t rb_cap = 0;
+  template <class V>
+  const V *read_back(const void *dev, size_t count) {
+    const size_t bytes = count * sizeof(V);
+    if (rb_cap < bytes) {
+      if (rb_pin) HIP_OK(hipHostFree(rb_pin));
+      rb_pin = nullptr, rb_cap = 0;
+      const size_t cap = std::max<size_t>(bytes, 4096);
+      HIP_OK(hipHostMalloc(&rb_pin, cap, hipHostMallocDefault));
+      rb_cap = cap;
+    }
+    HIP_OK(hipMemcpyAsync(rb_pin, dev, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return (const V *)rb_pin;
+  }
 
   // Import and host-side analysis (CCS -> CSR, level schedules, dense QRCP) need no GPU; the
   // device is bound in finalize(), and every compute entry point requires a finalized handle.
@@ -587,8 +608,7 @@ class Engine : public EngineBase {
     // nothing of this handle may still be in flight when its graphs, events, streams and pinned buffers go (the runtime
     // completes asynchronous work on threads of its own; see DESIGN 8 on the host copy that changed twice in four rounds)
     if (stream && !is_twin) (void)hipDeviceSynchronize();
-    if (gm_ctl_host) (void)hipHostFree(gm_ctl_host);
-    if (kr_pin) (void)hipHostFree(kr_pin);
+    if (rb_pin) (void)hipHostFree(rb_pin);
 #ifdef HIFAMD_CSPROBE
     csprobe_dump();
 #endif
@@ -980,9 +1000,7 @@ class Engine : public EngineBase {
                            dg.as<unsigned long long>() + q0);
       }
       HIP_OK(hipGetLastError());
-      std::vector<unsigned long long> gbits(nblk);
-      HIP_OK(hipMemcpyAsync(gbits.data(), dg.p, dg.bytes, hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
+      const unsigned long long *gbits = read_back<unsigned long long>(dg.p, nblk);
       for (size_t q = 0; q < nblk; ++q) {
         double g;
         std::memcpy(&g, &gbits[q], 8);
@@ -2601,9 +2619,8 @@ class Engine : public EngineBase {
     hipLaunchKernelGGL((k_nsp_coef<D, kNspMax>), dim3(kCgBlocks), dim3(256), 0, stream, n, kNspMax, V, (int64_t)kNspMax, V, part);
     hipLaunchKernelGGL((k_nsp_finish<D>), dim3(kNspMax), dim3(1024), 0, stream, (const D *)part, C);
     HIP_OK(hipGetLastError());
-    G.resize((size_t)kNspMax * 64);
-    HIP_OK(hipMemcpyAsync(G.data(), C, G.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
+    const T *g = read_back<T>(C, (size_t)kNspMax * 64);
+    G.assign(g, g + (size_t)kNspMax * 64);
   }
   // V <- V M for a host 16 x 16 row-major M (the stream is idle when M's device copy is overwritten: nsp_gram synchronized)
   void nsp_rmul(D *V, const std::vector<T> &M, D *dM) {
@@ -2876,13 +2893,11 @@ class Engine : public EngineBase {
     out.assign((size_t)nrhs, 0.0);
     const int nblk = 512;
     if (ir_part.bytes < (size_t)nblk * 64 * sizeof(double)) ir_part.alloc((size_t)nblk * 64 * sizeof(double));
-    std::vector<double> part((size_t)nblk * 64);
     for (int64_t c0 = 0; c0 < nrhs; c0 += 64) {
       const int nc = (int)std::min<int64_t>(64, nrhs - c0);
       hipLaunchKernelGGL((k_colnorm2_partial<D>), dim3(nblk), dim3(256), 0, stream, n, nc, x + c0, ldx,
                          ir_part.as<double>());
-      HIP_OK(hipMemcpyAsync(part.data(), ir_part.p, (size_t)nblk * nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
+      const double *part = read_back<double>(ir_part.p, (size_t)nblk * nc);
       for (int c = 0; c < nc; ++c) {
         double tot = 0.0;
         for (int b = 0; b < nblk; ++b) tot += part[(size_t)b * nc + c];
@@ -2939,16 +2954,12 @@ class Engine : public EngineBase {
     for (int64_t c = 0; c < nrhs; ++c)
       if (bnorm[(size_t)c] == 0.0) active[(size_t)c] = 0;  // :134-137: x = 0, (0, 0)
     vec_op(1, n, nrhs, r, nrhs, dB, ldb, nullptr, 0);
-    DevBuf mask;
-    mask.alloc((size_t)nrhs * sizeof(int));
-    std::vector<int> hmask((size_t)nrhs);
     int nactive = 0;
     for (char a : active) nactive += a;
     while (nactive > 0) {
       solve_dev(r, nrhs, xk, nrhs, nrhs, rank, nullptr);  // xk = M^{-1} r
-      for (int64_t c = 0; c < nrhs; ++c) hmask[(size_t)c] = active[(size_t)c];
-      HIP_OK(hipMemcpyAsync(mask.p, hmask.data(), (size_t)nrhs * sizeof(int), hipMemcpyHostToDevice, stream));
-      launch_masked_add(n, nrhs, dX, ldx, xk, nrhs, mask.as<int>());  // x += xk on active columns
+      const int *mask = column_mask((size_t)nrhs, [&](size_t c) { return active[c] != 0; });
+      launch_masked_add(n, nrhs, dX, ldx, xk, nrhs, mask);  // x += xk on active columns
       for (int64_t c = 0; c < nrhs; ++c)
         if (active[(size_t)c] && ++iters[(size_t)c] >= nirs) {
           flag[(size_t)c] = -1;
@@ -2978,6 +2989,19 @@ class Engine : public EngineBase {
       for (int64_t c = 0; c < nrhs; ++c) ir_status[2 * c] = iters[(size_t)c], ir_status[2 * c + 1] = flag[(size_t)c];
   }
 
+  // The column mask of the two refinement drivers (bounded refinement, GMRES-IR): mask[c] = pred(c) for c < nc, enqueued
+  // for the launch that follows.  The source is pageable on purpose: the copy has read it when the call returns, so the
+  // next mask may overwrite it at once.
+  DevBuf ir_mask;
+  std::vector<int> ir_hmask;
+  template <class Pred>
+  const int *column_mask(size_t nc, Pred pred) {
+    if (ir_mask.bytes < nc * sizeof(int)) ir_mask.alloc(nc * sizeof(int));
+    ir_hmask.resize(nc);
+    for (size_t c = 0; c < nc; ++c) ir_hmask[c] = pred(c) ? 1 : 0;
+    HIP_OK(hipMemcpyAsync(ir_mask.p, ir_hmask.data(), nc * sizeof(int), hipMemcpyHostToDevice, stream));
+    return ir_mask.as<int>();
+  }
   // masked axpy of the bounded IR variant: where mask[c], y[:, c] += x[:, c]
   void launch_masked_add(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
     hipLaunchKernelGGL((k_masked_add<D>), dim3(vec_grid(n * nrhs)), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
@@ -2992,60 +3016,62 @@ class Engine : public EngineBase {
   // ---- what the lock-step Krylov solvers share -------------------------------------------------------
   // The [n][64] work vectors of all of them: a tile asks for the first k (block GCR 1, GMRES 2, PCG and block CG 4, BiCGSTAB 5, symmetric QMR 7,
   // IDR(s) 2 s + 4), each grown to the tile's size and never shrunk.  One tile owns them from its first launch to its last read-back.
-  // That holds because no solver runs inside another one's tile: the null-space search calls gmres_dev between its own
-  // local blocks, flexible GMRES calls the refinement (ir_r, ir_xk) and the projected PCG / QMR call apply_nsp
-  // (nsp_cpart, nsp_C); none of these takes a pool vector.  Keep it so when adding a solver.
+  // The same holds for the tile's scalars (kr_state) and for what read_back last returned.  It holds because no solver
+  // runs inside another one's tile: the null-space search calls gmres_dev between its own local blocks, GMRES-IR calls
+  // it between its residual (ir_r, ir_xk, gi_d) and its masked update with the bookkeeping on the host, and both copy
+  // what they read back (col_norms, nsp_gram) into vectors of their own before the next call.  Flexible GMRES, the one
+  // solver that calls out of a tile, calls the unbounded refinement (ir_r, ir_xk), which reads nothing back, and keeps
+  // no read_back pointer across it; the projected PCG / QMR call apply_nsp (nsp_cpart, nsp_C).  None of these takes a
+  // pool vector, the state block or a pointer into the pinned buffer.  Keep it so when adding a solver.
   DevBuf kr_vec[2 * kIdrMax + 4];
   void krylov_vectors(int k, size_t bytes) {
     for (int i = 0; i < k; ++i)
       if (kr_vec[i].bytes < bytes) kr_vec[i].alloc(bytes);
   }
 
-  // The per-column scalars of PCG, BiCGSTAB and symmetric QMR in one zeroed block: the [64] slots of D, those of double,
-  // then iter | flag | active | ctl.  One pinned buffer takes the read-backs: [0] active columns, [1, 65) iterations,
-  // [65, 129) flags.
+  // The per-column scalars of every lock-step solver in one zeroed block: the slots of D, those of double, then
+  // iter | flag | active | ctl and the solver's further int slots.  A slot is `rows` rows of [64] (IDR(s) keeps an s x s
+  // matrix per column; GMRES indexes its slots [column][restart] and only needs the room).
+  template <class V>
+  struct Slot {
+    V **p;
+    int rows;
+    Slot(V **p_, int rows_ = 1) : p(p_), rows(rows_) {}
+  };
   DevBuf kr_state;
-  int *kr_pin = nullptr;
-  void krylov_state(KrylovState &S, std::initializer_list<D **> ds, std::initializer_list<double **> rs, double rtol, int maxit) {
-    std::vector<std::pair<D **, int>> rows;
-    for (D **slot : ds) rows.push_back({slot, 1});
-    krylov_state(S, rows, rs, rtol, maxit);
-  }
-  // (the same with slots of several [64] rows each: IDR(s) keeps an s x s matrix per column)
-  void krylov_state(KrylovState &S, const std::vector<std::pair<D **, int>> &ds, std::initializer_list<double **> rs, double rtol,
-                    int maxit) {
-    size_t nd = 0;
-    for (const auto &slot : ds) nd += (size_t)slot.second;
-    const size_t o_re = nd * 64 * sizeof(D), o_int = o_re + rs.size() * 64 * sizeof(double),
-                 bytes = o_int + (3 * 64 + 4) * sizeof(int);
-    if (!kr_pin) HIP_OK(hipHostMalloc((void **)&kr_pin, 129 * sizeof(int), hipHostMallocDefault));
+  void krylov_state(KrylovState &S, std::initializer_list<Slot<D>> ds, std::initializer_list<Slot<double>> rs, double rtol, int maxit,
+                    std::initializer_list<int **> is = {}) {
+    size_t nd = 0, nr = 0;
+    for (const auto &slot : ds) nd += (size_t)slot.rows;
+    for (const auto &slot : rs) nr += (size_t)slot.rows;
+    const size_t o_re = nd * 64 * sizeof(D), o_int = o_re + nr * 64 * sizeof(double),
+                 bytes = o_int + ((3 + is.size()) * 64 + 4) * sizeof(int);
     if (kr_state.bytes < bytes) kr_state.alloc(bytes);
     HIP_OK(hipMemsetAsync(kr_state.p, 0, bytes, stream));
     char *b = kr_state.as<char>();
     D *d = (D *)b;
-    for (const auto &slot : ds) *slot.first = d, d += 64 * (size_t)slot.second;
+    for (const auto &slot : ds) *slot.p = d, d += 64 * (size_t)slot.rows;
     double *r = (double *)(b + o_re);
-    for (double **slot : rs) *slot = r, r += 64;
+    for (const auto &slot : rs) *slot.p = r, r += 64 * (size_t)slot.rows;
     int *ib = (int *)(b + o_int);
     S.iter = ib;
     S.flag = ib + 64;
     S.active = ib + 128;
     S.ctl = ib + 192;
+    ib += 196;
+    for (int **slot : is) *slot = ib, ib += 64;
     S.maxit = maxit;
     S.rtol = rtol;
   }
-  int krylov_active(const KrylovState &S) {
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return kr_pin[0];
-  }
+  // the four ctl ints of a tile: [0] columns still active, the rest the solver's own (valid until the next read_back)
+  const int *krylov_ctl(const KrylovState &S) { return read_back<int>(S.ctl, 4); }
+  int krylov_active(const KrylovState &S) { return krylov_ctl(S)[0]; }
   void krylov_result(const KrylovState &S, int nc, int *flags, int *iters) {
-    HIP_OK(hipMemcpyAsync(kr_pin + 1, S.iter, 128 * sizeof(int), hipMemcpyDeviceToHost, stream));  // iter, flag
-    HIP_OK(hipStreamSynchronize(stream));
+    const int *st = read_back<int>(S.iter, 128);  // iter | flag
     check_device_error();
     for (int c = 0; c < nc; ++c) {
-      if (iters) iters[c] = kr_pin[1 + c];
-      if (flags) flags[c] = kr_pin[65 + c];
+      if (iters) iters[c] = st[c];
+      if (flags) flags[c] = st[64 + c];
     }
   }
 
@@ -3093,9 +3119,8 @@ class Engine : public EngineBase {
   }
   // the tile's rank after its start and during its last step (ctl[1..2]) -> ranks[0..1] (may be null)
   void block_ranks(const KrylovState &S, int *ranks) {
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    if (ranks) ranks[0] = kr_pin[1], ranks[1] = kr_pin[2];
+    const int *ctl = krylov_ctl(S);
+    if (ranks) ranks[0] = ctl[1], ranks[1] = ctl[2];
   }
   void block_check(int block, double deftol, int restart = 1) {
     if (block < 1 || block > 64) throw Error(HIFAMD_MISMATCHED_SIZES, "need 1 <= block <= 64");
@@ -3114,49 +3139,13 @@ class Engine : public EngineBase {
   // The reference's driver (examples/advanced/gmres.hpp:19-123: MGS Arnoldi, Givens rotations, relative
   // residual |y_{j+1}| / ||b||, flags 0 converged / 1 stagnated / 2 reached maxit) run for up to 64
   // columns in lock step.  Everything lives in HBM: the vectors, the Krylov basis, AND the per-column
-  // scalars (Hessenberg column, rotations, residuals, iteration counts, flags: GmState, kernels.hip.hpp).
+  // scalars (Hessenberg column, rotations, residuals, iteration counts, flags: GmState, kernels.hip.hpp,
+  // carved out of kr_state like every lock-step solver's).
   // One inner step = one batched apply + one SpMM + j+2 fused axpy/dot passes (k_gm_step) each followed
-  // by a one-workgroup finishing kernel, and ONE 12-byte read-back (how many columns are still active).
+  // by a one-workgroup finishing kernel, and ONE read-back of ctl (how many columns are still active).
   // A column that leaves the inner loop keeps a zero basis vector.  Real and complex handles (Hermitian
   // inner product; for real data identical to the reference's hif::inner).
   static constexpr int kGmBlocks = 1024;
-  GmState<D> gm_state(int nc, int restart, int maxit, double rtol) {
-    const size_t rs = (size_t)restart;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-      const size_t o = off;
-      off += (bytes + 255) & ~(size_t)255;
-      return o;
-    };
-    const size_t o_w2 = take(nc * rs * sizeof(D)), o_jc = take(nc * rs * sizeof(D)), o_js = take(nc * rs * sizeof(double)),
-                 o_y = take(nc * (rs + 1) * sizeof(D)), o_R = take(nc * rs * rs * sizeof(D)),
-                 o_res = take(nc * sizeof(double)), o_b0 = take(nc * sizeof(double)), o_int = take(6 * (size_t)nc * sizeof(int)),
-                 o_al = take(nc * sizeof(D)), o_ctl = take(4 * sizeof(int));
-    if (gm_alpha.bytes < off) gm_alpha.alloc(off);
-    HIP_OK(hipMemsetAsync(gm_alpha.p, 0, off, stream));
-    char *b = gm_alpha.as<char>();
-    GmState<D> S;
-    S.w2 = (D *)(b + o_w2);
-    S.Jc = (D *)(b + o_jc);
-    S.Js = (double *)(b + o_js);
-    S.y = (D *)(b + o_y);
-    S.R = (D *)(b + o_R);
-    S.resid = (double *)(b + o_res);
-    S.beta0 = (double *)(b + o_b0);
-    int *ib = (int *)(b + o_int);
-    S.iter = ib;
-    S.flag = ib + nc;
-    S.active = ib + 2 * nc;
-    S.jfin = ib + 3 * nc;
-    S.done = ib + 4 * nc;
-    S.sweeps = ib + 5 * nc;
-    S.alpha = (D *)(b + o_al);
-    S.ctl = (int *)(b + o_ctl);
-    S.restart = restart;
-    S.maxit = maxit;
-    S.rtol = rtol;
-    return S;
-  }
   // v -= h q_prev (h = S.alpha, from the previous finish) fused with the reduction against q (nullptr: |v|^2)
   void gm_step(int64_t n, int nc, D *v, const D *qp, const D *q, const GmState<D> &S) {
     const size_t need = (size_t)kGmBlocks * kGmVals * 64 * sizeof(D);  // (what k_gm_block needs: no reallocation between the passes)
@@ -3181,13 +3170,6 @@ class Engine : public EngineBase {
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL((k_gm_colop<D>), dim3((unsigned)g), dim3(256), 0, stream, op, n, nc, y, ldy, x, ldx, (const D *)S.alpha);
   }
-  int *gm_ctl_host = nullptr;  // pinned: [0] active columns [1] max jfin [2] columns not done
-  void gm_read_ctl(const GmState<D> &S) {
-    if (!gm_ctl_host) HIP_OK(hipHostMalloc((void **)&gm_ctl_host, 4 * sizeof(int), hipHostMallocDefault));
-    HIP_OK(hipMemcpyAsync(gm_ctl_host, S.ctl, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-  }
-
   void gmres_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, int restart, double rtol, int maxit,
                   int64_t rank, int *flags, int *iters, bool flexible, int *sweeps) {
     const int64_t n = lv[0]->n;
@@ -3199,16 +3181,21 @@ class Engine : public EngineBase {
     D *v = kr_vec[0].as<D>(), *w = kr_vec[1].as<D>(), *Q = gm_Q.as<D>(), *Z = gm_Z.as<D>();
     auto Qk = [&](int k) { return Q + (size_t)k * (size_t)n * nc; };
     auto Zk = [&](int k) { return Z + (size_t)k * (size_t)n * nc; };
-    const GmState<D> S = gm_state(nc, restart, maxit, rtol);
+    GmState<D> S;
+    const size_t rs = (size_t)restart;
+    auto rows = [nc](size_t per_column) { return (int)((nc * per_column + 63) / 64); };  // [nc][per_column] in rows of [64]
+    krylov_state(S, {{&S.w2, rows(rs)}, {&S.Jc, rows(rs)}, {&S.y, rows(rs + 1)}, {&S.R, rows(rs * rs)}, &S.alpha},
+                 {{&S.Js, rows(rs)}, &S.resid, &S.bnorm}, rtol, maxit, {&S.jfin, &S.done, &S.sweeps});
+    S.restart = restart;
     int64_t grid = (n * nc + 255) / 256;
     if (grid > 4096) grid = 4096;
     vec_op(1, n, nc, v, nc, dB, ldb, nullptr, 0);  // v = b (contiguous copy: the first residual, :52)
     gm_step(n, nc, v, nullptr, nullptr, S);
     gm_finish(nc, 3, 0, 0, S);                     // beta0, quick return (:30-36)
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0  (:33-34)
-    gm_read_ctl(S);
+    int not_done = krylov_ctl(S)[2];
     const int max_outer = (maxit + restart - 1) / restart;  // :43
-    for (int outer = 0; outer < max_outer && gm_ctl_host[2] > 0; ++outer) {
+    for (int outer = 0; outer < max_outer && not_done > 0; ++outer) {
       if (outer) {
         resid_dev(dB, ldb, (const D *)dX, ldx, v, nc, nc, opt.resid_mode);  // v = b - A x  (:48-50)
         gm_step(n, nc, v, nullptr, nullptr, S);
@@ -3240,13 +3227,13 @@ class Engine : public EngineBase {
         gm_block(n, nc, v, Qk(kl), ml, nullptr, 0, S);  // the last block's update + |v|^2  (:65,67)
         gm_finish(nc, 1, j, flexible ? nirs : 0, S);  // rotations, residual, stopping rules  (:73-103)
         if (j + 1 < restart) gm_colop(1, n, nc, Qk(j + 1), nc, v, nc, S);  // :69-70
-        gm_read_ctl(S);
-        if (gm_ctl_host[0] == 0) break;
+        if (krylov_active(S) == 0) break;
         ++j;
       }
       hipLaunchKernelGGL((k_gm_backsolve<D>), dim3(1), dim3(64), 0, stream, nc, S);  // :106-110, :120
-      gm_read_ctl(S);
-      const int jmax = gm_ctl_host[1];
+      const int *ctl = krylov_ctl(S);
+      const int jmax = ctl[1];
+      not_done = ctl[2];
       if (flexible) {  // x += Z y  (:214-218)
         hipLaunchKernelGGL((k_gm_combine<D>), dim3((unsigned)grid), dim3(256), 0, stream, n, nc, dX, ldx, 1, (const D *)Z, jmax, S);
       } else {
@@ -3255,15 +3242,8 @@ class Engine : public EngineBase {
         gm_colop(0, n, nc, dX, ldx, (const D *)w, nc, S);       // x += w  (:119; alpha = 1 for the columns that took part)
       }
     }
-    std::vector<int> st((size_t)6 * nc);
-    HIP_OK(hipMemcpyAsync(st.data(), S.iter, st.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    check_device_error();
-    for (int c = 0; c < nc; ++c) {
-      if (iters) iters[c] = st[(size_t)c];
-      if (flags) flags[c] = st[(size_t)nc + c];
-      if (sweeps) sweeps[c] = st[(size_t)5 * nc + c];
-    }
+    krylov_result(S, nc, flags, iters);
+    if (sweeps) std::copy_n(read_back<int>(S.sweeps, (size_t)nc), nc, sweeps);
   }
 
   void gmres_check(int restart, int maxit, double rtol) {
@@ -3299,7 +3279,7 @@ class Engine : public EngineBase {
   // column norms) per outer step.  A zero column: x = 0, flag 0, 0 steps; a column whose norm or residual is not finite:
   // flag 1 at once.  The restart residuals of the inner GMRES follow the handle's mode.  No pool vector is held while
   // gmres_dev runs (see kr_vec): r lives in ir_r, the previous iterate in ir_xk, the correction in gi_d.
-  DevBuf gi_d, gi_mask;
+  DevBuf gi_d;
   void launch_masked_set(int64_t n, int64_t nrhs, D *y, int64_t ldy, const D *x, int64_t ldx, const int *mask) {
     hipLaunchKernelGGL((k_masked_set<D>), dim3(vec_grid(n * nrhs)), dim3(256), 0, stream, n, (int)nrhs, y, ldy, x, ldx, mask);
   }
@@ -3314,17 +3294,12 @@ class Engine : public EngineBase {
     if (ir_r.bytes < vec) ir_r.alloc(vec);
     if (ir_xk.bytes < vec) ir_xk.alloc(vec);
     if (gi_d.bytes < vec) gi_d.alloc(vec);
-    if (!gi_mask.p) gi_mask.alloc(64 * sizeof(int));
     D *r = ir_r.as<D>(), *xk = ir_xk.as<D>(), *d = gi_d.as<D>();
     StreamWait wait{stream};
     const size_t w = (size_t)nc;
     std::vector<double> bn, rn, res(w, 0.0), prev(w, 0.0);
-    std::vector<int> fl(w, 0), nout(w, 0), nit(w, 0), gfl((size_t)W), git((size_t)W), hmask(w);
+    std::vector<int> fl(w, 0), nout(w, 0), nit(w, 0), gfl((size_t)W), git((size_t)W);
     std::vector<char> active(w, 1);
-    auto mask_of = [&](auto pred) {  // (a pageable source: the copy has read it when the call returns)
-      for (size_t c = 0; c < w; ++c) hmask[c] = pred(c) ? 1 : 0;
-      HIP_OK(hipMemcpyAsync(gi_mask.p, hmask.data(), w * sizeof(int), hipMemcpyHostToDevice, stream));
-    };
     vec_op(0, n, nc, dX, ldx, nullptr, 0, nullptr, 0);  // x = 0
     HIP_OK(hipMemsetAsync(r, 0, vec, stream));
     vec_op(1, n, nc, r, W, dB, ldb, nullptr, 0);  // r = b
@@ -3359,18 +3334,17 @@ class Engine : public EngineBase {
           fl[c] = 2, active[c] = 0;
       }
       if (nback) {
-        mask_of([&](size_t c) { return back[c] != 0; });
-        launch_masked_set(n, nc, dX, ldx, (const D *)xk, nc, gi_mask.as<int>());
+        launch_masked_set(n, nc, dX, ldx, (const D *)xk, nc, column_mask(w, [&](size_t c) { return back[c] != 0; }));
       }
       nactive = 0;
       for (char a : active) nactive += a;
       if (!nactive) break;
-      mask_of([&](size_t c) { return !active[c]; });
-      launch_masked_set(n, nc, r, W, (const D *)nullptr, 0, gi_mask.as<int>());  // the frozen columns take no part
+      // the frozen columns take no part
+      launch_masked_set(n, nc, r, W, (const D *)nullptr, 0, column_mask(w, [&](size_t c) { return !active[c]; }));
       gmres_dev((const D *)r, W, d, W, W, restart, inner_rtol, inner_maxit, rank, gfl.data(), git.data());
       vec_op(1, n, nc, xk, nc, (const D *)dX, ldx, nullptr, 0);  // the iterate of this step, should the next be no better
-      mask_of([&](size_t c) { return active[c] != 0; });
-      launch_masked_add(n, nc, dX, ldx, (const D *)d, W, gi_mask.as<int>());  // x += d on the active columns
+      // x += d on the active columns
+      launch_masked_add(n, nc, dX, ldx, (const D *)d, W, column_mask(w, [&](size_t c) { return active[c] != 0; }));
       HIP_OK(hipGetLastError());
       for (size_t c = 0; c < w; ++c)
         if (active[c]) ++nout[c], nit[c] += git[c];
@@ -3410,7 +3384,7 @@ class Engine : public EngineBase {
   // x += alpha p, r -= alpha q, stop on ||r|| / ||b|| <= rtol, z = M^{-1} r, rho' = r^H z, p = z + (rho' / rho) p.
   // Up to 64 columns in lock step: one batched apply, one SpMM and four fused vector passes (k_cg_*) per step, each
   // pass followed by a one-workgroup finishing kernel; the per-column scalars live in HBM (CgState) and the host reads
-  // one integer per step (how many columns are still active) through a pinned buffer of the engine.  Only for a
+  // ctl once per step (how many columns are still active) through the pinned buffer of the engine.  Only for a
   // Hermitian M^{-1} (import.hpp check_hermitian); flags 0 converged / 1 breakdown / 2 reached maxit.
   void pcg_tile(const D *dB, int64_t ldb, D *dX, int64_t ldx, int nc, double rtol, int maxit, int64_t rank, int *flags,
                 int *iters) {
@@ -3620,10 +3594,9 @@ class Engine : public EngineBase {
                          (const D *)S.CC);
     };
     auto refused = [&] {  // the start's verdict
-      HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-      HIP_OK(hipStreamSynchronize(stream));
+      const int verdict = krylov_ctl(S)[3];
       check_device_error();
-      if (kr_pin[3] >= 1 && kr_pin[3] <= 3) throw Error(HIFAMD_BAD_PREC, refusal[GEN][kr_pin[3] - 1]);
+      if (verdict >= 1 && verdict <= 3) throw Error(HIFAMD_BAD_PREC, refusal[GEN][verdict - 1]);
     };
     HIP_OK(hipMemsetAsync(Sb, 0, blk, stream));
     HIP_OK(hipMemsetAsync(ASb, 0, blk, stream));
@@ -3663,15 +3636,13 @@ class Engine : public EngineBase {
     vec_op(1, n, k, dX, ldx, (const D *)Sb, s, nullptr, 0);
     int its[64];
     krylov_result(S, k, flags, its);
-    std::vector<double> out(128);
-    HIP_OK(hipMemcpyAsync(kr_pin, S.ctl, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipMemcpyAsync(out.data(), S.lam, 128 * sizeof(double), hipMemcpyDeviceToHost, stream));  // lam | res
-    HIP_OK(hipStreamSynchronize(stream));
+    const int *ctl = krylov_ctl(S);
+    if (info3) info3[0] = its[0], info3[1] = ctl[1], info3[2] = ctl[2];
+    const double *out = read_back<double>(S.lam, 128);  // lam | res (ctl is gone with this read)
     for (int c = 0; c < k; ++c) {
-      if (lambda) lambda[c] = out[(size_t)c];
-      if (res) res[c] = out[64 + (size_t)c];
+      if (lambda) lambda[c] = out[c];
+      if (res) res[c] = out[64 + c];
     }
-    if (info3) info3[0] = its[0], info3[1] = kr_pin[1], info3[2] = kr_pin[2];
   }
 
   // gen: the generalized problem's checks: the mass matrix directly after the matrix, no filter of any kind

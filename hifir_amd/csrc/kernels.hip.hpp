@@ -1900,7 +1900,7 @@ __global__ void __launch_bounds__(256) k_sub_colmean(int64_t r0, int64_t r1, int
 // ---------------------------------------------------------------------------------------------
 // Device-resident Arnoldi process of the batched GMRES driver (examples/advanced/gmres.hpp:57-103 for up to
 // 64 columns in lock step): the Hessenberg column, the rotations, the residuals and the per-column state
-// (iteration count, flag, active mask) live in HBM; the host sees three integers per inner step.
+// (iteration count, flag, active mask) live in HBM; the host sees the three ctl counters per inner step.
 // The inner product is the Hermitian one, h = sum conj(q_i) v_i (for real data this IS hif::inner,
 // utils/math.hpp:83; for complex data the example's sum conj(v_i) q_i would not orthogonalize).
 // ---------------------------------------------------------------------------------------------
@@ -1916,18 +1916,16 @@ __device__ __forceinline__ bool viszero(double a) { return a == 0.0; }
 __device__ __forceinline__ bool viszero(cplx a) { return a.x == 0.0 && a.y == 0.0; }
 
 template <class T>
-struct GmState {
+struct GmState : KrylovState {  // bnorm: ||b|| (beta0, :30); ctl: [0] columns still active after the step  [1] max jfin  [2] columns not done
   T *w2;          // [nc][restart]           Hessenberg column of the running step (gmres.hpp:64,73-78)
   T *Jc;          // [nc][restart]           J(:,0)
   double *Js;     // [nc][restart]           J(:,1) (real)
   T *y;           // [nc][restart + 1]
   T *R;           // [nc][restart][restart]  column j of column c at R + (c * restart + j) * restart
-  double *resid, *beta0;
-  int *iter, *flag, *active, *jfin, *done, *sweeps;
+  double *resid;
+  int *jfin, *done, *sweeps;
   T *alpha;       // [nc] coefficient of the next column operation
-  int *ctl;       // [0] columns still active after the step  [1] max jfin  [2] columns not done
-  int restart, maxit;
-  double rtol;
+  int restart;
 };
 
 // One modified-Gram-Schmidt step, fused: first v -= h_prev q_prev (the axpy of the PREVIOUS step, :65), then the
@@ -2101,7 +2099,7 @@ __global__ void __launch_bounds__(256) k_gm_finish(const T *__restrict__ partial
       S.alpha[c] = tot;
     } else if (mode == 3) {
       const double b0 = sqrt(vreal(tot));
-      S.beta0[c] = b0;
+      S.bnorm[c] = b0;
       S.done[c] = (b0 == 0.0);
       S.resid[c] = 1.0;
       S.iter[c] = 0;
@@ -2143,7 +2141,7 @@ __global__ void __launch_bounds__(256) k_gm_finish(const T *__restrict__ partial
         wc[j] = vfromreal(rho, T());
         for (int i = 0; i <= j; ++i) Rc[(size_t)j * rs + i] = wc[i];  // :85
         const double resid_prev = S.resid[c];
-        const double resid = vabs1(yc[j + 1]) / S.beta0[c];  // :89
+        const double resid = vabs1(yc[j + 1]) / S.bnorm[c];  // :89
         S.resid[c] = resid;
         bool brk = false;
         if (resid >= resid_prev * (1.0 - 1e-8)) {  // :90-93
