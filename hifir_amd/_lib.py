@@ -83,6 +83,13 @@ SIGNATURES = {
     "hifamd_lobpcg_gen": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "hifamd_lobpcg_gen_dev": (_int, [_vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp, _i64, _vp, _vp,
                                      _vp]),
+    "hifamd_eig_project": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "hifamd_eig_project_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _vp, _i64]),
+    "hifamd_eigs": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp,
+                           _i64, _vp, _vp, _vp]),
+    "hifamd_eigs_dev": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, C.c_uint64, _dbl, _dbl, _int, _i64, _vp, _vp,
+                               _i64, _vp, _vp, _vp]),
+    "hifamd_eigs_sweeps": (_int, [_vp, _vp, _int]),
     "hifamd_bicgstab_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_bicgstab_batch_dev": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _dbl, _int, _i64, _vp, _vp]),
     "hifamd_idrs_batch": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, C.c_uint64, _dbl, _int, _i64, _vp, _vp]),

@@ -3552,9 +3552,16 @@ class Engine : public EngineBase {
   // of the pair (X is B-normalized, so ||x_j|| is in the scale).  No filter of any kind (lobpcg_check).  With B = I given
   // explicitly BS is a bitwise copy of S and every iterate is the standard problem's, bit for bit, until the two stopping
   // tests differ.
+  // lock (m > 0): the constraint block of the locked sweeps (eigs_dev): X is projected once, behind the start's filter and in
+  // front of BX = B X, and W once per step, behind W = M^{-1} R and in front of AW = A W, both with P = I - Y (BY)^H
+  // (eig_project).  The converged columns of W are exact zeros and stay exact zeros.  m = 0 launches nothing.
+  struct EigLock {
+    const D *Y = nullptr, *BY = nullptr;  // [n][kEigMaxM]; BY == Y on the standard problem
+    int m = 0;
+  };
   template <bool GEN>
   void lobpcg_tile(const D *dX0, int64_t ldx0, uint64_t seed, int k, int nev, double tol, double deftol, int maxit, int64_t rank,
-                   D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3) {
+                   D *dX, int64_t ldx, double *lambda, double *res, int *flags, int *info3, const EigLock &lock = EigLock()) {
     static const char *const refusal[2][3] = {
       {"LOBPCG: the start block is rank deficient", "LOBPCG: the start block is not finite",
        "LOBPCG: X^H A X of the start block is not finite, or its eigendecomposition did not end"},
@@ -3608,6 +3615,7 @@ class Engine : public EngineBase {
       vec_op(1, n, k, Sb, s, (const D *)R, k, nullptr, 0);
     }
     if (!GEN && nsp_k > 0) apply_nsp(Sb, s, k, stream);  // on the complement of span(Q)
+    if (lock.m > 0) eig_project(lock.m, lock.Y, lock.BY, kEigMaxM, k, Sb, s, pt);
     if (GEN) spmm_launch(Bm, (const D *)Sb, s, BSb, s, k, stream);  // BX = B X
     gram();
     small(0, 0);
@@ -3626,6 +3634,7 @@ class Engine : public EngineBase {
       if (krylov_active(S) == 0) break;
       hipLaunchKernelGGL((k_lob_lock<D>), dim3(vec_grid(n * k)), dim3(256), 0, stream, n, k, R, (const int *)S.active);
       solve_dev((const D *)R, k, Sb + k, s, k, rank, nullptr);  // W = M^{-1} R
+      if (lock.m > 0) eig_project(lock.m, lock.Y, lock.BY, kEigMaxM, k, Sb + k, s, pt);
       spmv_dev((const D *)(Sb + k), s, ASb + k, s, k, nullptr);  // AW = A W
       if (GEN) spmm_launch(Bm, (const D *)(Sb + k), s, BSb + k, s, k, stream);  // BW = B W
       gram();
@@ -3647,12 +3656,19 @@ class Engine : public EngineBase {
 
   // gen: the generalized problem's checks: the mass matrix directly after the matrix, no filter of any kind
   void lobpcg_check(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx, bool gen) {
+    lobpcg_args(k, nev, tol, deftol, maxit, ldx0, has_x0, ldx);
+    lobpcg_handle(k, gen);
+  }
+  // (the two halves of lobpcg_check: the arguments come first, then the handle; the locked sweeps put theirs in between)
+  void lobpcg_args(int64_t k, int64_t nev, double tol, double deftol, int maxit, int64_t ldx0, bool has_x0, int64_t ldx) {
     if (k < 1 || k > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= k <= 16");
     if (nev < 1 || nev > k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 1 <= nev <= k");
     if (!(tol > 0.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need tol > 0");
     if (maxit < 1) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need maxit >= 1");
     if (!(deftol > 0.0 && deftol < 1.0)) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: need 0 < deftol < 1");
     if ((has_x0 && ldx0 < k) || ldx < k) throw Error(HIFAMD_MISMATCHED_SIZES, "LOBPCG: row stride smaller than k");
+  }
+  void lobpcg_handle(int64_t k, bool gen) {
     if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
     if (k > std::max<int64_t>(Rmax, max_nrhs))
       throw Error(HIFAMD_MISMATCHED_SIZES, "block wider than the max_nrhs given to hifamd_finalize");
@@ -3690,6 +3706,231 @@ class Engine : public EngineBase {
                flags, info3);
     HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, k * sizeof(T), k * sizeof(T), n, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
+  }
+
+  // ---- the B-orthogonal projector and the locked LOBPCG sweeps (up to 128 eigenpairs) --------------------------------
+  // W <- W - Y C, C = (BY)^H W: Y, BY [n][m] (m <= 128; the same pointer on the standard problem), W [n][kw] (kw <= 16), any
+  // row strides.  k_eig_cgram's kBcgBlocks partials of C go through pt (kBcgBlocks x [128][16]) and are added in block
+  // order; k_eig_cproj subtracts the row-local product.  Three launches, nothing read back.
+  DevBuf eig_C, eig_Y, eig_BY, eig_blk;
+  static constexpr size_t kEigPart = (size_t)kBcgBlocks * kEigMaxM * 16;  // elements of the partials
+  void eig_coeff(int m, const D *BY, int64_t ldby, int kw, const D *W, int64_t ldw, D *pt) {
+    if (eig_C.bytes < (size_t)kEigMaxM * 16 * sizeof(D)) eig_C.alloc((size_t)kEigMaxM * 16 * sizeof(D));
+    const int rows = 16 * ((m + 15) / 16);
+    hipLaunchKernelGGL((k_eig_cgram<D>), dim3(kBcgBlocks), dim3(256), 0, stream, lv[0]->n, m, BY, ldby, kw, W, ldw, pt);
+    hipLaunchKernelGGL((k_eig_csum<D>), dim3((rows * 16 + 255) / 256), dim3(256), 0, stream, (const D *)pt, kBcgBlocks, rows,
+                       eig_C.as<D>());
+  }
+  void eig_project(int m, const D *Y, const D *BY, int64_t ldy, int kw, D *W, int64_t ldw, D *pt) {
+    eig_coeff(m, BY, ldy, kw, (const D *)W, ldw, pt);
+    hipLaunchKernelGGL((k_eig_cproj<D>), dim3(kBcgBlocks), dim3(256), 0, stream, lv[0]->n, m, Y, ldy, kw, W, ldw,
+                       (const D *)eig_C.as<D>());
+    HIP_OK(hipGetLastError());
+  }
+  D *eig_partials() {
+    if (ir_part.bytes < kEigPart * sizeof(D)) ir_part.alloc(kEigPart * sizeof(D));
+    return ir_part.as<D>();
+  }
+  // the [n][128] blocks of the locked vectors and of their images under B: allocated on first use, freed with the engine
+  void eig_blocks(bool y, bool by) {
+    const size_t need = (size_t)lv[0]->n * kEigMaxM * sizeof(D);
+    if (y && eig_Y.bytes < need) eig_Y.alloc(need);
+    if (by && eig_BY.bytes < need) eig_BY.alloc(need);
+  }
+
+  // hifamd_eig_project(_dev): the projector alone.  gen: BY = B Y is formed here (spmm_launch: 64 columns a launch).
+  void eig_project_check(bool gen, int64_t m, int64_t ldy, int64_t kw, int64_t ldw) {
+    if (m < 1 || m > kEigMaxM) throw Error(HIFAMD_MISMATCHED_SIZES, "eig_project: need 1 <= m <= 128");
+    if (kw < 1 || kw > 16) throw Error(HIFAMD_MISMATCHED_SIZES, "eig_project: need 1 <= kw <= 16");
+    if (ldy < m || ldw < kw) throw Error(HIFAMD_MISMATCHED_SIZES, "eig_project: row stride smaller than the block");
+    if (!finalized) throw Error(HIFAMD_BAD_PREC, "hierarchy not finalized (hifamd_finalize)");
+    if (gen && !has_B) throw Error(HIFAMD_BAD_PREC, "the B-orthogonal projector needs the mass matrix (hifamd_set_mass_matrix)");
+  }
+  void eig_project_dev(bool gen, int64_t m, const D *dY, int64_t ldy, int64_t kw, D *dW, int64_t ldw) {
+    eig_project_check(gen, m, ldy, kw, ldw);
+    if (!dY || !dW) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    StreamWait wait{stream};
+    D *pt = eig_partials();
+    if (gen) {
+      eig_blocks(false, true);  // (BY alone: the caller's Y is read where it lies)
+      spmm_launch(Bm, dY, ldy, eig_BY.as<D>(), kEigMaxM, m, stream);
+      eig_coeff((int)m, (const D *)eig_BY.as<D>(), kEigMaxM, (int)kw, (const D *)dW, ldw, pt);
+      hipLaunchKernelGGL((k_eig_cproj<D>), dim3(kBcgBlocks), dim3(256), 0, stream, lv[0]->n, (int)m, dY, ldy, (int)kw, dW, ldw,
+                         (const D *)eig_C.as<D>());
+      HIP_OK(hipGetLastError());
+    } else {
+      eig_project((int)m, dY, dY, ldy, (int)kw, dW, ldw, pt);
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+  }
+  void eig_project_host(bool gen, int64_t m, const T *Y, int64_t ldy, int64_t kw, T *W, int64_t ldw) {
+    eig_project_check(gen, m, ldy, kw, ldw);
+    if (!Y || !W) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t ny = (size_t)n * m * sizeof(T), nw = (size_t)n * kw * sizeof(T);
+    if (stage_r.bytes < ny) stage_r.alloc(ny);
+    if (stage_x.bytes < nw) stage_x.alloc(nw);
+    StreamWait wait{stream};
+    HIP_OK(hipMemcpy2DAsync(stage_r.p, m * sizeof(T), Y, ldy * sizeof(T), m * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    HIP_OK(hipMemcpy2DAsync(stage_x.p, kw * sizeof(T), W, ldw * sizeof(T), kw * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    eig_project_dev(gen, m, (const D *)stage_r.as<D>(), m, kw, stage_x.as<D>(), kw);
+    HIP_OK(hipMemcpy2DAsync(W, ldw * sizeof(T), stage_x.p, kw * sizeof(T), kw * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+
+  // max |Y^H BY - I| of the first m columns of eig_Y / BY, sixteen columns of Y a pass (k_eig_cgram), read back per pass
+  double eig_orthonormality(int m, const D *Y, const D *BY, D *pt) {
+    double worst = 0.0;
+    const int rows = 16 * ((m + 15) / 16);
+    for (int j0 = 0; j0 < m; j0 += 16) {
+      const int kw = std::min(16, m - j0);
+      eig_coeff(m, BY, kEigMaxM, kw, Y + j0, kEigMaxM, pt);
+      HIP_OK(hipGetLastError());
+      const D *Ch = read_back<D>(eig_C.p, (size_t)rows * 16);
+      for (int i = 0; i < m; ++i)
+        for (int j = 0; j < kw; ++j) {
+          const double *z = (const double *)&Ch[i * 16 + j];  // (re | im of a complex handle)
+          const double re = z[0] - (i == j0 + j ? 1.0 : 0.0), im = sizeof(D) > sizeof(double) ? z[sizeof(D) / sizeof(double) - 1] : 0.0;
+          const double d = std::sqrt(re * re + im * im);
+          if (!(d <= worst)) worst = d;  // (a NaN stays)
+        }
+    }
+    return worst;
+  }
+
+  // The locked sweeps: the nev <= 128 - m0 smallest eigenpairs through tiles of k <= 16 candidates, `guard` of them guard
+  // columns.  Y (m0 >= 0 columns, B-orthonormal: checked to 1e-10) seeds the constraint block; every sweep runs the
+  // constrained tile for want = min(nev - L, k - guard) columns, locks the leading run of p converged ones (projected once
+  // more; generalized: their image under B is recomputed) and restarts from the unconverged columns plus p generated ones
+  // (seed + sweep).  Host decisions (lobpcg_small.hpp) only between sweeps.  p = 0 ends the run: the tile's candidates and flags
+  // fill the columns it was asked for, what was never reached stays zero with lambda = NaN and flag 2.
+  // info4: total steps, sweeps, locked, smallest basis rank seen.  eig_sweeps keeps (want, locked, steps) per sweep.
+  std::vector<int> eig_sweeps;
+  void eigs_check(bool gen, int64_t nev, int64_t k, int64_t guard, bool has_y, int64_t ldy, int64_t m0, bool has_x0, int64_t ldx0,
+                  double tol, double deftol, int maxit, int64_t ldx) {
+    const int64_t room = std::max<int64_t>(1, std::min<int64_t>(k, k - guard));
+    lobpcg_args(k, std::max<int64_t>(1, std::min(nev, room)), tol, deftol, maxit, ldx0, has_x0, k);
+    if (const char *bad = lob::sweep_args(nev, k, guard, m0)) throw Error(HIFAMD_MISMATCHED_SIZES, bad);
+    if ((m0 > 0 && ldy < m0) || ldx < nev) throw Error(HIFAMD_MISMATCHED_SIZES, "eigs: row stride smaller than the block");
+    if (m0 > 0 && !has_y) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    lobpcg_handle(k, gen);
+  }
+  template <bool GEN>
+  void eigs_run(int nev, int k, int guard, const D *dY, int64_t ldy, int m0, const D *dX0, int64_t ldx0, uint64_t seed, double tol,
+                double deftol, int maxit, int64_t rank, double *lambda, D *dX, int64_t ldx, double *res, int *flags, int *info4) {
+    const int64_t n = lv[0]->n;
+    StreamWait wait{stream};
+    eig_sweeps.clear();
+    const size_t blk = (size_t)n * lob::kMaxK * sizeof(D);
+    if (eig_blk.bytes < 3 * blk) eig_blk.alloc(3 * blk);
+    D *Tx = eig_blk.as<D>(), *X0b = Tx + n * lob::kMaxK, *Gn = X0b + n * lob::kMaxK;  // the tile's X, the next start, generated columns
+    // (the partials are asked for at every use: the tile grows ir_part, and a pointer taken before it would dangle)
+    D *Y = nullptr, *BY = nullptr;
+    auto blocks = [&] {  // (allocated at the first use: a run of one sweep without constraints never needs them)
+      eig_blocks(true, GEN);
+      Y = eig_Y.as<D>(), BY = GEN ? eig_BY.as<D>() : Y;
+    };
+    if (m0 > 0) {
+      blocks();
+      vec_op(1, n, m0, Y, kEigMaxM, dY, ldy, nullptr, 0);
+      if (GEN) spmm_launch(Bm, (const D *)Y, kEigMaxM, BY, kEigMaxM, m0, stream);
+      const double off = eig_orthonormality(m0, Y, BY, eig_partials());
+      check_device_error();
+      if (!(off <= 1e-10)) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "eigs: the constraint block Y is not B-orthonormal (max |Y^H B Y - I| = %.3g > 1e-10); "
+                      "orthonormalize it first", off);
+        throw Error(HIFAMD_BAD_PREC, msg);
+      }
+    }
+    vec_op(0, n, nev, dX, ldx, nullptr, 0, nullptr, 0);
+    for (int c = 0; c < nev; ++c) {
+      if (lambda) lambda[c] = std::nan("");
+      if (res) res[c] = std::nan("");
+      if (flags) flags[c] = 2;
+    }
+    int m = m0, L = 0, steps = 0, minrank = 3 * k;
+    const D *x0 = dX0;
+    int64_t ld0 = ldx0;
+    for (int t = 0;; ++t) {
+      const int want = lob::sweep_want(nev, L, k, guard);
+      double lam[lob::kMaxK], rs[lob::kMaxK];
+      int fl[lob::kMaxK], info3[3];
+      EigLock lock;
+      lock.Y = Y, lock.BY = BY, lock.m = m;
+      lobpcg_tile<GEN>(x0, ld0, seed, k, want, tol, deftol, maxit, rank, Tx, k, lam, rs, fl, info3, lock);
+      steps += info3[0], minrank = std::min(minrank, info3[1]);
+      const int p = lob::lock_prefix(fl, want);
+      eig_sweeps.insert(eig_sweeps.end(), {want, p, info3[0]});
+      const int shown = p > 0 ? p : want;  // columns of the tile that reach the output
+      if (p > 0 && m > 0) eig_project(m, Y, BY, kEigMaxM, p, Tx, k, eig_partials());
+      vec_op(1, n, shown, dX + L, ldx, (const D *)Tx, k, nullptr, 0);
+      for (int c = 0; c < shown; ++c) {
+        if (lambda) lambda[L + c] = lam[c];
+        if (res) res[L + c] = rs[c];
+        if (flags) flags[L + c] = p > 0 ? 0 : lob::unlocked_flag(fl[c]);
+      }
+      if (p == 0) break;
+      if (L + p == nev) {
+        L += p;
+        break;
+      }
+      blocks();
+      vec_op(1, n, p, Y + m, kEigMaxM, (const D *)Tx, k, nullptr, 0);
+      if (GEN) spmm_launch(Bm, (const D *)(Y + m), kEigMaxM, BY + m, kEigMaxM, p, stream);
+      m += p, L += p;
+      // the next start block: the unconverged columns p .. k - 1 in their order, then p generated ones (the generator
+      // fills a whole [n][p] block, so they pass through Gn)
+      if (k - p > 0) vec_op(1, n, k - p, X0b, k, (const D *)(Tx + p), k, nullptr, 0);
+      hipLaunchKernelGGL((k_idr_pfill<D>), dim3(vec_grid(n * p)), dim3(256), 0, stream, n, p, p, seed + (uint64_t)t + 1, Gn);
+      vec_op(1, n, p, X0b + (k - p), k, (const D *)Gn, p, nullptr, 0);
+      HIP_OK(hipGetLastError());
+      x0 = X0b, ld0 = k;
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    check_device_error();
+    if (info4) info4[0] = steps, info4[1] = (int)(eig_sweeps.size() / 3), info4[2] = L, info4[3] = minrank;
+  }
+  void eigs_dev(bool gen, int64_t nev, int64_t k, int64_t guard, const D *dY, int64_t ldy, int64_t m0, const D *dX0, int64_t ldx0,
+                uint64_t seed, double tol, double deftol, int maxit, int64_t rank, double *lambda, D *dX, int64_t ldx, double *res,
+                int *flags, int *info4) {
+    eigs_check(gen, nev, k, guard, dY != nullptr, ldy, m0, dX0 != nullptr, ldx0, tol, deftol, maxit, ldx);
+    if (!dX) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    if (gen)
+      eigs_run<true>((int)nev, (int)k, (int)guard, dY, ldy, (int)m0, dX0, ldx0, seed, tol, deftol, maxit, rank, lambda, dX, ldx, res,
+                     flags, info4);
+    else
+      eigs_run<false>((int)nev, (int)k, (int)guard, dY, ldy, (int)m0, dX0, ldx0, seed, tol, deftol, maxit, rank, lambda, dX, ldx, res,
+                      flags, info4);
+  }
+  void eigs_host(bool gen, int64_t nev, int64_t k, int64_t guard, const T *Y, int64_t ldy, int64_t m0, const T *X0, int64_t ldx0,
+                 uint64_t seed, double tol, double deftol, int maxit, int64_t rank, double *lambda, T *X, int64_t ldx, double *res,
+                 int *flags, int *info4) {
+    eigs_check(gen, nev, k, guard, Y != nullptr, ldy, m0, X0 != nullptr, ldx0, tol, deftol, maxit, ldx);
+    if (!X) throw Error(HIFAMD_NULL_OBJ, "NULL vector");
+    HIP_OK(hipSetDevice(device));
+    const int64_t n = lv[0]->n;
+    const size_t nx0 = (size_t)n * k * sizeof(T), nx = (size_t)n * nev * sizeof(T), ny = (size_t)n * std::max<int64_t>(m0, 1) * sizeof(T);
+    if (stage_b.bytes < nx0) stage_b.alloc(nx0);
+    if (stage_x.bytes < nx) stage_x.alloc(nx);
+    if (m0 > 0 && stage_r.bytes < ny) stage_r.alloc(ny);
+    StreamWait wait{stream};
+    if (X0) HIP_OK(hipMemcpy2DAsync(stage_b.p, k * sizeof(T), X0, ldx0 * sizeof(T), k * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    if (m0 > 0) HIP_OK(hipMemcpy2DAsync(stage_r.p, m0 * sizeof(T), Y, ldy * sizeof(T), m0 * sizeof(T), n, hipMemcpyHostToDevice, stream));
+    eigs_dev(gen, nev, k, guard, m0 > 0 ? (const D *)stage_r.as<D>() : nullptr, m0, m0, X0 ? (const D *)stage_b.as<D>() : nullptr, k, seed,
+             tol, deftol, maxit, rank, lambda, stage_x.as<D>(), nev, res, flags, info4);
+    HIP_OK(hipMemcpy2DAsync(X, ldx * sizeof(T), stage_x.p, nev * sizeof(T), nev * sizeof(T), n, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+  }
+  // (want, locked, steps) of every sweep of the last eigs call on this engine -> the number of sweeps; at most cap triples are written
+  int eigs_sweeps(int *out, int cap) const {
+    const int ns = (int)(eig_sweeps.size() / 3);
+    for (int i = 0; out && i < std::min(ns, cap) * 3; ++i) out[i] = eig_sweeps[(size_t)i];
+    return ns;
   }
 
   // ---- restarted block GCR for a general pair (A, M): block CG's shared space without its conditions ------------
@@ -4938,6 +5179,45 @@ HifAmdStatus hifamd_lobpcg_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *
     E.lobpcg_dev(false, k, nev, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx, res, flags, info3);
   });
   API_END
+}
+
+HifAmdStatus hifamd_eig_project(HifAmdHdl h, int gen, int64_t m, const void *Y, int64_t ldy, int64_t kw, void *W, int64_t ldw) {
+  API_BEGIN
+  visit(h, [&](auto &E) { E.eig_project_host(gen != 0, m, E.val(Y), ldy, kw, E.val(W), ldw); });
+  API_END
+}
+
+HifAmdStatus hifamd_eig_project_dev(HifAmdHdl h, int gen, int64_t m, const void *dY, int64_t ldy, int64_t kw, void *dW, int64_t ldw) {
+  API_BEGIN
+  visit(h, [&](auto &E) { E.eig_project_dev(gen != 0, m, E.dev(dY), ldy, kw, E.dev(dW), ldw); });
+  API_END
+}
+
+HifAmdStatus hifamd_eigs(HifAmdHdl h, int gen, int64_t nev, int64_t k, int64_t guard, const void *Y, int64_t ldy, int64_t m0,
+                         const void *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit, int64_t rank,
+                         double *lambda, void *X, int64_t ldx, double *res, int *flags, int *info4) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.eigs_host(gen != 0, nev, k, guard, E.val(Y), ldy, m0, E.val(X0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.val(X), ldx, res,
+                flags, info4);
+  });
+  API_END
+}
+
+HifAmdStatus hifamd_eigs_dev(HifAmdHdl h, int gen, int64_t nev, int64_t k, int64_t guard, const void *dY, int64_t ldy, int64_t m0,
+                             const void *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit, int64_t rank,
+                             double *lambda, void *dX, int64_t ldx, double *res, int *flags, int *info4) {
+  API_BEGIN
+  visit(h, [&](auto &E) {
+    E.eigs_dev(gen != 0, nev, k, guard, E.dev(dY), ldy, m0, E.dev(dX0), ldx0, seed, tol, deftol, maxit, rank, lambda, E.dev(dX), ldx,
+               res, flags, info4);
+  });
+  API_END
+}
+
+int hifamd_eigs_sweeps(HifAmdHdl h, int *out, int cap) {
+  if (!h || !h->eng) return -1;
+  return visit(h, [&](auto &E) { return E.eigs_sweeps(out, cap); });
 }
 
 HifAmdStatus hifamd_set_mass_matrix(HifAmdHdl h, int64_t n, const int64_t *indptr, const int32_t *indices, const void *vals) {

@@ -6638,4 +6638,146 @@ __global__ void __launch_bounds__(256) k_lob_small(int mode, int step, const dou
   if (mode == 1 || mode == 3) lob::ritz_step(Sm, W, mode == 1, step, tm);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The B-orthogonal projector of the locked LOBPCG sweeps (Engine::eig_project, Engine::eigs_dev): W <- W - Y C with
+// C = (BY)^H W for a block Y of m <= 128 locked, B-orthonormal vectors ([n][m], row stride ldy; BY the same shape, and on the
+// standard problem the same pointer) and a block W of kw <= 16 columns with any row stride (the W block of S in the driver).
+//   k_eig_cgram   partials of C ([128][16] per workgroup), rows as the K dimension of v_mfma_f64_16x16x4_f64: the conjugated
+//                 strip of BY is the left operand, the strip of W the right one, one accumulator per 16-column tile of BY
+//   k_eig_csum    C = the partials in block order (one thread per entry, as k_bcg_sum)
+//   k_eig_cproj   the row-local product [n][m] . [m][16] subtracted from W in place, C staged in LDS
+// Lane maps, complex handles on real planes, partials in wave order, then block order, no atomics: as block CG above.  A
+// column of W that is exactly zero gives an exactly zero column of C and keeps its bits; a column's values depend on no
+// other column of W.
+// ---------------------------------------------------------------------------------------------
+constexpr int kEigMaxM = 128;  // widest block of locked vectors
+constexpr int kEigTiles = kEigMaxM / 16;
+
+// element (row, col) of an [n][ld] block whose first `cols` columns are in use, an exact zero outside; the load is unconditional
+template <class T>
+__device__ __forceinline__ T eig_load(const T *__restrict__ x, int64_t n, int64_t ld, int cols, int64_t row, int col) {
+  const bool ok = row < n && col < cols;
+  const T v = x[ok ? row * ld + col : 0];
+  return ok ? v : vzero(T());
+}
+
+// partial[blockIdx.x] ([128][16]; rows < 16 ceil(m / 16) are written) = the block's share of (BY)^H W.  Wave w of block b
+// owns the row groups g = 4 b + w + j * 4 gridDim.x (rows 4 g .. 4 g + 3, one K step each), two of them in flight; only the
+// tiles that m needs are loaded and multiplied.
+template <class T>
+__global__ void __launch_bounds__(256) k_eig_cgram(int64_t n, int m, const T *__restrict__ BY, int64_t ldy, int kw,
+                                                   const T *__restrict__ W, int64_t ldw,
+                                                   T *__restrict__ partial /* [gridDim.x][128][16] */) {
+  __shared__ T lds[kEigMaxM * 16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int nt = (m + 15) >> 4;
+  BcgAcc<T> acc[kEigTiles];
+#pragma unroll
+  for (int t = 0; t < kEigTiles; ++t) bcg_clear(acc[t]);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t g = (int64_t)blockIdx.x * 4 + wave; 4 * g < n; g += 2 * stride) {
+    T a[2][kEigTiles], b[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int64_t row = 4 * (g + u * stride) + kq;
+      b[u] = eig_load(W, n, ldw, kw, row, ci);
+#pragma unroll
+      for (int t = 0; t < kEigTiles; ++t) {
+        a[u][t] = vzero(T());
+        if (t < nt) a[u][t] = vconj(eig_load(BY, n, ldy, m, row, 16 * t + ci));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int t = 0; t < kEigTiles; ++t)
+        if (t < nt) bcg_mma(acc[t], a[u][t], b[u]);
+  }
+  // the four waves of the block in wave order
+  for (int w = 1; w < 4; ++w) {
+    __syncthreads();
+    if (wave == w) {
+#pragma unroll
+      for (int t = 0; t < kEigTiles; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) lds[(16 * t + kq + 4 * reg) * 16 + ci] = bcg_get(acc[t], reg);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int t = 0; t < kEigTiles; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const T v = lds[(16 * t + kq + 4 * reg) * 16 + ci];
+          if constexpr (std::is_same<T, cplx>::value)
+            acc[t].re[reg] += v.x, acc[t].im[reg] += v.y;
+          else
+            acc[t].re[reg] += v;
+        }
+    }
+  }
+  if (wave != 0) return;
+  T *__restrict__ out = partial + (int64_t)blockIdx.x * kEigMaxM * 16;
+#pragma unroll
+  for (int t = 0; t < kEigTiles; ++t)
+    if (t < nt) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) out[(16 * t + kq + 4 * reg) * 16 + ci] = bcg_get(acc[t], reg);
+    }
+}
+
+// C[e] = partial[0][e] + partial[1][e] + ... in block order, e < 16 rows (rows = 16 ceil(m / 16)); one thread per entry
+template <class T>
+__global__ void __launch_bounds__(256) k_eig_csum(const T *__restrict__ partial, int nb, int rows, T *__restrict__ C /* [128][16] */) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= rows * 16) return;
+  const T *p = partial + e;
+  T acc = p[0];
+  int b = 1;
+  for (; b + 8 <= nb; b += 8) {  // (eight loads in flight; the additions keep their order)
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(b + u) * kEigMaxM * 16];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = vadd(acc, v[u]);
+  }
+  for (; b < nb; ++b) acc = vadd(acc, p[(int64_t)b * kEigMaxM * 16]);
+  C[e] = acc;
+}
+
+// W <- W - Y C in place: C ([128][16]; rows >= 16 ceil(m / 16) are not read) is staged in LDS once per workgroup.  A wave
+// owns the 16-row strips 4 b + w + j * 4 gridDim.x and reads its strip of Y (as the left operand, four columns a K step) and
+// of W completely before it writes.
+template <class T>
+__global__ void __launch_bounds__(256) k_eig_cproj(int64_t n, int m, const T *__restrict__ Y, int64_t ldy, int kw,
+                                                   T *__restrict__ W, int64_t ldw, const T *__restrict__ C) {
+  __shared__ T cc[kEigMaxM * 16];
+  const int nt = (m + 15) >> 4;
+  for (int e = threadIdx.x; e < nt * 256; e += blockDim.x) cc[e] = C[e];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, kq = lane >> 4;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t st = (int64_t)blockIdx.x * 4 + wave; 16 * st < n; st += stride) {
+    const int64_t r0 = 16 * st;
+    T y[4 * kEigTiles], w[4];
+#pragma unroll
+    for (int kk = 0; kk < 4 * kEigTiles; ++kk) {
+      y[kk] = vzero(T());
+      if (kk < 4 * nt) y[kk] = eig_load(Y, n, ldy, m, r0 + ci, 4 * kk + kq);
+    }
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) w[reg] = eig_load((const T *)W, n, ldw, kw, r0 + kq + 4 * reg, ci);
+    BcgAcc<T> acc;
+    bcg_clear(acc);
+#pragma unroll
+    for (int kk = 0; kk < 4 * kEigTiles; ++kk)
+      if (kk < 4 * nt) bcg_mma(acc, y[kk], cc[(4 * kk + kq) * 16 + ci]);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int64_t row = r0 + kq + 4 * reg;
+      if (row < n && ci < kw) W[row * ldw + ci] = vsub(w[reg], bcg_get(acc, reg));
+    }
+  }
+}
+
 }  // namespace hifamd

@@ -395,5 +395,35 @@ HIFAMD_HD inline void ritz_step(const Small<T> &S, const RitzScratch<T> &w, bool
   tm.sync();
 }
 
+// ---- the decisions between the locked sweeps (Engine::eigs_dev): host only, no device state -------------------------------------
+constexpr int kMaxLocked = 128;  // widest constraint block: the caller's m0 columns plus the nev locked ones
+
+// columns the sweep asks its tile for: what is still wanted, at most the block without its guard columns
+inline int sweep_want(int nev, int locked, int k, int guard) {
+  const int left = nev - locked, room = k - guard;
+  return left < room ? left : room;
+}
+
+// length of the leading run of flag-0 columns among the first `want`: what the sweep locks.  (A converged column behind an
+// unconverged one is not locked: lambda comes back in lock order, ascending up to the tolerance.)
+inline int lock_prefix(const int *flags, int want) {
+  int p = 0;
+  while (p < want && flags[p] == 0) ++p;
+  return p;
+}
+
+// the flag of an output column that the last sweep left unlocked: the tile's 1 (breakdown) stays, everything else -- not
+// converged, or converged behind an unconverged column -- is 2: 0 means locked
+inline int unlocked_flag(int tile_flag) { return tile_flag == 1 ? 1 : 2; }
+
+// the sweep loop's verdict on its arguments; nullptr when they are fine (the caps of the constraint buffers)
+inline const char *sweep_args(long long nev, long long k, long long guard, long long m0) {
+  if (k < 1 || k > kMaxK) return "eigs: need 1 <= k <= 16";
+  if (guard < 0 || guard >= k) return "eigs: need 0 <= guard < k";
+  if (nev < 1) return "eigs: need nev >= 1";
+  if (m0 < 0 || m0 + nev > kMaxLocked) return "eigs: need m0 >= 0 and m0 + nev <= 128";
+  return nullptr;
+}
+
 }  // namespace lob
 }  // namespace hifamd

@@ -736,6 +736,85 @@ class HIF:
         self.last_lobpcg_info = info
         return lam, X, res, fl, int(info[0])
 
+    def _eig_block(self, V, name, like_dev):
+        """V as an [nrows][c] block the C entries take: -> (block, pointer, row stride); like_dev: it must be a CUDA tensor"""
+        if like_dev != _is_torch(V):
+            raise HifAmdError(2, f"{name}: host arrays and CUDA tensors cannot be mixed in one call")
+        if like_dev:
+            V = self._dev_block(V, name)
+            return V, V.data_ptr(), V.stride(0)
+        V = np.asarray(V)
+        if V.ndim != 2 or V.shape[0] != self.nrows():
+            raise HifAmdError(2, f"{name}: expected an [nrows][c] block")
+        if np.iscomplexobj(V) and self.dtype.kind != "c":
+            raise HifAmdError(2, f"{name}: a complex block on a {self.dtype} hierarchy")
+        V = np.ascontiguousarray(V, dtype=self.dtype)
+        return V, _p(V), V.shape[1]
+
+    def b_project(self, W, Y, gen=False):
+        """The B-orthogonal projector W <- W - Y (B Y)^H W in place (hifamd_eig_project / _dev): Y [n][m], m <= 128, with
+        B-orthonormal columns (not checked), W [n][kw], kw <= 16; B = I, or with gen the mass matrix of set_mass_matrix.
+        W: a C-contiguous host array of the handle's dtype, or a CUDA tensor with unit column stride (any row stride); Y
+        the same kind.  Returns W."""
+        dev = _is_torch(W)
+        Y, py, ldy = self._eig_block(Y, "Y", dev)
+        if dev:
+            W2 = self._dev_block(W, "W")
+            if W2.data_ptr() != W.data_ptr():
+                raise HifAmdError(2, "W: blocks must be row-interleaved (unit column stride)")
+            _check(lib().hifamd_eig_project_dev(self._h, int(bool(gen)), Y.shape[1], py, ldy, W2.shape[1], W2.data_ptr(),
+                                                W2.stride(0)))
+            return W
+        if not isinstance(W, np.ndarray) or W.dtype != self.dtype or not W.flags.c_contiguous or W.ndim != 2 \
+                or W.shape[0] != self.nrows():
+            raise HifAmdError(2, f"W: expected a C-contiguous {self.dtype} array of shape (n, kw)")
+        _check(lib().hifamd_eig_project(self._h, int(bool(gen)), Y.shape[1], py, ldy, W.shape[1], _p(W), W.shape[1]))
+        return W
+
+    def eigsh(self, nev, k=16, guard=None, gen=False, Y=None, X0=None, seed=0, tol=1e-8, maxit=200, deftol=1e-12,
+              full_rank=False):
+        """The nev smallest eigenpairs of the matrix of set_matrix (gen: of the pencil with the mass matrix of
+        set_mass_matrix) by locked LOBPCG sweeps (hifamd_eigs / _dev): blocks of k <= 16 candidates with `guard` guard
+        columns (default max(1, k // 4); 0 for k = 1), every sweep locks its leading converged columns into a block of
+        B-orthonormal constraints that all later search directions are projected against.  Y ([n][m0], B-orthonormal,
+        m0 + nev <= 128): constraints to start from -- eigenvectors of an earlier call, or a known null space, which is how
+        a singular pencil is deflated.  X0 ([n][k]) or the generated block of `seed` starts the first sweep; maxit is per
+        sweep.  Host arrays or CUDA tensors (Y and X0 of one kind).  Returns (lam, X, res, flags, info): lam [nev] in lock
+        order, X [n][nev] with X^H B X = I and Y^H B X = 0, res [nev], flags [nev] 0 locked / 1 breakdown / 2 not
+        converged, info = (total steps, sweeps, locked, smallest basis rank); last_eigsh_sweeps keeps the sweeps'
+        (want, locked, steps)."""
+        k = int(k) if X0 is None else int(X0.shape[1])
+        if guard is None:
+            guard = max(1, k // 4) if k > 1 else 0
+        given = [v for v in (Y, X0) if v is not None]
+        dev = bool(given) and _is_torch(given[0])
+        py, ldy, m0 = None, 0, 0
+        if Y is not None:
+            Y, py, ldy = self._eig_block(Y, "Y", dev)
+            m0 = int(Y.shape[1])
+        px0, ldx0 = None, 0
+        if X0 is not None:
+            X0, px0, ldx0 = self._eig_block(X0, "X0", dev)
+        nev = int(nev)
+        cols = max(nev, 1)
+        if dev:
+            import torch
+
+            X = torch.empty((self.nrows(), cols), dtype=given[0].dtype, device=given[0].device)
+            px, ldx = X.data_ptr(), X.stride(0)
+        else:
+            X = np.empty((self.nrows(), cols), dtype=self.dtype)
+            px, ldx = _p(X), cols
+        lam, res = np.zeros(cols), np.zeros(cols)
+        fl, info = np.zeros(cols, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        fn = lib().hifamd_eigs_dev if dev else lib().hifamd_eigs
+        _check(fn(self._h, int(bool(gen)), nev, k, int(guard), py, ldy, m0, px0, ldx0, int(seed), float(tol), float(deftol),
+                  int(maxit), -1 if full_rank else 0, _p(lam), px, ldx, _p(res), _p(fl), _p(info)))
+        sweeps = np.zeros((max(int(info[1]), 1), 3), dtype=np.int32)
+        ns = lib().hifamd_eigs_sweeps(self._h, _p(sweeps), sweeps.shape[0])
+        self.last_eigsh_sweeps = [tuple(int(v) for v in row) for row in sweeps[:max(ns, 0)]]
+        return lam, X, res, fl, info
+
     def bgcr(self, b, block=64, restart=10, rtol=1e-6, maxit=500, deftol=1e-12, full_rank=False):
         """Restarted block GCR (x0 = 0; block GMRES(restart) with right preconditioning in exact arithmetic) for a general
         pair (A, M) (hifamd_bgcr_batch / _dev): the columns of b ([n] or [n][nrhs], host array or CUDA tensor) are cut into

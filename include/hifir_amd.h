@@ -489,7 +489,7 @@ HifAmdStatus hifamd_bcg_batch_dev(HifAmdHdl h, const void *dB, int64_t ldb, void
  * [n][48] x [48][32] product on the f64 matrix cores, and the small matrices in one workgroup; the host reads back one
  * integer per step.  Sums run in a fixed order: the same inputs give the same bits.  The eigenvectors come back
  * orthonormal; their phase (sign) is not fixed.  Smallest eigenvalues of A only: no largest or interior ones; the
- * generalized problem A x = lambda B x is hifamd_lobpcg_gen's.  The pair has to be definite for the iteration to converge; on an indefinite pair it runs to maxit
+ * generalized problem A x = lambda B x is hifamd_lobpcg_gen's, more than k - guard eigenpairs are hifamd_eigs's.  The pair has to be definite for the iteration to converge; on an indefinite pair it runs to maxit
  * (flag 2), which is not refused.
  * Refusals, in this order: a NULL handle (HIFAMD_NULL_OBJ); k outside [1, 16], nev outside [1, k], tol <= 0, maxit < 1,
  * deftol outside (0, 1), a row stride below k (HIFAMD_MISMATCHED_SIZES); a handle that is not finalized (HIFAMD_BAD_PREC;
@@ -530,7 +530,8 @@ HifAmdStatus hifamd_set_mass_matrix(HifAmdHdl h, int64_t n, const int64_t *indpt
  * A step costs one more SpMM on k columns than hifamd_lobpcg's, and its row passes read and move a third block.  The
  * orders of summation are hifamd_lobpcg's: with an explicit identity as B the iterates are that driver's, bit for bit,
  * until the two stopping tests decide differently.  Out: lambda ascending, X with X^H B X = I, res, flags, info3 as
- * hifamd_lobpcg.  Not done here: a null-space basis under B, largest or interior eigenvalues, k > 16.
+ * hifamd_lobpcg.  Not done here: largest or interior eigenvalues; a null-space basis under B (the B-orthogonal projector) and more
+ * eigenpairs than one block of k <= 16 holds are hifamd_eigs's: the null space goes into its constraint block Y.
  * Refusals in hifamd_lobpcg's order, with: no mass matrix (hifamd_set_mass_matrix; HIFAMD_BAD_PREC) directly after no
  * matrix; after the Hermitian check ANY null-space filter on HIFAMD_S, the constant-mode one and a basis filter alike
  * (HIFAMD_BAD_PREC): the Euclidean projector I - Q Q^H would solve the pencil (A, P B P), and the B-orthogonal projector
@@ -543,6 +544,55 @@ HifAmdStatus hifamd_lobpcg_gen(HifAmdHdl h, int64_t k, int64_t nev, const void *
 HifAmdStatus hifamd_lobpcg_gen_dev(HifAmdHdl h, int64_t k, int64_t nev, const void *dX0, int64_t ldx0, uint64_t seed, double tol,
                                    double deftol, int maxit, int64_t rank, double *lambda, void *dX, int64_t ldx, double *res,
                                    int *flags, int *info3);
+
+/* ---- locked LOBPCG sweeps: up to 128 eigenpairs, constraints under B ------------------------------ */
+/* The B-orthogonal projector alone: W <- W - Y C, C = (BY)^H W, for Y ([n][m], 1 <= m <= 128, row stride ldy) with
+ * B-orthonormal columns and W ([n][kw], 1 <= kw <= 16, row stride ldw), in place.  gen == 0: B = I (BY is Y, no copy);
+ * gen != 0: B is the mass matrix and BY = B Y is formed here, 64 columns a product.  C is summed in a fixed order on the f64
+ * matrix cores (the same inputs give the same bits); a column of W that is exactly zero keeps its bits, and no column of W
+ * reads another.  Y is NOT checked for orthonormality here.  Refusals, in this order: a NULL handle; m outside [1, 128], kw
+ * outside [1, 16], a row stride below its block (HIFAMD_MISMATCHED_SIZES); a handle that is not finalized, gen without a
+ * mass matrix (HIFAMD_BAD_PREC); a NULL block (HIFAMD_NULL_OBJ).  The _dev variant takes device pointers and returns when
+ * the projection is done. */
+HifAmdStatus hifamd_eig_project(HifAmdHdl h, int gen, int64_t m, const void *Y, int64_t ldy, int64_t kw, void *W, int64_t ldw);
+HifAmdStatus hifamd_eig_project_dev(HifAmdHdl h, int gen, int64_t m, const void *dY, int64_t ldy, int64_t kw, void *dW,
+                                    int64_t ldw);
+/* The nev smallest eigenpairs of A (gen == 0) or of the pencil (A, B) (gen != 0), m0 + nev <= 128, by sweeps of
+ * hifamd_lobpcg / hifamd_lobpcg_gen on blocks of k <= 16 candidates, `guard` of them guard columns (0 <= guard < k), under
+ * the constraint block Y of locked, B-orthonormal vectors: hard locking plus constraints.
+ *   Y = the caller's m0 >= 0 columns ([n][m0], row stride ldy; NULL with m0 = 0), BY = B Y; L = 0;
+ *   X0 = the caller's block ([n][k]) or the generated one of `seed`, as hifamd_lobpcg takes or generates it
+ *   sweep t = 0, 1, ...: want = min(nev - L, k - guard); the iteration of hifamd_lobpcg(_gen) with (k, nev = want, tol,
+ *     deftol, maxit PER SWEEP) and two more operations: X <- X - Y (BY)^H X once, directly behind the start block (and the
+ *     basis filter of the standard problem) and in front of BX = B X, and W <- W - Y (BY)^H W once per step, directly
+ *     behind W = M^{-1} R and in front of AW = A W (converged columns of W stay exact zeros);
+ *     p = the length of the leading run of flag-0 columns among the first `want`; p == 0: end;
+ *     X_c = X[:, :p], projected once more, is appended to Y (generalized: B X_c is recomputed, appended to BY); L += p;
+ *     L == nev: end; the next X0 = [X[:, p:k] | p columns generated from seed + t + 1] (P is dropped)
+ * With m0 = 0 and nev <= k - guard this is one sweep without a projector launch: the bits of hifamd_lobpcg(_gen) with
+ * (k, nev).  Y and BY live in two [n][128] buffers of the handle, allocated at the first call that needs them.
+ * Out: lambda[nev] in lock order (ascending up to the tolerance), X ([n][nev], row stride ldx; X^H B X = I, Y^H B X = 0),
+ * res[nev], flags[nev]: 0 locked, 1 breakdown, 2 not converged -- the columns the last sweep asked for and did not lock
+ * carry its candidates with its flag (a converged one behind an unconverged one counts as 2), the columns never reached
+ * are zero with lambda = res = NaN and flag 2 -- and info4 = {total steps, sweeps, locked, smallest basis rank seen};
+ * lambda, res, flags, info4 may be NULL.  hifamd_eigs_sweeps returns the sweeps' (want, locked, steps).
+ * Refusals, in this order: a NULL handle; hifamd_lobpcg's argument checks with nev = want of the first sweep; guard outside
+ * [0, k), nev < 1, m0 < 0 or m0 + nev > 128, a row stride below its block (HIFAMD_MISMATCHED_SIZES); Y == NULL with m0 > 0
+ * (HIFAMD_NULL_OBJ); the handle checks of hifamd_lobpcg / hifamd_lobpcg_gen in their order -- with gen every null-space
+ * filter stays refused (the constraint block is how a null space is deflated there), on the standard problem a basis
+ * filter keeps working; a Y with max |Y^H B Y - I| > 1e-10 (HIFAMD_BAD_PREC: orthonormalizing Y is the caller's job); a
+ * sweep's start block that hifamd_lobpcg refuses.
+ * Not done here: largest or interior eigenvalues, orthonormalizing Y, more than 128 locked vectors.  Host pointers; the
+ * _dev variant takes device pointers for Y, X0 and X. */
+HifAmdStatus hifamd_eigs(HifAmdHdl h, int gen, int64_t nev, int64_t k, int64_t guard, const void *Y, int64_t ldy, int64_t m0,
+                         const void *X0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit, int64_t rank,
+                         double *lambda, void *X, int64_t ldx, double *res, int *flags, int *info4);
+HifAmdStatus hifamd_eigs_dev(HifAmdHdl h, int gen, int64_t nev, int64_t k, int64_t guard, const void *dY, int64_t ldy, int64_t m0,
+                             const void *dX0, int64_t ldx0, uint64_t seed, double tol, double deftol, int maxit, int64_t rank,
+                             double *lambda, void *dX, int64_t ldx, double *res, int *flags, int *info4);
+/* (want, locked, steps) of every sweep of the handle's last hifamd_eigs(_dev) call: at most cap triples into out (may be
+ * NULL) -> the number of sweeps, -1 for a NULL handle */
+int hifamd_eigs_sweeps(HifAmdHdl h, int *out, int cap);
 
 /* ---- restarted block GCR for a general pair (A, M): a shared block space without conditions ---- */
 /* Restarted block GCR with x0 = 0: in exact arithmetic block GMRES(restart) with right preconditioning, flexible by

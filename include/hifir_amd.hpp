@@ -381,6 +381,37 @@ class HIF {
     return lobpcg_call<ArrayType>(hifamd_lobpcg_gen, "lobpcg_gen", k, nev, X0, tol, maxit, seed, deftol, full_rank);
   }
 
+  // ---- locked LOBPCG sweeps: up to 128 eigenpairs under a block of constraints (hifamd_eigs, hifamd_eig_project) ----
+  // W <- W - Y (B Y)^H W in place: Y [n][m] (m <= 128, B-orthonormal columns), W [n][kw] (kw <= 16), both row-interleaved;
+  // gen: B is the mass matrix of set_mass_matrix, else the identity.
+  template <class ArrayType>
+  void b_project(ArrayType &W, const int kw, const ArrayType &Y, const int m, const bool gen = false) {
+    require();
+    if (m < 1 || kw < 1 || (std::size_t)Y.size() != (std::size_t)nrows() * m || (std::size_t)W.size() != (std::size_t)nrows() * kw)
+      throw std::runtime_error("hifir_amd: b_project needs Y of nrows() * m and W of nrows() * kw entries");
+    detail::check(hifamd_eig_project(_h, gen ? 1 : 0, m, Y.data(), m, kw, W.data(), kw));
+  }
+  // The nev smallest eigenpairs of A (with a Matrix B: of the pencil A x = lambda B x) by sweeps of blocks of k <= 16
+  // candidates with `guard` guard columns; Y ([n][m0], B-orthonormal, may be empty; m0 + nev <= 128) seeds the constraints,
+  // X0 ([n][k], may be empty) the first sweep; maxit is per sweep.  -> (lambda, X, res, flags, info4): lambda in lock order,
+  // X [n][nev], flags 0 locked / 1 breakdown / 2 not converged, info4 = {total steps, sweeps, locked, smallest basis rank}.
+  template <class Matrix, class ArrayType>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, std::vector<int>> eigsh(
+      const Matrix &A, const int nev, const int k, const int guard, const ArrayType &Y, const int m0, const ArrayType &X0,
+      const double tol, const int maxit, const std::uint64_t seed = 0, const double deftol = 1e-12, const bool full_rank = false) {
+    ensure_matrix(A);
+    return eigs_call(false, nev, k, guard, Y, m0, X0, tol, maxit, seed, deftol, full_rank);
+  }
+  template <class Matrix, class ArrayType>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, std::vector<int>> eigsh(
+      const Matrix &A, const Matrix &B, const int nev, const int k, const int guard, const ArrayType &Y, const int m0,
+      const ArrayType &X0, const double tol, const int maxit, const std::uint64_t seed = 0, const double deftol = 1e-12,
+      const bool full_rank = false) {
+    ensure_matrix(A);
+    if (!_has_B) set_mass_matrix(B);
+    return eigs_call(true, nev, k, guard, Y, m0, X0, tol, maxit, seed, deftol, full_rank);
+  }
+
   // ---- symmetric QMR for a Hermitian indefinite pair (A, M) on the device (hifamd_sqmr_batch) ----
   // Needs an is_symm hierarchy: is_hermitian(); neither A nor M has to be definite.  iters counts iterations (one apply
   // plus one SpMM each); flag 0 converged, 1 breakdown, 2 reached maxit.
@@ -437,6 +468,21 @@ class HIF {
     detail::check(entry(_h, k, nev, X0.size() ? X0.data() : nullptr, k, seed, tol, deftol, maxit, full_rank ? -1 : 0, lambda.data(),
                         X.data(), k, res.data(), flags.data(), info3));
     return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), info3[0]);
+  }
+  template <class ArrayType>
+  std::tuple<std::vector<double>, ArrayType, std::vector<double>, std::vector<int>, std::vector<int>> eigs_call(
+      const bool gen, const int nev, const int k, const int guard, const ArrayType &Y, const int m0, const ArrayType &X0,
+      const double tol, const int maxit, const std::uint64_t seed, const double deftol, const bool full_rank) {
+    if (nev < 1 || k < 1 || m0 < 0) throw std::runtime_error("hifir_amd: eigsh needs nev >= 1, k >= 1 and m0 >= 0");
+    if ((std::size_t)Y.size() != (std::size_t)nrows() * m0 || (X0.size() && (std::size_t)X0.size() != (std::size_t)nrows() * k))
+      throw std::runtime_error("hifir_amd: eigsh needs Y of nrows() * m0 entries and an empty X0 or one of nrows() * k entries");
+    ArrayType X((std::size_t)nrows() * nev);
+    std::vector<double> lambda(nev, 0.0), res(nev, 0.0);
+    std::vector<int> flags(nev, 0), info4(4, 0);
+    detail::check(hifamd_eigs(_h, gen ? 1 : 0, nev, k, guard, m0 ? Y.data() : nullptr, m0, m0, X0.size() ? X0.data() : nullptr, k, seed,
+                              tol, deftol, maxit, full_rank ? -1 : 0, lambda.data(), X.data(), nev, res.data(), flags.data(),
+                              info4.data()));
+    return std::make_tuple(std::move(lambda), std::move(X), std::move(res), std::move(flags), std::move(info4));
   }
   void require() const {
     if (!_h) throw std::runtime_error("hifir_amd: MILU-Prec is empty!");  // builder.hpp:412
